@@ -2,8 +2,13 @@
 """bench.py -- clerk share-combine throughput on MI355X (BASELINE.json metric), plus packed-Shamir
 share-gen / reveal and ChaCha mask-combine side legs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the result checks, the
+side legs (signed combine, host path, multi-device handle, packed Shamir, ChaCha, codec, snapshot, role
+pipelines) and the CPU baseline to the same line.  --dump-outputs DIR writes the last timed step's result
+as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 
 Step = one exact clerk combine (combiner.rs:16-28) of this rank's 10,000 x 1,000,000 i64 share
 matrix (BASELINE.json configs[1]), HBM-resident before timing starts.  With N > 1 ranks every rank
@@ -70,7 +75,39 @@ def parse():
     ap.add_argument("--pipeline-dim", type=int, default=10_000_000, help="vector dimension of the role pipelines")
     ap.add_argument("--only", choices=["combine", "shamir", "chacha", "codec", "snapshot", "pipelines"], default=None,
                     help="profile helper: run just one leg (no JSON contract)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the result checks, the signed, host-path, "
+                         "multi-device, packed-Shamir, ChaCha, codec, snapshot and pipeline legs and the CPU baseline "
+                         "(each still has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full and args.only is None:
+        # a plain run: set up, warm up, time the steps, print the line -- nothing else
+        args.no_side = args.no_cpu = args.no_host_path = args.no_multi_device = True
+        args.no_signed_split = args.no_check = True
+    return args
+
+
+DUMP_LIMIT_BYTES = 60_000_000    # array data of one dump, all files together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: write each named device tensor as <directory>/<name>.npy in float64 (the engine's
+    int64 results lie in (-2^31, 2^31), so the conversion is exact).  If all of them together would pass
+    DUMP_LIMIT_BYTES, each is cut to an equal budget by a fixed, seeded sample of its elements (sorted indices,
+    the same from run to run)."""
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // 8 // max(1, len(arrays))
+    whole = sum(t.numel() for t in arrays.values()) * 8 <= DUMP_LIMIT_BYTES
+    for name, t in arrays.items():
+        a = t.detach().reshape(-1).cpu().numpy()
+        if not whole and a.size > budget:
+            pick = np.sort(np.random.default_rng(SEED_BASE).choice(a.size, size=budget, replace=False))
+            a = a[pick]
+        np.save(os.path.join(directory, name + ".npy"), a.astype(np.float64))
 
 
 class Timer:
@@ -570,6 +607,8 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
         kernel_ms = ktimer.mean_ms()
+        if args.dump_outputs and rank == 0:      # the last timed step's result (after the all-reduce at N > 1)
+            dump_outputs(args.dump_outputs, {"combine": out})
         # check the last step's result on 4096 sampled columns
         cols = torch.randint(0, D, (4096,), device=dev, generator=torch.Generator(device=dev).manual_seed(7))
         if args.no_check:
@@ -1086,7 +1125,9 @@ def run_config4(args, torch, dist, eng, dev, stream, barrier, world, rank, backe
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    ok = torch.equal(out, sec)                 # positive(unmask(reveal)) == the secrets, every element
+    if args.dump_outputs and rank == 0:          # the combined mask (all ranks') and this rank's revealed slice
+        dump_outputs(args.dump_outputs, {"mask": mask, "revealed": out})
+    ok = torch.equal(out, sec)                # positive(unmask(reveal)) == the secrets, every element
     if world > 1:
         okt = torch.tensor([1 if ok else 0], dtype=torch.int64, device=dev)
         dist.all_reduce(okt, op=dist.ReduceOp.MIN)

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof_${1:-r01}
 mkdir -p $OUT
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
-    python3 bench.py --steps 10 --warmup 2 --no-cpu > $OUT/bench_traced.json 2> $OUT/bench_traced.log || exit $?
+    python3 bench.py --full --steps 10 --warmup 2 --no-cpu > $OUT/bench_traced.json 2> $OUT/bench_traced.log || exit $?
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 120 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$c -o run -- \
       python3 bench.py --only combine --steps 3 --warmup 1 --no-check > $OUT/pmc_$c.log 2>&1 || exit $?

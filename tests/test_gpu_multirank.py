@@ -117,8 +117,8 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     root = os.path.dirname(HERE)
     env = dict(os.environ, SDA_DIST_BACKEND="gloo", PYTHONUNBUFFERED="1")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--no-side", "--no-cpu", "--steps", "2",
-           "--warmup", "1", "--rows", "64", "--dim", "200000"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--no-side", "--no-cpu",
+           "--steps", "2", "--warmup", "1", "--rows", "64", "--dim", "200000"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=170)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
