@@ -33,7 +33,7 @@ $(OBJDIR)/packed_reveal_%.o: $(CSRC)/packed_reveal.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -DSDA_REVEAL_PART=$* -c $< -o $@
 
-$(OBJDIR)/engine.o: $(CSRC)/engine.cpp $(HDRS)
+$(OBJDIR)/engine.o: $(CSRC)/engine.cpp $(CSRC)/host_pack.h $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -x hip -c $< -o $@
 

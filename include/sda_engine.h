@@ -191,6 +191,32 @@ sda_status sda_combine_accumulate_dev(sda_engine* h, int64_t modulus, const int6
                                       uint64_t n, uint64_t dim, uint64_t row_stride,
                                       int64_t* inout, void* stream);
 
+/* int32 share rows as an input type of the combine: shares [n][dim] int32, `row_stride` in int32 elements.
+ * Every shipped configuration has |share| < m <= 2^31, so half of an i64 row is sign extension; these entry
+ * points read half the bytes.  The rows are sign-extended and run through the same recurrence: the i64 result
+ * is bit-identical to widening the rows and calling sda_combine_dev / sda_combine_accumulate_dev, for every
+ * modulus.  Argument checks, the n == 0 behaviour and the stream ordering are those of the i64 entry points;
+ * accumulate calls of the two widths may alternate on one `inout`. */
+sda_status sda_combine32_dev(sda_engine* h, int64_t modulus, const int32_t* shares, uint64_t n, uint64_t dim,
+                             uint64_t row_stride, int64_t* out, void* stream);
+sda_status sda_combine32_accumulate_dev(sda_engine* h, int64_t modulus, const int32_t* shares, uint64_t n,
+                                        uint64_t dim, uint64_t row_stride, int64_t* inout, void* stream);
+
+/* dst[n][dim] (int32, row stride dst_stride) = (int32_t)src[n][dim] (i64, row stride src_stride), on the
+ * device.  flag: device int64[1], zeroed by the caller; set to 1 (never cleared) when some element lies
+ * outside [-2^31, 2^31 - 1] -- dst is then not a copy of src.  No condition on any modulus: the values only
+ * have to fit. */
+sda_status sda_narrow32_dev(sda_engine* h, const int64_t* src, uint64_t n, uint64_t dim, uint64_t src_stride,
+                            int32_t* dst, uint64_t dst_stride, int64_t* flag, void* stream);
+
+/* Counters of the row-tile stream of i64 host rows (sda_share_combine, the Full sda_mask_combine, the Additive
+ * sda_secret_reconstruct), cumulative since the handle was created, summed over a multi-device handle's
+ * devices: tiles staged as int32 rows (every value of the tile fitted; SDA_HOST_NARROW) and as
+ * i64 rows, and the bytes of their host -> device copies.  Any pointer may be NULL.
+ * sda_clerk_decode_combine's stream is not counted. */
+sda_status sda_host_stream_stats(const sda_engine* h, uint64_t* tiles_i32, uint64_t* tiles_i64,
+                                 uint64_t* bytes_h2d);
+
 /* Multi-GPU finalize: `sums` are the int64 sums (RCCL-reduced; |sum| <= 2^63 - 1, signed allowed)
  * of per-GPU combine results; out = their canonical residue in [0, m).  Exact w.r.t. the reference
  * when all combined inputs were non-negative. */

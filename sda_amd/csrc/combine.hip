@@ -13,7 +13,7 @@
 // the once-read stream from thrashing L2/MALL.
 //
 // Roofline: HBM.  Algorithmic bytes per launch = 8 * n * dim (read) + 8 * dim (write)
-// (4 * n * dim read for the int32 rows of the clerk's decode -> combine).
+// (4 * n * dim read for int32 rows: the clerk's decode -> combine, sda_combine32_dev, the half-width host stream).
 #include <stdlib.h>
 
 #include "kernels.h"
@@ -405,21 +405,117 @@ hipError_t launch_split_resolve(const int64_t* total, const int32_t* code, uint6
     return hipGetLastError();
 }
 
+namespace {
+
+// the codec's int32 kernels: 2 columns per lane (8-byte loads: the i64 kernel's grid) or, with
+// SDA_COMBINE32_VEC=4 (A/B knob), 4 (16-byte loads, half the lanes); unpipelined, 8 rows per batch
+template <bool ACC>
+hipError_t combine32_narrow_lanes(const int32_t* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* out,
+                                  const Mod64& M, bool small_m, hipStream_t s, bool want4) {
+    const uintptr_t a = (uintptr_t)in, o = (uintptr_t)out;
+    if (want4 && dim % 4 == 0 && stride % 4 == 0 && a % 16 == 0 && o % 32 == 0)
+        return launch_vec<int32_t, 4, 8, ACC>(in, n, dim, stride, out, M, small_m, s);
+    const bool v2 = dim % 2 == 0 && stride % 2 == 0 && a % 8 == 0 && o % 16 == 0;
+    return v2 ? launch_vec<int32_t, 2, 8, ACC>(in, n, dim, stride, out, M, small_m, s)
+              : launch_vec<int32_t, 1, 8, ACC>(in, n, dim, stride, out, M, small_m, s);
+}
+
+// The int32 share rows of the public entry points (sda_combine32_dev, the half-width host stream): 4 columns
+// per lane -- a 16-byte load and a 32-byte result per lane -- software-pipelined on the balanced grid like the
+// i64 default (SDA_COMBINE_PIPE=0 / SDA_COMBINE_BALANCE=0 switch it the same way).  Two buffers of kWide32Rows
+// = 2 rows: four accumulators and the m > 2^62 slow path cost more registers than the i64 kernel's two, and 4
+// rows per buffer take 74-78 VGPRs (6 waves per SIMD), 3 rows 62-66; 2 rows take 50-54 and measured fastest
+// (10k x 1M in one process, scripts/combine32_inproc.py: 6.31 ms at 2 rows, 6.50 at 3, 7.44 at 4, 6.78
+// unpipelined at 8, 6.67 for the codec's 2-column kernel).  Rows that do not line up for 16-byte
+// loads take the codec's kernels.  SDA_COMBINE32_VEC=2 (A/B knob) sends every shape there.
+constexpr int kWide32Rows = 2;
+template <bool ACC>
+hipError_t combine32_wide_lanes(const int32_t* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* out,
+                                const Mod64& M, bool small_m, hipStream_t s) {
+    const char* env = getenv("SDA_COMBINE32_VEC");
+    const bool want4 = !(env && atoi(env) == 2);
+    const uintptr_t a = (uintptr_t)in, o = (uintptr_t)out;
+    if (want4 && combine_pipe() && dim % 4 == 0 && stride % 4 == 0 && a % 16 == 0 && o % 32 == 0)
+        return launch_vec<int32_t, 4, kWide32Rows, ACC, false, true>(in, n, dim, stride, out, M, small_m, s);
+    return combine32_narrow_lanes<ACC>(in, n, dim, stride, out, M, small_m, s, want4);
+}
+
+// dst = (int32_t)src over [n][dim] (row strides in elements); flag[0] = 1 when a value does not fit (every
+// writer stores the same 1: plain stores, the split kernel's convention).  One lane narrows QUAD adjacent
+// columns of the rows blockIdx.y, blockIdx.y + gridDim.y, ...: with QUAD = 4, two 16-byte nontemporal loads
+// and one 16-byte store per row (the row's last dim % 4 columns go element by element); QUAD = 1 is the
+// scalar kernel of shapes that do not line up.  Roofline: HBM, 12 bytes per element.  (More rows in flight per
+// lane -- 2 or 4 rows' loads before the first store -- measured the same within 0.5 %: occupancy covers it.)
+template <int QUAD>
+__global__ __launch_bounds__(256) void narrow32_kernel(const int64_t* __restrict__ src, uint64_t n, uint64_t dim,
+                                                       uint64_t src_stride, int32_t* __restrict__ dst,
+                                                       uint64_t dst_stride, int64_t* __restrict__ flag) {
+    const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * QUAD;
+    if (c >= dim) return;
+    uint32_t bad = 0;
+    auto fits = [&](int64_t v) {
+        bad |= (uint32_t)((uint64_t)v + 0x80000000ull > 0xFFFFFFFFull);
+        return (int32_t)v;
+    };
+    for (uint64_t r = blockIdx.y; r < n; r += gridDim.y) {
+        const int64_t* s = src + r * src_stride + c;
+        int32_t* d = dst + r * dst_stride + c;
+        if (QUAD == 4 && c + 4 <= dim) {
+            typedef int64_t L2 __attribute__((ext_vector_type(2)));
+            typedef int32_t I4 __attribute__((ext_vector_type(4)));
+            const L2 lo = __builtin_nontemporal_load(reinterpret_cast<const L2*>(s));
+            const L2 hi = __builtin_nontemporal_load(reinterpret_cast<const L2*>(s) + 1);
+            I4 o;
+            o[0] = fits(lo[0]);
+            o[1] = fits(lo[1]);
+            o[2] = fits(hi[0]);
+            o[3] = fits(hi[1]);
+            *reinterpret_cast<I4*>(d) = o;
+        } else {
+            const uint64_t e1 = dim - c < (uint64_t)QUAD ? dim - c : (uint64_t)QUAD;
+            for (uint64_t e = 0; e < e1; ++e) d[e] = fits(__builtin_nontemporal_load(s + e));
+        }
+    }
+    if (bad) flag[0] = 1;
+}
+
+}  // namespace
+
 hipError_t launch_combine_exact32(const int32_t* in, uint64_t n, uint64_t dim, uint64_t stride,
-                                  int64_t* out, int64_t modulus, hipStream_t s) {
+                                  int64_t* out, int64_t modulus, hipStream_t s, bool accumulate) {
     if (dim == 0) return hipSuccess;
     const Mod64 M = make_mod64(modulus);
     const bool small_m = modulus <= ((int64_t)1 << 62);
-    // 2 columns per lane (8-byte loads: the i64 kernel's grid) or, with SDA_COMBINE32_VEC=4 (A/B knob),
-    // 4 (16-byte loads, half the lanes)
     const char* env = getenv("SDA_COMBINE32_VEC");
     const bool want4 = env && atoi(env) == 4;
-    const uintptr_t a = (uintptr_t)in, o = (uintptr_t)out;
-    if (want4 && dim % 4 == 0 && stride % 4 == 0 && a % 16 == 0 && o % 32 == 0)
-        return launch_vec<int32_t, 4, 8, false>(in, n, dim, stride, out, M, small_m, s);
-    const bool v2 = dim % 2 == 0 && stride % 2 == 0 && a % 8 == 0 && o % 16 == 0;
-    return v2 ? launch_vec<int32_t, 2, 8, false>(in, n, dim, stride, out, M, small_m, s)
-              : launch_vec<int32_t, 1, 8, false>(in, n, dim, stride, out, M, small_m, s);
+    return accumulate ? combine32_narrow_lanes<true>(in, n, dim, stride, out, M, small_m, s, want4)
+                      : combine32_narrow_lanes<false>(in, n, dim, stride, out, M, small_m, s, want4);
+}
+
+hipError_t launch_combine_wide32(const int32_t* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* out,
+                                 int64_t modulus, hipStream_t s, bool accumulate) {
+    if (dim == 0) return hipSuccess;
+    const Mod64 M = make_mod64(modulus);
+    const bool small_m = modulus <= ((int64_t)1 << 62);
+    return accumulate ? combine32_wide_lanes<true>(in, n, dim, stride, out, M, small_m, s)
+                      : combine32_wide_lanes<false>(in, n, dim, stride, out, M, small_m, s);
+}
+
+hipError_t launch_narrow32(const int64_t* src, uint64_t n, uint64_t dim, uint64_t src_stride, int32_t* dst,
+                           uint64_t dst_stride, int64_t* flag, hipStream_t s) {
+    if (n == 0 || dim == 0) return hipSuccess;
+    const bool quad = (uintptr_t)src % 16 == 0 && src_stride % 2 == 0 && (uintptr_t)dst % 16 == 0 &&
+                      dst_stride % 4 == 0;
+    const uint64_t lanes = quad ? (dim + 3) / 4 : dim;
+    const uint64_t bx = (lanes + 255) / 256;
+    if (bx > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    // every row its own workgroup row up to the grid's y limit; lanes loop past it
+    const dim3 grid((unsigned)bx, (unsigned)(n < 65535 ? n : 65535));
+    if (quad)
+        hipLaunchKernelGGL(narrow32_kernel<4>, grid, dim3(256), 0, s, src, n, dim, src_stride, dst, dst_stride, flag);
+    else
+        hipLaunchKernelGGL(narrow32_kernel<1>, grid, dim3(256), 0, s, src, n, dim, src_stride, dst, dst_stride, flag);
+    return hipGetLastError();
 }
 
 hipError_t launch_mod_canonical(const int64_t* sums, uint64_t dim, int64_t* out, int64_t modulus,

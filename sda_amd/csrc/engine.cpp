@@ -22,6 +22,7 @@
 #include <thread>
 #include <vector>
 
+#include "host_pack.h"
 #include "kernels.h"
 
 struct sda_engine {
@@ -57,6 +58,9 @@ struct sda_engine {
     size_t hs_pin_bytes = 0;
     void* hs_dev = nullptr;       // device: 2 tiles + the accumulator
     size_t hs_dev_bytes = 0;
+    // sda_host_stream_stats: tiles staged as int32 / as i64 and the bytes of their host -> device copies, since
+    // the handle was created (a sub-handle is driven by one host thread at a time)
+    uint64_t hs_tiles32 = 0, hs_tiles64 = 0, hs_bytes_h2d = 0;
     // a handle over G devices (sda_engine_create_multi): sub[0] is this handle, sub[1..G) are owned
     // single-device handles; empty for a single-device handle
     std::vector<sda_engine*> sub;
@@ -734,6 +738,62 @@ sda_status sda_combine_accumulate_dev(sda_engine* h, int64_t modulus, const int6
     HIP_TRY(hipSetDevice(h->device));
     if (n == 0) return ok();
     HIP_TRY(sda::launch_combine_exact(shares, n, dim, n > 1 ? row_stride : dim, inout, m, pick(h, stream), true));
+    return ok();
+}
+
+// int32 share rows (|v| < 2^31: every shipped configuration): half the bytes per share; the kernels sign-extend
+// and run the i64 recurrence, so the result is that of the widened rows for any modulus
+sda_status sda_combine32_dev(sda_engine* h, int64_t modulus, const int32_t* shares, uint64_t n, uint64_t dim,
+                             uint64_t row_stride, int64_t* out, void* stream) {
+    SDA_ENTRY;
+    if (!h || (dim && (!out || (n && !shares)))) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n > 1 && row_stride < dim) return fail(SDA_ERR_INVALID_ARGUMENT, "row_stride < dim");
+    int64_t m;
+    if (sda_status st = modulus_abs(modulus, &m)) return st;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(sda::launch_combine_wide32(shares, n, dim, n > 1 ? row_stride : dim, out, m, pick(h, stream)));
+    return ok();
+}
+
+sda_status sda_combine32_accumulate_dev(sda_engine* h, int64_t modulus, const int32_t* shares, uint64_t n,
+                                        uint64_t dim, uint64_t row_stride, int64_t* inout, void* stream) {
+    SDA_ENTRY;
+    if (!h || (dim && (!inout || (n && !shares)))) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n > 1 && row_stride < dim) return fail(SDA_ERR_INVALID_ARGUMENT, "row_stride < dim");
+    int64_t m;
+    if (sda_status st = modulus_abs(modulus, &m)) return st;
+    HIP_TRY(hipSetDevice(h->device));
+    if (n == 0) return ok();
+    HIP_TRY(sda::launch_combine_wide32(shares, n, dim, n > 1 ? row_stride : dim, inout, m, pick(h, stream), true));
+    return ok();
+}
+
+sda_status sda_narrow32_dev(sda_engine* h, const int64_t* src, uint64_t n, uint64_t dim, uint64_t src_stride,
+                            int32_t* dst, uint64_t dst_stride, int64_t* flag, void* stream) {
+    SDA_ENTRY;
+    if (!h || (n && dim && (!src || !dst || !flag))) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n > 1 && (src_stride < dim || dst_stride < dim)) return fail(SDA_ERR_INVALID_ARGUMENT, "row stride < dim");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(sda::launch_narrow32(src, n, dim, n > 1 ? src_stride : dim, dst, n > 1 ? dst_stride : dim, flag,
+                                 pick(h, stream)));
+    return ok();
+}
+
+sda_status sda_host_stream_stats(const sda_engine* h, uint64_t* tiles_i32, uint64_t* tiles_i64,
+                                 uint64_t* bytes_h2d) {
+    SDA_ENTRY;
+    if (!h) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    uint64_t t32 = 0, t64 = 0, by = 0;
+    auto add = [&](const sda_engine* e) {
+        t32 += e->hs_tiles32;
+        t64 += e->hs_tiles64;
+        by += e->hs_bytes_h2d;
+    };
+    if (h->sub.empty()) add(h);
+    for (const sda_engine* e : h->sub) add(e);           // sub[0] is the handle itself
+    if (tiles_i32) *tiles_i32 = t32;
+    if (tiles_i64) *tiles_i64 = t64;
+    if (bytes_h2d) *bytes_h2d = by;
     return ok();
 }
 
@@ -1919,6 +1979,12 @@ sda_status sda_participant_share_dev(sda_engine* h, const sda_masking_scheme* ms
 // stream; the combine continues the recurrence across tiles (launch_combine_exact, accumulate), so the
 // result is bit-identical to one pass over all rows.
 //
+// Half-width tiles (SDA_HOST_NARROW, host_narrow()): a tile is first packed as int32 (pack_rows32); when every
+// value fits -- |v| < m <= 2^31 in every shipped configuration -- it ships and combines as int32 rows
+// (launch_combine_wide32, accumulate) in half of its buffers: half the bytes over PCIe.  A tile with a value
+// that does not fit is repacked as i64, and the rest of that column chunk's tiles ship as i64 without trying,
+// so raw i64 rows cost at most one wasted pack per chunk.  sda_host_stream_stats counts both kinds.
+//
 // A handle over G devices (sda_engine_create_multi) splits the host calls:
 //   - combine (ShareCombiner, Full MaskCombiner, Additive reconstruct): by COLUMNS.  Device g walks every
 //     row, in order, over its column slice and writes that slice of the result: exact for signed inputs in
@@ -1952,34 +2018,13 @@ uint64_t host_stage_bytes() {
     return (uint64_t)std::max<long long>(mb, 1) << 20;
 }
 
-// copy the column slice [lo, lo + w) of rows [r0, r0 + R) into dst ([R][w], dense) on `threads` threads
-void pack_rows(int64_t* dst, const int64_t* const* rows, uint64_t r0, uint64_t R, uint64_t lo, uint64_t w,
-               int threads) {
-    const uint64_t total = R * w;
-    auto work = [=](uint64_t e0, uint64_t e1) {
-        while (e0 < e1) {
-            const uint64_t r = e0 / w, c = e0 % w;
-            const uint64_t n = std::min(e1 - e0, w - c);
-            memcpy(dst + e0, rows[r0 + r] + lo + c, n * 8);
-            e0 += n;
-        }
-    };
-    const uint64_t min_per_thread = 512 * 1024;             // elements (4 MiB): smaller pieces are not worth a thread
-    const int T = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)threads, total / min_per_thread));
-    if (T <= 1) {
-        work(0, total);
-        return;
-    }
-    const uint64_t per = (total + T - 1) / T;
-    std::vector<std::thread> ts;
-    ts.reserve(T - 1);
-    for (int t = 1; t < T; ++t) {
-        const uint64_t e0 = std::min(total, (uint64_t)t * per), e1 = std::min(total, e0 + per);
-        if (e0 < e1) ts.emplace_back(work, e0, e1);
-    }
-    work(0, std::min(per, total));
-    for (auto& t : ts) t.join();
-}
+// (the tile packing -- pack_rows, pack_rows32 -- is host_pack.h: HIP-free, tested under a host sanitizer)
+using sda::pack_rows;
+using sda::pack_rows32;
+
+// SDA_HOST_NARROW (read per call): 1 ships every tile whose values fit as int32 rows -- half the bytes over
+// PCIe and into the combine --, 0 ships every tile as i64.  The results are bit-identical.
+bool host_narrow() { return env_ll("SDA_HOST_NARROW", 1) != 0; }
 
 sda_status host_stream_ensure(sda_engine* h, size_t tile_bytes, size_t acc_bytes) {
     if (!h->copy_stream) {
@@ -2014,6 +2059,7 @@ sda_status stream_combine_slice(sda_engine* h, int64_t m, const int64_t* const* 
                                 uint64_t w, int64_t* out_host, int threads) {
     HIP_TRY(hipSetDevice(h->device));
     const uint64_t stage = host_stage_bytes();
+    const bool narrow = host_narrow();
     const uint64_t wc_max = std::max<uint64_t>(2, stage / 8 / 2 * 2);
     for (uint64_t c0 = 0; c0 < w; c0 += wc_max) {
         const uint64_t wc = std::min(wc_max, w - c0);
@@ -2024,17 +2070,26 @@ sda_status stream_combine_slice(sda_engine* h, int64_t m, const int64_t* const* 
         int64_t* acc = static_cast<int64_t*>(h->hs_dev) + 2 * rup(tile) / 8;
         int64_t* hp[2] = {static_cast<int64_t*>(h->hs_pin), static_cast<int64_t*>(h->hs_pin) + rup(tile) / 8};
         uint64_t i = 0;
+        bool try32 = narrow;                     // until a tile of this column chunk has to ship wide
         for (uint64_t r0 = 0; r0 < n_rows; r0 += R, ++i) {
             const uint64_t Ri = std::min(R, n_rows - r0);
             const int b = (int)(i & 1);
             if (i >= 2) HIP_TRY(hipEventSynchronize(h->h2d_done[b]));        // tile i - 2 has left hp[b]
-            pack_rows(hp[b], rows, r0, Ri, lo + c0, wc, threads);
+            if (try32) try32 = pack_rows32(reinterpret_cast<int32_t*>(hp[b]), rows, r0, Ri, lo + c0, wc, threads);
+            if (!try32) pack_rows(hp[b], rows, r0, Ri, lo + c0, wc, threads);
+            const size_t bytes = (size_t)(Ri * wc * (try32 ? 4 : 8));
             if (i >= 2) HIP_TRY(hipStreamWaitEvent(h->copy_stream, h->tile_free[b], 0));   // ... and dt[b]
-            HIP_TRY(hipMemcpyAsync(dt[b], hp[b], Ri * wc * 8, hipMemcpyHostToDevice, h->copy_stream));
+            HIP_TRY(hipMemcpyAsync(dt[b], hp[b], bytes, hipMemcpyHostToDevice, h->copy_stream));
             HIP_TRY(hipEventRecord(h->h2d_done[b], h->copy_stream));
             HIP_TRY(hipStreamWaitEvent(h->stream, h->h2d_done[b], 0));
-            HIP_TRY(sda::launch_combine_exact(dt[b], Ri, wc, wc, acc, m, h->stream, i > 0));
+            if (try32)
+                HIP_TRY(sda::launch_combine_wide32(reinterpret_cast<const int32_t*>(dt[b]), Ri, wc, wc, acc, m,
+                                                   h->stream, i > 0));
+            else
+                HIP_TRY(sda::launch_combine_exact(dt[b], Ri, wc, wc, acc, m, h->stream, i > 0));
             HIP_TRY(hipEventRecord(h->tile_free[b], h->stream));
+            ++(try32 ? h->hs_tiles32 : h->hs_tiles64);
+            h->hs_bytes_h2d += bytes;
         }
         HIP_TRY(hipMemcpyAsync(out_host + c0, acc, wc * 8, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));

@@ -17,7 +17,16 @@ hipError_t launch_combine_exact(const int64_t* in, uint64_t n, uint64_t dim, uin
                                 int64_t* out, int64_t modulus, hipStream_t s, bool accumulate = false);
 // The same recurrence over int32 rows (decoded field shares: the clerk's decode -> combine).
 hipError_t launch_combine_exact32(const int32_t* in, uint64_t n, uint64_t dim, uint64_t stride,
-                                  int64_t* out, int64_t modulus, hipStream_t s);
+                                  int64_t* out, int64_t modulus, hipStream_t s, bool accumulate = false);
+// int32 share rows as an input type of the combine (sda_combine32_dev, the half-width host stream): 16-byte
+// loads (4 columns per lane), software-pipelined on the balanced grid where the rows line up, else the
+// kernels above.  Sign-extends and runs the i64 recurrence: exact for every modulus.
+hipError_t launch_combine_wide32(const int32_t* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* out,
+                                 int64_t modulus, hipStream_t s, bool accumulate = false);
+// dst[n][dim] (int32, row stride dst_stride) = (int32_t)src[n][dim] (row stride src_stride); flag[0] = 1 when
+// a value lies outside int32 (never cleared).
+hipError_t launch_narrow32(const int64_t* src, uint64_t n, uint64_t dim, uint64_t src_stride, int32_t* dst,
+                           uint64_t dst_stride, int64_t* flag, hipStream_t s);
 // Canonical residue of the int64 sums of the ranks' results (multi-GPU finalize; signed sums allowed).
 hipError_t launch_mod_canonical(const int64_t* sums, uint64_t dim, int64_t* out, int64_t modulus,
                                 hipStream_t s);

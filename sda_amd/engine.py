@@ -81,6 +81,10 @@ SIGNATURES = [
     ("sda_combine_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp]),
     ("sda_combine_finalize_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, _vp, _vp]),
     ("sda_combine_accumulate_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp]),
+    ("sda_combine32_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp]),
+    ("sda_combine32_accumulate_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp]),
+    ("sda_narrow32_dev", _st, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    ("sda_host_stream_stats", _st, [_vp, _u64p, _u64p, _u64p]),
     ("sda_combine_split_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     ("sda_combine_split_prefix_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp,
                                            _vp]),
@@ -396,6 +400,26 @@ class Engine:
     def combine_accumulate_dev(self, modulus, shares_ptr, n, dim, row_stride, inout_ptr, stream=None):
         _check(self.lib.sda_combine_accumulate_dev(self.h, modulus, shares_ptr, n, dim, row_stride, inout_ptr,
                                                    stream))
+
+    # int32 share rows (row_stride in int32 elements; i64 results, bit-identical to the widened rows)
+    def combine32_dev(self, modulus, shares_ptr, n, dim, row_stride, out_ptr, stream=None):
+        _check(self.lib.sda_combine32_dev(self.h, modulus, shares_ptr, n, dim, row_stride, out_ptr, stream))
+
+    def combine32_accumulate_dev(self, modulus, shares_ptr, n, dim, row_stride, inout_ptr, stream=None):
+        _check(self.lib.sda_combine32_accumulate_dev(self.h, modulus, shares_ptr, n, dim, row_stride, inout_ptr,
+                                                     stream))
+
+    def narrow32_dev(self, src_ptr, n, dim, src_stride, dst_ptr, dst_stride, flag_ptr, stream=None):
+        """dst (int32) = src (i64) on the device; flag_ptr: device int64[1], zeroed by the caller, set to 1
+        when a value does not fit (sda_narrow32_dev)."""
+        _check(self.lib.sda_narrow32_dev(self.h, src_ptr, n, dim, src_stride, dst_ptr, dst_stride, flag_ptr, stream))
+
+    def host_stream_stats(self):
+        """(tiles_i32, tiles_i64, bytes_h2d) of the host rows' tile stream since the handle was created
+        (sda_host_stream_stats)."""
+        v = [C.c_uint64() for _ in range(3)]
+        _check(self.lib.sda_host_stream_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
 
     def combine_finalize_dev(self, modulus, sums_ptr, dim, out_ptr, stream=None):
         _check(self.lib.sda_combine_finalize_dev(self.h, modulus, sums_ptr, dim, out_ptr, stream))
