@@ -217,6 +217,14 @@ sda_status sda_narrow32_dev(sda_engine* h, const int64_t* src, uint64_t n, uint6
 sda_status sda_host_stream_stats(const sda_engine* h, uint64_t* tiles_i32, uint64_t* tiles_i64,
                                  uint64_t* bytes_h2d);
 
+/* Diagnostic (read-only): how many batches the handle's most recent packed-Shamir generate or reconstruct
+ * launch handed to its generic fix-up kernel (raw i64 inputs outside (-p, p), or a lazy-truncation / sign-bit
+ * trap).  A value above 65536 (the log's capacity) means the launch recomputed every batch.
+ * 0 when that launch logged nothing by construction (the workspace kernels of the wide schemes, the canonical
+ * Lagrange reveal) or when no packed launch has run.  Waits for the handle's last call to finish and copies 4
+ * bytes per device; summed over a multi-device handle's devices. */
+sda_status sda_packed_fixup_count(sda_engine* h, uint64_t* batches);
+
 /* Multi-GPU finalize: `sums` are the int64 sums (RCCL-reduced; |sum| <= 2^63 - 1, signed allowed)
  * of per-GPU combine results; out = their canonical residue in [0, m).  Exact w.r.t. the reference
  * when all combined inputs were non-negative. */

@@ -35,6 +35,7 @@ struct sda_engine {
     sda::DeviceTable gen_tab;     // packed-Shamir twiddles (per scheme)
     void* gen_log = nullptr;      // packed-Shamir generic fix-up log (sda::packed_gen_log_bytes())
     size_t gen_log_bytes = 0;
+    bool gen_log_used = false;    // the last packed launch zeroed gen_log's count and logs into it
     void* codec_work = nullptr;   // varint codec plan / scan workspace
     size_t codec_work_bytes = 0;
     void* codec_mat = nullptr;    // decoded [N][len] matrix of the clerk decode+combine path
@@ -797,6 +798,34 @@ sda_status sda_host_stream_stats(const sda_engine* h, uint64_t* tiles_i32, uint6
     return ok();
 }
 
+sda_status sda_packed_fixup_count(sda_engine* h, uint64_t* batches) {
+    SDA_ENTRY;
+    if (!h || !batches) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    *batches = 0;
+    uint64_t total = 0;
+    auto add = [&](sda_engine* e) -> sda_status {
+        if (!e->gen_log || !e->gen_log_used) return SDA_OK;
+        HIP_TRY(hipSetDevice(e->device));
+        // the last call's stream may be gone (pick()): wait on the event that call recorded when it ended, and
+        // on the handle's own stream (the host entry points' launches)
+        if (e->order_ok) HIP_TRY(hipEventSynchronize(e->order_ev));
+        else HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        unsigned int n = 0;
+        HIP_TRY(hipMemcpy(&n, e->gen_log, sizeof(n), hipMemcpyDeviceToHost));
+        total += n;
+        return SDA_OK;
+    };
+    if (h->sub.empty()) {
+        if (sda_status st = add(h)) return st;
+    }
+    for (sda_engine* e : h->sub)                          // sub[0] is the handle itself
+        if (sda_status st = add(e)) return st;
+    if (!h->sub.empty()) HIP_TRY(hipSetDevice(h->device));
+    *batches = total;
+    return ok();
+}
+
 sda_status sda_combine_finalize_dev(sda_engine* h, int64_t modulus, const int64_t* sums, uint64_t dim, int64_t* out,
                                     void* stream) {
     SDA_ENTRY;
@@ -874,7 +903,8 @@ sda_status sda_packed_generate_dev(sda_engine* h, const sda_sharing_scheme* s, c
     if (sda_status st = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return st;
     HIP_TRY(sda::launch_packed_generate(ga, (uint32_t)s->secret_count, (uint32_t)s->privacy_threshold,
                                         (uint32_t)s->share_count, (uint32_t)s->modulus, (uint32_t)s->omega_secrets,
-                                        (uint32_t)s->omega_shares, h->gen_tab, h->gen_log, pick(h, stream)));
+                                        (uint32_t)s->omega_shares, h->gen_tab, h->gen_log, pick(h, stream),
+                                        &h->gen_log_used));
     return ok();
 }
 
@@ -891,7 +921,8 @@ sda_status sda_packed_generate_mode_dev(sda_engine* h, const sda_sharing_scheme*
     if (sda_status st = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return st;
     HIP_TRY(sda::launch_packed_generate(ga, (uint32_t)s->secret_count, (uint32_t)s->privacy_threshold,
                                         (uint32_t)s->share_count, (uint32_t)s->modulus, (uint32_t)s->omega_secrets,
-                                        (uint32_t)s->omega_shares, h->gen_tab, h->gen_log, pick(h, stream)));
+                                        (uint32_t)s->omega_shares, h->gen_tab, h->gen_log, pick(h, stream),
+                                        &h->gen_log_used));
     return ok();
 }
 
@@ -913,8 +944,10 @@ sda_status sda_packed_reconstruct_dev(sda_engine* h, const sda_sharing_scheme* s
     if (sda_status e = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
     sda::PackedRevealArgs ra{shares, dimension, n_vectors, out};
     hipError_t e = sda::launch_packed_reveal(ra, indices, (uint32_t)n_idx, (uint32_t)s->secret_count,
+                                             (uint32_t)s->privacy_threshold,
                                              (uint32_t)s->modulus, (uint32_t)s->omega_secrets,
-                                             (uint32_t)s->omega_shares, mode, h->rev_tab, h->gen_log, st);
+                                             (uint32_t)s->omega_shares, mode, h->rev_tab, h->gen_log, st,
+                                             &h->gen_log_used);
     if (e == hipErrorInvalidValue && mode == SDA_REVEAL_CANONICAL)
         return fail(SDA_ERR_UNSUPPORTED, "canonical reveal needs distinct clerk indices");
     HIP_TRY(e);
@@ -1744,12 +1777,15 @@ sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const
                                   !(keep && atoi(keep) == 1);
         const int32_t run_mode = (mode == SDA_REVEAL_EXACT && residue_only) ? SDA_REVEAL_CANONICAL : mode;
         hipError_t e = sda::launch_packed_reveal(ra, indices, (uint32_t)n_idx, (uint32_t)ss->secret_count,
+                                                 (uint32_t)ss->privacy_threshold,
                                                  (uint32_t)p, (uint32_t)ss->omega_secrets,
-                                                 (uint32_t)ss->omega_shares, run_mode, h->rev_tab, h->gen_log, st);
+                                                 (uint32_t)ss->omega_shares, run_mode, h->rev_tab, h->gen_log, st,
+                                                 &h->gen_log_used);
         if (e == hipErrorInvalidValue && run_mode != mode)
-            e = sda::launch_packed_reveal(ra, indices, (uint32_t)n_idx, (uint32_t)ss->secret_count, (uint32_t)p,
+            e = sda::launch_packed_reveal(ra, indices, (uint32_t)n_idx, (uint32_t)ss->secret_count,
+                                          (uint32_t)ss->privacy_threshold, (uint32_t)p,
                                           (uint32_t)ss->omega_secrets, (uint32_t)ss->omega_shares, mode, h->rev_tab,
-                                          h->gen_log, st);
+                                          h->gen_log, st, &h->gen_log_used);
         if (e == hipErrorInvalidValue && mode == SDA_REVEAL_CANONICAL)
             return fail(SDA_ERR_UNSUPPORTED, "canonical reveal needs distinct clerk indices");
         HIP_TRY(e);
@@ -1940,7 +1976,8 @@ sda_status sda_participant_share_dev(sda_engine* h, const sda_masking_scheme* ms
                 sda::PackedGenArgs ga{masked, D, 1, draws, shares_out, mode == SDA_REVEAL_CANONICAL};
                 HIP_TRY(sda::launch_packed_generate(ga, (uint32_t)ss->secret_count, (uint32_t)ss->privacy_threshold,
                                                     (uint32_t)n, (uint32_t)ss->modulus, (uint32_t)ss->omega_secrets,
-                                                    (uint32_t)ss->omega_shares, h->gen_tab, h->gen_log, st));
+                                                    (uint32_t)ss->omega_shares, h->gen_tab, h->gen_log, st,
+                                                    &h->gen_log_used));
             } else {
                 HIP_TRY(sda::launch_additive_generate(masked, D, draws, n, shares_out, ss->modulus, st));
             }
@@ -2426,7 +2463,7 @@ sda_status host_packed_generate(sda_engine* h, const sda_sharing_scheme* s, cons
         sda::PackedGenArgs ga{dsec, ds, 1, ddr, dout};
         HIP_TRY(sda::launch_packed_generate(ga, (uint32_t)k, (uint32_t)t, (uint32_t)n, (uint32_t)s->modulus,
                                             (uint32_t)s->omega_secrets, (uint32_t)s->omega_shares, d->gen_tab,
-                                            d->gen_log, d->stream));
+                                            d->gen_log, d->stream, &d->gen_log_used));
         HIP_TRY(hipMemcpy2DAsync(out + b0, B * 8, dout, nb * 8, nb * 8, n, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(hipStreamSynchronize(d->stream));
         return SDA_OK;
@@ -2453,9 +2490,10 @@ sda_status host_packed_reconstruct(sda_engine* h, const sda_sharing_scheme* s, u
             HIP_TRY(hipMemcpyAsync(din + i * nb, rows[i] + b0, nb * 8, hipMemcpyHostToDevice, d->stream));
         if (sda_status e = ensure(&d->gen_log, &d->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
         sda::PackedRevealArgs ra{din, ds, 1, dout};
-        HIP_TRY(sda::launch_packed_reveal(ra, indices, (uint32_t)n_rows, (uint32_t)k, (uint32_t)s->modulus,
+        HIP_TRY(sda::launch_packed_reveal(ra, indices, (uint32_t)n_rows, (uint32_t)k, (uint32_t)s->privacy_threshold,
+                                          (uint32_t)s->modulus,
                                           (uint32_t)s->omega_secrets, (uint32_t)s->omega_shares, SDA_REVEAL_EXACT,
-                                          d->rev_tab, d->gen_log, d->stream));
+                                          d->rev_tab, d->gen_log, d->stream, &d->gen_log_used));
         HIP_TRY(hipMemcpyAsync(out + s0, dout, ds * 8, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(hipStreamSynchronize(d->stream));
         return SDA_OK;

@@ -92,9 +92,11 @@ struct GenFixupLog {
     uint32_t cap;
 };
 size_t packed_gen_log_bytes();
+// *logged (host, optional; both launchers): whether this launch zeroed `log_buf`'s count and ran kernels that
+// log into it -- false for the workspace kernels and the canonical Lagrange reveal (sda_packed_fixup_count).
 hipError_t launch_packed_generate(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p,
                                   uint32_t omega_secrets, uint32_t omega_shares, DeviceTable& tab, void* log_buf,
-                                  hipStream_t s);
+                                  hipStream_t s, bool* logged = nullptr);
 struct PackedRevealArgs {
     const int64_t* shares; uint64_t dimension; uint64_t n_vectors; int64_t* out;
 };
@@ -111,9 +113,12 @@ hipError_t launch_packed_generate_wide(const PackedGenArgs& a, uint32_t k, uint3
                                        hipStream_t s);
 // returns hipErrorInvalidValue for CANONICAL mode with duplicate clerk points.  `log_buf`: device
 // memory of packed_gen_log_bytes() bytes (batches the exact kernel hands to its generic fix-up).
+// t (the privacy threshold) picks the exact kernel: from exactly t + k shares every Newton coefficient is generic
+// and the lazily truncating sign-bit kernel runs; from more, the coefficients past degree t + k are 0 in every
+// batch, which is that kernel's trap, so the kernel with tss' truncation verbatim runs instead.
 hipError_t launch_packed_reveal(const PackedRevealArgs& a, const uint64_t* indices, uint32_t n_idx, uint32_t k,
-                                uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, int mode,
-                                DeviceTable& tab, void* log_buf, hipStream_t s);
+                                uint32_t t, uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, int mode,
+                                DeviceTable& tab, void* log_buf, hipStream_t s, bool* logged = nullptr);
 hipError_t launch_packed_reveal_wide(const PackedRevealArgs& a, const uint64_t* indices, uint32_t n_idx, uint32_t k,
                                      uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, int mode,
                                      DeviceTable& tab, hipStream_t s);

@@ -715,7 +715,8 @@ size_t packed_gen_log_bytes() { return 64 + (size_t)kGenLogCap * sizeof(uint64_t
 
 hipError_t launch_packed_generate(const PackedGenArgs& args, uint32_t k, uint32_t t, uint32_t n, uint32_t p,
                                   uint32_t omega_secrets, uint32_t omega_shares, DeviceTable& tab, void* log_buf,
-                                  hipStream_t s) {
+                                  hipStream_t s, bool* logged) {
+    if (logged) *logged = false;
     PackedGenArgs a = args;
     a.prime = p;
     const uint32_t L = k + t + 1, N3 = n + 1;
@@ -743,6 +744,7 @@ hipError_t launch_packed_generate(const PackedGenArgs& args, uint32_t k, uint32_
                     reinterpret_cast<uint64_t*>(static_cast<unsigned int*>(log_buf) + 16), kGenLogCap};
     hipError_t e = hipMemsetAsync(log.count, 0, sizeof(unsigned int), s);
     if (e != hipSuccess) return e;
+    if (logged) *logged = true;
     switch (N3 * 128 + L) {             // one object per (N3, L): Makefile GEN_PARTS
 #define SDA_GEN_CASE(N, LL) case N * 128 + LL: e = gen_launch<LL, N>(a, k, t, B, T, log, s); break;
         SDA_GEN_CASE(3, 2)

@@ -22,7 +22,7 @@ constexpr int KMAX = 64;
 // One launcher per MM (the padded point count); each is compiled in its own object
 // (Makefile: -DSDA_REVEAL_PART=MM) so the wide instantiations build in parallel.
 template <int MM>
-hipError_t reveal_launch(int mode, const PackedRevealArgs& a, uint64_t B, uint32_t n_idx, uint32_t k,
+hipError_t reveal_launch(int mode, const PackedRevealArgs& a, uint64_t B, uint32_t n_idx, uint32_t k, bool lazy,
                          const uint32_t* tab, const MontP& M, unsigned int* log, hipStream_t s);
 
 #ifdef SDA_REVEAL_PART
@@ -230,9 +230,9 @@ __device__ __forceinline__ bool newton_reveal(FE (&s)[MMAX], uint32_t m, uint32_
     return tr.bad(p);
 }
 
-// One lane = one batch.  LAZY (p >= kLazyTruncMinP): the sign-bit path with its zero trap.  A lane whose
-// batch hit the trap (probability ~1/p per value) or has a share outside (-p, p) (raw i64 input) logs
-// the batch and stores garbage; packed_reveal_fixup_kernel, launched right after on the same stream,
+// One lane = one batch.  LAZY (p >= kLazyTruncMinP, exactly t + k shares): the sign-bit path with its zero
+// trap.  A lane whose batch hit the trap (probability ~1/p per value) or has a share outside (-p, p) (raw
+// i64 input) logs the batch and stores garbage; packed_reveal_fixup_kernel, launched right after on the same stream,
 // recomputes the logged batches (exact truncation in registers, or the generic i64 path).  Keeping
 // the generic path (a 128-entry i64 array per lane) out of this kernel keeps it free of scratch.
 template <int MMAX, bool STAGED, int KU, bool LAZY, bool FULL = false>
@@ -488,7 +488,7 @@ __global__ __launch_bounds__(256) void packed_reveal_canon_kernel(const int64_t*
 }  // namespace
 
 template <int MM>
-hipError_t reveal_launch(int mode, const PackedRevealArgs& a, uint64_t B, uint32_t n_idx, uint32_t k,
+hipError_t reveal_launch(int mode, const PackedRevealArgs& a, uint64_t B, uint32_t n_idx, uint32_t k, bool lazy,
                          const uint32_t* tab, const MontP& M, unsigned int* log, hipStream_t s) {
     dim3 grid((unsigned)((B + 255) / 256), (unsigned)a.n_vectors);
     const bool staged = k <= 16;                      // LDS stage: 256 * k * 8 B <= 32 KiB
@@ -497,24 +497,36 @@ hipError_t reveal_launch(int mode, const PackedRevealArgs& a, uint64_t B, uint32
     if (mode == 0) {
         bool done = false;
         if constexpr (MM <= 16) {
+            // lazy (launch_packed_reveal): p >= kLazyTruncMinP and exactly t + k shares, so n_idx + 1 = k + t + 1 is a
+            // power of 2: 16 points are this bucket's FULL kernel, 2 or 4 the 8-point bucket's partial one
             done = staged && k <= 8;
-            if (done && M.p >= kLazyTruncMinP && n_idx + 1 == MM)
+            if (done && lazy && n_idx + 1 == MM)
                 hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, true, 8, true, true>), grid, dim3(256), lds, s,
                                    a.shares, B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
-            else if (done && M.p >= kLazyTruncMinP)
-                hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, true, 8, true>), grid, dim3(256), lds, s,
-                                   a.shares, B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
-            else if (done)
+            else if (done && lazy && MM == 8) {
+                if constexpr (MM == 8)
+                    hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, true, 8, true>), grid, dim3(256), lds, s,
+                                       a.shares, B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
+            } else if (done)
                 hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, true, 8, false>), grid, dim3(256), lds, s,
                                    a.shares, B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
         }
+        // A reveal takes at least k shares (n_idx >= t + k: sda_packed_reconstruct_dev), so k < MM: the staged
+        // kernel without the unrolled evaluation (8 < k <= 16) exists from MM = 16, the unstaged one (k > 16)
+        // from MM = 32 -- every instantiation in the library can be launched (tests/test_packed_matrix_plan.py).
         if (done) {
         } else if (staged) {
-            hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, true, 0, false>), grid, dim3(256), lds, s, a.shares,
-                               B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
+            if constexpr (MM > 8)
+                hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, true, 0, false>), grid, dim3(256), lds, s,
+                                   a.shares, B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
+            else
+                return hipErrorInvalidValue;
         } else {
-            hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, false, 0, false>), grid, dim3(256), 0, s, a.shares,
-                               B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
+            if constexpr (MM > 16)
+                hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, false, 0, false>), grid, dim3(256), 0, s,
+                                   a.shares, B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
+            else
+                return hipErrorInvalidValue;
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
@@ -532,15 +544,17 @@ hipError_t reveal_launch(int mode, const PackedRevealArgs& a, uint64_t B, uint32
         if (staged)
             hipLaunchKernelGGL((packed_reveal_canon_kernel<MM, true>), grid, dim3(256), lds, s, a.shares, B,
                                a.dimension, a.out, n_idx, k, tab, M, xcd);
-        else
+        else if constexpr (MM > 16)                   // k <= n_idx <= MM: unstaged (k > 16) only at MM = 32
             hipLaunchKernelGGL((packed_reveal_canon_kernel<MM, false>), grid, dim3(256), 0, s, a.shares, B,
                                a.dimension, a.out, n_idx, k, tab, M, xcd);
+        else
+            return hipErrorInvalidValue;
     } else {
         return hipErrorInvalidValue;                  // launch_packed_reveal runs these as exact + canonical
     }
     return hipGetLastError();
 }
-template hipError_t reveal_launch<SDA_REVEAL_PART>(int, const PackedRevealArgs&, uint64_t, uint32_t, uint32_t,
+template hipError_t reveal_launch<SDA_REVEAL_PART>(int, const PackedRevealArgs&, uint64_t, uint32_t, uint32_t, bool,
                                                    const uint32_t*, const MontP&, unsigned int*, hipStream_t);
 
 #else  // dispatcher + host tables
@@ -590,8 +604,9 @@ static void build_reveal_tables(std::vector<uint32_t>& tab, const uint64_t* indi
 }
 
 hipError_t launch_packed_reveal(const PackedRevealArgs& a, const uint64_t* indices, uint32_t n_idx, uint32_t k,
-                                uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, int mode,
-                                DeviceTable& tab, void* log_buf, hipStream_t s) {
+                                uint32_t t, uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, int mode,
+                                DeviceTable& tab, void* log_buf, hipStream_t s, bool* logged) {
+    if (logged) *logged = false;
     const uint64_t B = (a.dimension + k - 1) / k;
     if (B == 0 || a.n_vectors == 0) return hipSuccess;
     if ((mode == 0 ? n_idx + 1 : n_idx) > (uint32_t)kRevealMaxPoints || k > (uint32_t)KMAX)   // packed_wide.hip
@@ -609,8 +624,8 @@ hipError_t launch_packed_reveal(const PackedRevealArgs& a, const uint64_t* indic
         const uint32_t m = n_idx + 1;
         hipError_t e = m > (uint32_t)kRevealMaxPoints
                            ? launch_packed_reveal_wide(a, indices, n_idx, k, p, omega_secrets, omega_shares, 1, tab, s)
-                           : launch_packed_reveal(a, indices, n_idx, k, p, omega_secrets, omega_shares, 0, tab,
-                                                  log_buf, s);
+                           : launch_packed_reveal(a, indices, n_idx, k, t, p, omega_secrets, omega_shares, 0, tab,
+                                                  log_buf, s, logged);
         if (e != hipSuccess || m > (uint32_t)kRevealMaxPoints) return e;
         return launch_mod_canonical(a.out, a.dimension * a.n_vectors, a.out, p, s);
     }
@@ -633,11 +648,17 @@ hipError_t launch_packed_reveal(const PackedRevealArgs& a, const uint64_t* indic
     unsigned int* log = static_cast<unsigned int*>(log_buf);
     hipError_t e = hipSuccess;
     if (mode == 0 && (e = hipMemsetAsync(log, 0, sizeof(unsigned int), s)) != hipSuccess) return e;
-    if (need <= 8) e = reveal_launch<8>(mode, a, B, n_idx, k, dtab, M, log, s);
-    else if (need <= 16) e = reveal_launch<16>(mode, a, B, n_idx, k, dtab, M, log, s);
-    else if (need <= 32) e = reveal_launch<32>(mode, a, B, n_idx, k, dtab, M, log, s);
-    else if (need <= 64) e = reveal_launch<64>(mode, a, B, n_idx, k, dtab, M, log, s);
-    else if (need <= kRevealMaxPoints) e = reveal_launch<kRevealMaxPoints>(mode, a, B, n_idx, k, dtab, M, log, s);
+    if (logged) *logged = mode == 0;
+    // The sign-bit kernels are exact unless a residue on the way is 0 (ZeroTrap).  From more than t + k shares the
+    // divided differences past the polynomial's degree are 0 in EVERY batch: such a launch would log all of its
+    // batches and the fix-up would recompute them (right, and slower than never taking the lazy kernel).
+    const bool lazy = p >= kLazyTruncMinP && n_idx == k + t;
+    if (need <= 8) e = reveal_launch<8>(mode, a, B, n_idx, k, lazy, dtab, M, log, s);
+    else if (need <= 16) e = reveal_launch<16>(mode, a, B, n_idx, k, lazy, dtab, M, log, s);
+    else if (need <= 32) e = reveal_launch<32>(mode, a, B, n_idx, k, lazy, dtab, M, log, s);
+    else if (need <= 64) e = reveal_launch<64>(mode, a, B, n_idx, k, lazy, dtab, M, log, s);
+    else if (need <= kRevealMaxPoints)
+        e = reveal_launch<kRevealMaxPoints>(mode, a, B, n_idx, k, lazy, dtab, M, log, s);
     else return hipErrorInvalidValue;
     return e;
 }

@@ -85,6 +85,7 @@ SIGNATURES = [
     ("sda_combine32_accumulate_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp]),
     ("sda_narrow32_dev", _st, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
     ("sda_host_stream_stats", _st, [_vp, _u64p, _u64p, _u64p]),
+    ("sda_packed_fixup_count", _st, [_vp, _u64p]),
     ("sda_combine_split_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     ("sda_combine_split_prefix_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp,
                                            _vp]),
@@ -420,6 +421,13 @@ class Engine:
         v = [C.c_uint64() for _ in range(3)]
         _check(self.lib.sda_host_stream_stats(self.h, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    def packed_fixup_count(self) -> int:
+        """Batches the last packed generate / reconstruct launch sent to its generic fix-up kernel; 0 after a
+        launch that logs nothing (workspace kernels, canonical Lagrange reveal) (sda_packed_fixup_count)."""
+        v = C.c_uint64()
+        _check(self.lib.sda_packed_fixup_count(self.h, C.byref(v)))
+        return int(v.value)
 
     def combine_finalize_dev(self, modulus, sums_ptr, dim, out_ptr, stream=None):
         _check(self.lib.sda_combine_finalize_dev(self.h, modulus, sums_ptr, dim, out_ptr, stream))

@@ -158,6 +158,21 @@ def test_narrow32_dev(engine, sstride, dstride):
         assert _narrow(engine, torch.from_numpy(y).cuda(), N, D, sstride, dstride)[1] == 1, (r, c, v)
 
 
+@pytest.mark.parametrize("sstride,dstride", [(8, 8), (7, 7)], ids=["16_byte_path", "scalar_path"])
+def test_narrow32_dev_rows_past_the_grid_limit(engine, sstride, dstride):
+    """launch_narrow32 clamps grid.y at 65,535 and the kernel reaches the rows past it with r += gridDim.y: 65,541
+    rows (six of them a lane's second row) of 6 columns -- one 16-byte quad and a 2-column tail, or 6 scalars."""
+    N, D = 65_541, 6
+    x = np.full((N, sstride), 1 << 40, dtype=np.int64)                         # padding: must not be read
+    x[:, :D] = _rows32(N, D, 6).astype(np.int64)
+    got, flag = _narrow(engine, torch.from_numpy(x).cuda(), N, D, sstride, dstride)
+    assert_same(got[:, :D], x[:, :D].astype(np.int32), "narrowed")
+    assert (got[:, D:] == 0x55555555).all(), "destination padding was written"
+    assert flag == 0
+    x[65_540, D - 1] = 1 << 31                                                 # only a second-pass row sees it
+    assert _narrow(engine, torch.from_numpy(x).cuda(), N, D, sstride, dstride)[1] == 1
+
+
 def test_combine32_of_narrowed_equals_combine(engine):
     N, D = 33, 2052
     x = torch.empty((N, D), dtype=torch.int64, device="cuda")

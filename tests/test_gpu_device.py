@@ -267,6 +267,7 @@ def _split_on_one_gpu(engine, m, x, G, tile=None):
     (1000003, 300, 9_999, -(1 << 61), 1 << 61, 5, None),                   # raw i64: the generic path
     (433, 1, 1_001, -432, 433, 1, None),                                   # one rank, one row
     (433, 3, 4_096, -432, 433, 8, None),                                   # ranks with no rows
+    (2147482801, 9, 262_146, -(2147482801 - 1), 2147482801, 2, None),      # pass 1 on the balanced grid (131,073 lanes)
 ])
 def test_participation_split_signed_exact(engine, oracle, m, N, D, lo, hi, G, tile):
     """The exact signed participation split (SURVEY §7 hard part 1 (b)): pass-1 flags,
@@ -307,6 +308,76 @@ def test_participation_split_flags(engine):
     assert flags()[0] == [0, 0]
     x[0, 0] = -(1 << 63)
     assert flags()[0] == [1, 1]
+
+
+def test_participation_split_flags_on_the_balanced_grid(engine):
+    """Pass 1 from 131,072 lanes up runs on the balanced grid (combine.hip: launch_vec<int64_t, 2, 4, true, true,
+    true> with wlo > 0): a value past 2^63 - m in the LAST column raises [., 1] there too, a negative one [1, .]."""
+    m, N, D = 2147482801, 9, 262_146
+    x = torch.empty((N, D), dtype=torch.int64, device="cuda")
+    engine.synth_fill_dev(x.data_ptr(), N, D, 0x5DA + 33, 0, m, _stream())
+
+    def flags():
+        f = torch.zeros(2, dtype=torch.int64, device="cuda")
+        acc = torch.zeros(D, dtype=torch.int64, device="cuda")
+        engine.combine_split_dev(m, x.data_ptr(), N, D, D, acc.data_ptr(), f.data_ptr(), _stream())
+        torch.cuda.synchronize()
+        return f.tolist(), acc
+    f, acc = flags()
+    assert f == [0, 0]
+    assert torch.equal(acc, torch.remainder(x.sum(dim=0), m))
+    x[N - 1, D - 1] = (1 << 63) - m + 1     # just past the no-wrap range
+    assert flags()[0] == [0, 1]
+    x[N - 1, D - 1] = (1 << 63) - m         # the range's edge: fine
+    assert flags()[0] == [0, 0]
+    x[4, D - 1] = -1
+    assert flags()[0] == [1, 0]
+
+
+@pytest.mark.parametrize("D", [1_001, 1_002], ids=["1_column_kernel", "2_column_kernel"])
+def test_participation_split_replay_above_2_62(engine, oracle, D):
+    """combine_replay_kernel<*, *, false>: the signed split's replay at m = 2^62 + 3 (the exact unsigned forms of
+    its step), inputs over the whole no-wrap range [-(2^63 - m), 2^63 - m], 3 simulated ranks of 20 rows.
+    sda_combine_split_prefix_dev refuses this modulus for more than one rank (the ranks' pass-1 results no
+    longer sum in an i64: world (m - 1) > 2^63 - 1), so the prefix -- c_in, total and rank 0's sign code -- is
+    computed here with Python integers; pass 1, the replay and the resolve run through the C ABI, and the result
+    is the reference's single sequential pass (combiner.rs:16-28) bit for bit."""
+    from sda_amd import distributed as Dd
+    from sda_amd import SdaError
+    m, N, G = (1 << 62) + 3, 60, 3
+    lim = (1 << 63) - m
+    x = torch.empty((N, D), dtype=torch.int64, device="cuda")
+    engine.synth_fill_dev(x.data_ptr(), N, D, 0x5DA + 34, -lim, lim + 1, _stream())
+    spans = [Dd.shard_range(N, g, G) for g in range(G)]
+    parts = torch.zeros((G, D), dtype=torch.int64, device="cuda")
+    flags = torch.zeros((G, 2), dtype=torch.int64, device="cuda")
+    for g, (s0, cnt) in enumerate(spans):
+        engine.combine_split_dev(m, x[s0].data_ptr(), cnt, D, x.stride(0), parts[g].data_ptr(), flags[g].data_ptr(),
+                                 _stream())
+    torch.cuda.synchronize()
+    fl = flags.sum(dim=0).tolist()
+    assert fl[0] > 0 and fl[1] == 0
+    scratch = torch.empty((3, D), dtype=torch.int64, device="cuda")
+    with pytest.raises(SdaError):
+        engine.combine_split_prefix_dev(m, parts.data_ptr(), G, 1, D, scratch[0].data_ptr(), scratch[1].data_ptr(),
+                                        scratch[2].data_ptr(), _stream())
+    ph = [[int(v) for v in row] for row in parts.cpu().numpy()]
+    total = torch.tensor([sum(ph[g][i] for g in range(G)) % m for i in range(D)], dtype=torch.int64, device="cuda")
+    codes = torch.zeros((G, D), dtype=torch.int32, device="cuda")
+    codes[0] = torch.tensor([1 + (v < 0) for v in ph[0]], dtype=torch.int32, device="cuda")
+    for g in range(1, G):
+        state = torch.tensor([sum(ph[h][i] for h in range(g)) % m for i in range(D)], dtype=torch.int64,
+                             device="cuda")
+        s0, cnt = spans[g]
+        engine.combine_split_replay_dev(m, x[s0].data_ptr(), cnt, D, x.stride(0), g, state.data_ptr(),
+                                        codes[g].data_ptr(), _stream())
+    code = codes.max(dim=0).values.contiguous()
+    out = torch.empty(D, dtype=torch.int64, device="cuda")
+    engine.combine_split_resolve_dev(m, total.data_ptr(), code.data_ptr(), D, out.data_ptr(), _stream())
+    torch.cuda.synchronize()
+    exp = oracle.combine(m, x.cpu().numpy())
+    assert (exp < 0).any() and (exp > 0).any()
+    assert_same(out.cpu().numpy(), exp)
 
 
 def test_finalize_signed_sums(engine):

@@ -367,9 +367,13 @@ def _bitrev(i, bits):
 def test_packed_generate_negative_multiple_of_p(engine, oracle, sch):
     """Exact share-gen where a first-stage dividend is exactly -p (tss: `-p % p == 0`).
 
-    The exact kernel for p >= 2^24 truncates lazily (packed_gen.hip: Trunc<true>) and must send
-    such batches to the generic fix-up; every other batch stays on the fast path.  The traps sit
-    in the radix-2 stage-1 butterflies (x[2m] +- x[2m+1] over bit-reversed inputs).
+    These schemes (p near 2^31, B even, aligned output) run the sign-bit kernel, packed_gen_kernel<L, N3, true,
+    false, true, SIGNBIT = true>: its radix-2 half keeps (residue, sign bit) pairs, and a butterfly output whose
+    residue is 0 trips RangeTrap (0 with the sign set would be a nonzero multiple of p), which must send such
+    batches to the generic fix-up; every other batch stays on the fast path.  The traps sit in the radix-2
+    stage-1 butterflies (x[2m] +- x[2m+1] over bit-reversed inputs).  (The lazily truncating kernel without
+    sign bits, Trunc<true>'s -p trap, runs in tests/test_gpu_packed_matrix.py: SDA_GEN_SIGNBIT=0 and the
+    small-root schemes.)
     """
     p, k, t = sch.prime_modulus, sch.secret_count, sch.privacy_threshold()
     L = k + t + 1
