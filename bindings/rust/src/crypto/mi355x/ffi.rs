@@ -135,6 +135,12 @@ extern "C" {
     pub fn sda_packed_reconstruct_dev(h: *mut SdaEngine, s: *const SdaSharingScheme, dimension: u64,
                                       indices: *const u64, n_idx: u64, n_vectors: u64, shares: *const i64,
                                       out: *mut i64, mode: i32, stream: *mut c_void) -> SdaStatus;
+    pub fn sda_packed_generate32_dev(h: *mut SdaEngine, s: *const SdaSharingScheme, secrets: *const i64,
+                                     dimension: u64, n_vectors: u64, draws: *const i64, out: *mut i32, mode: i32,
+                                     stream: *mut c_void) -> SdaStatus;
+    pub fn sda_packed_reconstruct32_dev(h: *mut SdaEngine, s: *const SdaSharingScheme, dimension: u64,
+                                        indices: *const u64, n_idx: u64, n_vectors: u64, shares: *const i32,
+                                        out: *mut i64, mode: i32, stream: *mut c_void) -> SdaStatus;
     pub fn sda_additive_generate_dev(h: *mut SdaEngine, modulus: i64, share_count: u64, secrets: *const i64,
                                      dimension: u64, draws: *const i64, out: *mut i64, stream: *mut c_void)
                                      -> SdaStatus;

@@ -276,6 +276,32 @@ sda_status sda_packed_reconstruct_dev(sda_engine* h, const sda_sharing_scheme* s
                                       const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
                                       const int64_t* shares, int64_t* out, int32_t mode, void* stream);
 
+/* ---- int32 share rows through the packed-Shamir data flow ----
+ * check_packed admits only primes p < 2^31 and every share is a `% p` result, so |share| <= p - 1 < 2^31: half
+ * of an i64 share is sign extension.  With these two entry points the device-resident chain generate ->
+ * sda_combine32_dev -> sda_narrow32_dev (of the n clerk results) -> reveal stays in int32 rows end to end
+ * (INTEGRATION.md).  Argument checks, error codes, the 65,535-vector and 1,023-share limits, the stream ordering
+ * on the handle and sda_packed_fixup_count afterwards are those of the i64 entry points; on a multi-device handle
+ * they run on ordinals[0].  out / shares need only 4-byte alignment and any B works; the fast stores need a
+ * 16-byte aligned out and even B (16 bytes per lane from B % 4 == 0), as the i64 kernels do.
+ *
+ * sda_packed_generate_mode_dev with int32 shares: out [n_vectors][n][B] int32, dense.  Bit-identical to
+ * (int32_t) of the i64 entry point's output, for every scheme in the engine's domain, both modes, raw i64
+ * secrets included (shares are `% p` results, p < 2^31: they always fit, so there is no flag).
+ * Schemes with n + 1 <= 27 and the workspace kernels (k + t + 1 > 64, n + 1 > 81) write int32 directly.  At
+ * n + 1 = 81 the register kernels write i64 shares into scratch owned by the handle (n_vectors * n * B * 8
+ * bytes, kept and reused until the handle is destroyed) and a narrowing pass writes out: when that scratch
+ * cannot be allocated the call returns SDA_ERR_OUT_OF_MEMORY and out is untouched. */
+sda_status sda_packed_generate32_dev(sda_engine* h, const sda_sharing_scheme* s, const int64_t* secrets,
+                                     uint64_t dimension, uint64_t n_vectors, const int64_t* draws,
+                                     int32_t* out, int32_t mode, void* stream);
+
+/* sda_packed_reconstruct_dev from int32 shares [n_vectors][n_idx][B]: out (i64) is bit-identical to widening
+ * the shares and calling the i64 entry point -- shares outside (-p, p) that fit int32 included (fix-up). */
+sda_status sda_packed_reconstruct32_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                        const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
+                                        const int32_t* shares, int64_t* out, int32_t mode, void* stream);
+
 /* Additive share generation: secrets [dimension], draws [dimension][n-1], out [n][dimension]. */
 sda_status sda_additive_generate_dev(sda_engine* h, int64_t modulus, uint64_t share_count,
                                      const int64_t* secrets, uint64_t dimension,

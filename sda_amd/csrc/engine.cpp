@@ -36,6 +36,8 @@ struct sda_engine {
     void* gen_log = nullptr;      // packed-Shamir generic fix-up log (sda::packed_gen_log_bytes())
     size_t gen_log_bytes = 0;
     bool gen_log_used = false;    // the last packed launch zeroed gen_log's count and logs into it
+    void* gen32_tmp = nullptr;    // sda_packed_generate32_dev at n + 1 = 81: i64 shares before the narrowing pass
+    size_t gen32_tmp_bytes = 0;
     void* codec_work = nullptr;   // varint codec plan / scan workspace
     size_t codec_work_bytes = 0;
     void* codec_mat = nullptr;    // decoded [N][len] matrix of the clerk decode+combine path
@@ -406,6 +408,7 @@ void sda_engine_destroy(sda_engine* h) {
     (void)hipDeviceSynchronize();            // _dev work may still be queued on callers' streams
     dev_free(h->work);
     dev_free(h->gen_log);
+    dev_free(h->gen32_tmp);
     dev_free(h->codec_work);
     dev_free(h->codec_mat);
     dev_free(h->pipe);
@@ -943,6 +946,64 @@ sda_status sda_packed_reconstruct_dev(sda_engine* h, const sda_sharing_scheme* s
     hipStream_t st = pick(h, stream);
     if (sda_status e = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
     sda::PackedRevealArgs ra{shares, dimension, n_vectors, out};
+    hipError_t e = sda::launch_packed_reveal(ra, indices, (uint32_t)n_idx, (uint32_t)s->secret_count,
+                                             (uint32_t)s->privacy_threshold,
+                                             (uint32_t)s->modulus, (uint32_t)s->omega_secrets,
+                                             (uint32_t)s->omega_shares, mode, h->rev_tab, h->gen_log, st,
+                                             &h->gen_log_used);
+    if (e == hipErrorInvalidValue && mode == SDA_REVEAL_CANONICAL)
+        return fail(SDA_ERR_UNSUPPORTED, "canonical reveal needs distinct clerk indices");
+    HIP_TRY(e);
+    return ok();
+}
+
+// int32 shares (every share is a `% p` result, p < 2^31): native int32 kernels, or at n + 1 = 81 the i64 register
+// kernels into handle-owned scratch and a narrowing pass (packed_gen.hip, launch_packed_generate)
+sda_status sda_packed_generate32_dev(sda_engine* h, const sda_sharing_scheme* s, const int64_t* secrets,
+                                     uint64_t dimension, uint64_t n_vectors, const int64_t* draws, int32_t* out,
+                                     int32_t mode, void* stream) {
+    SDA_ENTRY;
+    if (!h || !s || s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "need a PackedShamir scheme");
+    if (mode != SDA_REVEAL_EXACT && mode != SDA_REVEAL_CANONICAL) return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
+    if (sda_status st = check_packed(s)) return st;
+    if (n_vectors > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 vectors per launch");
+    if (dimension && n_vectors && (!out || !secrets || (s->privacy_threshold && !draws)))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    sda::PackedGenArgs ga{secrets, dimension, n_vectors, draws, nullptr, mode == SDA_REVEAL_CANONICAL};
+    ga.out32 = out;
+    const uint32_t k = (uint32_t)s->secret_count, t = (uint32_t)s->privacy_threshold, n = (uint32_t)s->share_count;
+    hipStream_t st = pick(h, stream);
+    if (sda_status e = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
+    if (const size_t tmp = sda::packed_gen32_scratch_bytes(ga, k, t, n, (uint32_t)s->modulus)) {
+        if (sda_status e = ensure(&h->gen32_tmp, &h->gen32_tmp_bytes, tmp + 64)) return e;
+        ga.scratch = static_cast<int64_t*>(h->gen32_tmp);
+        ga.flag = ga.scratch + tmp / sizeof(int64_t);      // launch_narrow32's overflow word: never set here
+    }
+    HIP_TRY(sda::launch_packed_generate(ga, k, t, n, (uint32_t)s->modulus, (uint32_t)s->omega_secrets,
+                                        (uint32_t)s->omega_shares, h->gen_tab, h->gen_log, st, &h->gen_log_used));
+    return ok();
+}
+
+sda_status sda_packed_reconstruct32_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                        const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
+                                        const int32_t* shares, int64_t* out, int32_t mode, void* stream) {
+    SDA_ENTRY;
+    if (!h || !s || s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "need a PackedShamir scheme");
+    if (sda_status st = check_packed(s)) return st;
+    if (mode != SDA_REVEAL_EXACT && mode != SDA_REVEAL_CANONICAL) return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
+    if (dimension == 0) return ok();                        // batched.rs:77-81: no batch, no check
+    if (n_idx < s->privacy_threshold + s->secret_count)
+        return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");
+    if (n_idx > sda::kRevealMaxShares)
+        return fail(SDA_ERR_UNSUPPORTED, "more than %u clerk shares per batch", sda::kRevealMaxShares);
+    if (n_vectors > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 vectors per launch");
+    if (n_vectors && (!out || !shares || !indices)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = pick(h, stream);
+    if (sda_status e = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
+    sda::PackedRevealArgs ra{nullptr, dimension, n_vectors, out};
+    ra.shares32 = shares;
     hipError_t e = sda::launch_packed_reveal(ra, indices, (uint32_t)n_idx, (uint32_t)s->secret_count,
                                              (uint32_t)s->privacy_threshold,
                                              (uint32_t)s->modulus, (uint32_t)s->omega_secrets,

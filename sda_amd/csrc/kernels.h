@@ -78,7 +78,17 @@ struct PackedGenArgs {
     uint32_t prime = 0;           // set by launch_packed_generate (selects the lazy-truncation kernel)
     bool signbit = false;         // set by launch_packed_generate (sign-bit radix-2 half, packed_gen.hip)
     bool xcd_order = true;        // set by launch_packed_generate: XCD-chunked tile order (xcd.h)
+    // int32 shares (sda_packed_generate32_dev): out32 != nullptr replaces out, [n_vectors][n][B] int32.  Native
+    // kernels up to n + 1 = 27 and on the workspace path; the n + 1 = 81 register kernels write i64 into
+    // `scratch` (packed_gen32_scratch_bytes() bytes) and launch_narrow32 narrows it (`flag`: its device word).
+    int32_t* out32 = nullptr;
+    int64_t* scratch = nullptr;
+    int64_t* flag = nullptr;
+    const void* align_as = nullptr;   // set by launch_packed_generate: the buffer whose alignment picks the kernel
+    int store32 = 0;              // set by launch_packed_generate: 2 = the 16-byte quad store (A/B, SDA_GEN32_QUAD builds)
 };
+// Scratch the int32 call needs (0: native int32 kernels serve it).
+size_t packed_gen32_scratch_bytes(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p);
 // A/B knob: SDA_XCD_ORDER=0 runs the streaming kernels in natural workgroup order (xcd.h).
 bool xcd_order_enabled();
 // Exact share-gen uses lazy truncation (packed_gen.hip: Trunc<true>) for primes at least this big.
@@ -99,6 +109,7 @@ hipError_t launch_packed_generate(const PackedGenArgs& a, uint32_t k, uint32_t t
                                   hipStream_t s, bool* logged = nullptr);
 struct PackedRevealArgs {
     const int64_t* shares; uint64_t dimension; uint64_t n_vectors; int64_t* out;
+    const int32_t* shares32 = nullptr;   // int32 shares (sda_packed_reconstruct32_dev): replaces `shares`
 };
 // The register reveal kernels take up to kRevealMaxPoints - 1 clerk shares per batch (n + 1 <= 81
 // gives n <= 80 clerks; they keep n_idx + 1 Newton points in registers).

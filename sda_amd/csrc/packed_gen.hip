@@ -121,6 +121,10 @@ __device__ __forceinline__ void gen_store(const V& v, V* a) {
     else *a = v;
 }
 
+#ifndef SDA_GEN32_QUAD
+#define SDA_GEN32_QUAD 0
+#endif
+
 // Workgroup size: 256 batches, fewer for the wide transforms so the LDS stage stays <= 32 KiB.
 template <int L>
 constexpr int gen_block() { return L <= 16 ? 256 : (L == 32 ? 128 : 64); }
@@ -245,12 +249,24 @@ __device__ __forceinline__ void transform_canon(const int64_t (&raw)[L], const G
 // per row pair (13 dwordx4 instead of 26 dwordx2 at n = 26) when WIDE (B even, 16-B aligned out).
 // (A persistent grid-stride variant was measured slower: the loop made hipcc keep the twiddle
 // words in SGPRs across tiles and spill.)
-template <int L, int N3, bool WIDE, bool CANON, bool LAZY, bool SIGNBIT = false>
-__global__ __launch_bounds__(gen_block<L>())
-__attribute__((amdgpu_waves_per_eu(gen_waves<L, N3, CANON, LAZY>(), gen_waves<L, N3, CANON, LAZY>())))
-void packed_gen_kernel(const int64_t* __restrict__ secrets, uint64_t D, const int64_t* __restrict__ draws,
-                       int64_t* __restrict__ out, uint32_t k, uint32_t t, uint64_t B,
-                       const GenTables* __restrict__ Tp, unsigned int* __restrict__ log, int xcd) {
+//
+// OT is the share type of `out`, int64_t or int32_t (sda_packed_generate32_dev: the shares are `% p` results,
+// p < 2^31, so the narrowing loses nothing).  The transform is the same; only the store tail differs.  STORE:
+//   0  each lane stores its own batch (odd B, or out not 16-byte aligned);
+//   1  the pair store above: 16 bytes per lane of i64 shares, 8 bytes of int32 ones;
+//   2  int32 only, B % 4 == 0: after the swap lanes 2m and 2m + 1 hold batches 4m .. 4m + 3 of one row; two row
+//      pairs at a time they trade halves (one DPP quad_perm per word), so each lane ends with four consecutive
+//      batches of one row: 16 bytes per lane, half the store instructions of form 1.  Measured 0.6-2 % SLOWER
+//      than form 1 at configs[2] in every process (5.33 against 5.23 ms canonical, 6.44 against 6.35 ms exact:
+//      the tail is not store-issue-bound, and the trade costs 12 DPP moves and 24 selects per lane; DESIGN.md
+//      §4.2, profiles/packed32), so it is compiled only with -DSDA_GEN32_QUAD=1 (A/B knob; SDA_GEN32_STORE=16
+//      then selects it at run time).
+template <class OT, int L, int N3, int STORE, bool CANON, bool LAZY, bool SIGNBIT>
+__device__ __forceinline__ void packed_gen_body(const int64_t* __restrict__ secrets, uint64_t D,
+                                                const int64_t* __restrict__ draws, OT* __restrict__ out, uint32_t k,
+                                                uint32_t t, uint64_t B, const GenTables* __restrict__ Tp,
+                                                unsigned int* __restrict__ log, int xcd) {
+    static_assert(STORE <= 1 || sizeof(OT) == 4, "the quad store is an int32 form");
     constexpr int LB = ilog(L, 2);
     constexpr int ND = ilog(N3, 3);
     constexpr int BS = gen_block<L>();
@@ -555,24 +571,73 @@ void packed_gen_kernel(const int64_t* __restrict__ secrets, uint64_t D, const in
         if constexpr (!CANON) set_prio<SDA_GEN_PRIO_STORE>();
         const uint64_t pb = b0 + pb_off;
         const bool st1 = pair_ok && pb + 1 < B;
-        int64_t* orow = out + ((uint64_t)vec * NR + half) * B + pb;
-        if constexpr (WIDE) {              // B even => pb + 1 < B whenever pb < B
-            static_for<0, NR / 2>([&](auto q) {
-                const auto r = __builtin_amdgcn_permlane32_swap((uint32_t)ys[1 + 2 * q], (uint32_t)ys[2 + 2 * q],
-                                                                false, false);
-                const int32_t lo = (int32_t)r[0], hi = (int32_t)r[1];  // batches pb, pb + 1 of row 1+2q+half
-                if (st1) {
-                    typedef int32_t v4i __attribute__((ext_vector_type(4)));
-                    v4i* d4 = reinterpret_cast<v4i*>(orow + (uint64_t)(2 * q) * B);
+        OT* orow = out + ((uint64_t)vec * NR + half) * B + pb;
+        typedef int32_t v2i __attribute__((ext_vector_type(2)));
+        typedef int32_t v4i __attribute__((ext_vector_type(4)));
+        // batches pb, pb + 1 of row 1 + 2 q + half (B even => pb + 1 < B whenever pb < B)
+        [[maybe_unused]] auto store_pair = [&](auto q, bool on) {
+            const auto r = __builtin_amdgcn_permlane32_swap((uint32_t)ys[1 + 2 * q], (uint32_t)ys[2 + 2 * q],
+                                                            false, false);
+            const int32_t lo = (int32_t)r[0], hi = (int32_t)r[1];
+            if (on) {                         // streamed once: keep it out of L2/MALL
+                if constexpr (sizeof(OT) == 8) {
                     const v4i val = {lo, lo >> 31, hi, hi >> 31};
-                    gen_store(val, d4);       // streamed once: keep it out of L2/MALL
+                    gen_store(val, reinterpret_cast<v4i*>(orow + (uint64_t)(2 * q) * B));
+                } else {
+                    const v2i val = {lo, hi};
+                    gen_store(val, reinterpret_cast<v2i*>(orow + (uint64_t)(2 * q) * B));
                 }
+            }
+        };
+        if constexpr (STORE == 2) {
+            // B % 4 == 0: the four batches of a quad are live together.  The quads are stored whether or not their
+            // pairs took the fast path: a pair that did not is in the log, and the fix-up kernel, next on the
+            // stream, rewrites every row of its batches.
+            const bool odd = lane & 1;
+            const bool stq = pb < B;
+            // rows 4 q + 2 odd + half, batches from the even lane's pb
+            OT* qrow = out + ((uint64_t)vec * NR + 2 * (odd ? 1u : 0u) + half) * B + (pb - 2 * (odd ? 1u : 0u));
+            static_for<0, NR / 4>([&](auto q) {
+                const auto ra = __builtin_amdgcn_permlane32_swap((uint32_t)ys[1 + 4 * q], (uint32_t)ys[2 + 4 * q],
+                                                                 false, false);
+                const auto rb = __builtin_amdgcn_permlane32_swap((uint32_t)ys[3 + 4 * q], (uint32_t)ys[4 + 4 * q],
+                                                                 false, false);
+                // the even lane keeps its rows 4q + half and takes the odd lane's; the odd lane keeps rows 4q + 2 + half
+                const int32_t s0 = (int32_t)(odd ? ra[0] : rb[0]), s1 = (int32_t)(odd ? ra[1] : rb[1]);
+                const int32_t g0 = __builtin_amdgcn_mov_dpp(s0, 0xB1, 0xF, 0xF, true);     // quad_perm [1, 0, 3, 2]
+                const int32_t g1 = __builtin_amdgcn_mov_dpp(s1, 0xB1, 0xF, 0xF, true);
+                const v4i val = odd ? v4i{g0, g1, (int32_t)rb[0], (int32_t)rb[1]}
+                                    : v4i{(int32_t)ra[0], (int32_t)ra[1], g0, g1};
+                if (stq) gen_store(val, reinterpret_cast<v4i*>(qrow + (uint64_t)(4 * q) * B));
             });
+            if constexpr (NR % 4 != 0) store_pair(std::integral_constant<int, NR / 2 - 1>{}, stq);
+        } else if constexpr (STORE == 1) {
+            static_for<0, NR / 2>([&](auto q) { store_pair(q, st1); });
         } else {                           // odd B: each lane stores its own batch
-            int64_t* own = out + (uint64_t)vec * NR * B + b;
-            static_for<1, N3>([&](auto j) { if (live && pair_ok) own[(uint64_t)(j - 1) * B] = (int64_t)ys[j]; });
+            OT* own = out + (uint64_t)vec * NR * B + b;
+            static_for<1, N3>([&](auto j) { if (live && pair_ok) own[(uint64_t)(j - 1) * B] = (OT)ys[j]; });
         }
     }
+}
+
+template <int L, int N3, bool WIDE, bool CANON, bool LAZY, bool SIGNBIT = false>
+__global__ __launch_bounds__(gen_block<L>())
+__attribute__((amdgpu_waves_per_eu(gen_waves<L, N3, CANON, LAZY>(), gen_waves<L, N3, CANON, LAZY>())))
+void packed_gen_kernel(const int64_t* __restrict__ secrets, uint64_t D, const int64_t* __restrict__ draws,
+                       int64_t* __restrict__ out, uint32_t k, uint32_t t, uint64_t B,
+                       const GenTables* __restrict__ Tp, unsigned int* __restrict__ log, int xcd) {
+    packed_gen_body<int64_t, L, N3, WIDE ? 1 : 0, CANON, LAZY, SIGNBIT>(secrets, D, draws, out, k, t, B, Tp, log, xcd);
+}
+
+// int32 shares (STORE as above), for n + 1 <= 27; the n + 1 = 81 objects dominate the build, and int32 output
+// there goes through the i64 kernels and launch_narrow32 (launch_packed_generate).
+template <int L, int N3, int STORE, bool CANON, bool LAZY, bool SIGNBIT = false>
+__global__ __launch_bounds__(gen_block<L>())
+__attribute__((amdgpu_waves_per_eu(gen_waves<L, N3, CANON, LAZY>(), gen_waves<L, N3, CANON, LAZY>())))
+void packed_gen32_kernel(const int64_t* __restrict__ secrets, uint64_t D, const int64_t* __restrict__ draws,
+                         int32_t* __restrict__ out, uint32_t k, uint32_t t, uint64_t B,
+                         const GenTables* __restrict__ Tp, unsigned int* __restrict__ log, int xcd) {
+    packed_gen_body<int32_t, L, N3, STORE, CANON, LAZY, SIGNBIT>(secrets, D, draws, out, k, t, B, Tp, log, xcd);
 }
 
 }  // namespace
@@ -583,7 +648,8 @@ static hipError_t gen_launch_mode(const PackedGenArgs& a, uint32_t k, uint32_t t
                                   uint32_t p, const GenFixupLog& log, hipStream_t s) {
     constexpr int BS = gen_block<L>();
     const dim3 grid((unsigned)((B + BS - 1) / BS), (unsigned)a.n_vectors);
-    const bool wide = B % 2 == 0 && ((uintptr_t)a.out % 16) == 0;
+    // (align_as: the i64 kernels run into scratch for an int32 caller and choose as for that caller's buffer)
+    const bool wide = B % 2 == 0 && ((uintptr_t)a.out % 16) == 0 && ((uintptr_t)a.align_as % 16) == 0;
     const int xcd = a.xcd_order && (uint64_t)grid.x * grid.y < (1ull << 32) ? 1 : 0;
     constexpr bool NONLAZY = CANON || gen_register_path(L, N3, true);
     if (wide && !CANON && p >= kLazyTruncMinP && a.signbit)   // exact shares, sign-bit radix-2 half
@@ -603,14 +669,55 @@ static hipError_t gen_launch_mode(const PackedGenArgs& a, uint32_t k, uint32_t t
     return hipSuccess;
 }
 
+// The same choice for int32 shares (a.out32).  Built with SDA_GEN32_QUAD, a.store32 == 2 (SDA_GEN32_STORE=16)
+// takes the 16-byte quad store when B % 4 == 0.
+template <int L, int N3, bool CANON>
+static hipError_t gen_launch_mode32(const PackedGenArgs& a, uint32_t k, uint32_t t, uint64_t B, const GenTables* T,
+                                    uint32_t p, const GenFixupLog& log, hipStream_t s) {
+    if constexpr (N3 > 27) {
+        return hipErrorInvalidValue;                          // launch_packed_generate narrows the i64 kernels' output
+    } else {
+        constexpr int BS = gen_block<L>();
+        const dim3 grid((unsigned)((B + BS - 1) / BS), (unsigned)a.n_vectors);
+        const bool wide = B % 2 == 0 && ((uintptr_t)a.out32 % 16) == 0;
+        constexpr bool QUAD = SDA_GEN32_QUAD;
+        const bool quad = QUAD && wide && B % 4 == 0 && a.store32 == 2;
+        const int xcd = a.xcd_order && (uint64_t)grid.x * grid.y < (1ull << 32) ? 1 : 0;
+#define SDA_GEN32(STORE, CN, LZ, SB)                                                                               \
+    hipLaunchKernelGGL((packed_gen32_kernel<L, N3, STORE, CN, LZ, SB>), grid, dim3(BS), 0, s, a.secrets, a.dimension, \
+                       a.draws, a.out32, k, t, B, T, log.count, xcd)
+#define SDA_GEN32_WIDE(CN, LZ, SB)                                 \
+    do {                                                           \
+        if constexpr (QUAD) {                                      \
+            if (quad) SDA_GEN32(2, CN, LZ, SB);                    \
+        }                                                          \
+        if (!quad) SDA_GEN32(1, CN, LZ, SB);                       \
+    } while (0)
+        if (wide && !CANON && p >= kLazyTruncMinP && a.signbit) {
+            SDA_GEN32_WIDE(false, true, true);
+        } else if (wide && !CANON && p >= kLazyTruncMinP) {
+            SDA_GEN32_WIDE(false, true, false);
+        } else if (wide) {
+            SDA_GEN32_WIDE(CANON, false, false);
+        } else {
+            SDA_GEN32(0, CANON, false, false);
+        }
+#undef SDA_GEN32_WIDE
+#undef SDA_GEN32
+        return hipSuccess;
+    }
+}
+
 template <int L, int N3>
 hipError_t gen_launch(const PackedGenArgs& a, uint32_t k, uint32_t t, uint64_t B, const GenTables* T,
                       const GenFixupLog& log, hipStream_t s) {
     constexpr int BS = gen_block<L>();
     if ((B + BS - 1) / BS > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const uint32_t p = a.prime;
-    const hipError_t e = a.canonical ? gen_launch_mode<L, N3, true>(a, k, t, B, T, p, log, s)
-                                     : gen_launch_mode<L, N3, false>(a, k, t, B, T, p, log, s);
+    const hipError_t e = a.out32 ? (a.canonical ? gen_launch_mode32<L, N3, true>(a, k, t, B, T, p, log, s)
+                                                : gen_launch_mode32<L, N3, false>(a, k, t, B, T, p, log, s))
+                         : a.canonical ? gen_launch_mode<L, N3, true>(a, k, t, B, T, p, log, s)
+                                       : gen_launch_mode<L, N3, false>(a, k, t, B, T, p, log, s);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }
@@ -629,12 +736,11 @@ namespace {
 // radix-2 level and outputs j, j + 64 of a radix-3 level, the state in LDS (radix-3 levels double
 // buffered, as their outputs overwrite other lanes' inputs).  If the log overflowed, every batch of the
 // launch is recomputed (correct, slow, and only reachable with raw i64 secrets far outside the field).
-__global__ __launch_bounds__(64) void packed_gen_fixup_kernel(const int64_t* __restrict__ secrets, uint64_t D,
-                                                              const int64_t* __restrict__ draws,
-                                                              int64_t* __restrict__ out, uint32_t k, uint32_t t,
-                                                              uint64_t B, uint64_t n_vec, int L, int N3,
-                                                              const GenTables* __restrict__ T, GenFixupLog log,
-                                                              int canonical) {
+template <class OT>
+__device__ __forceinline__ void gen_fixup_body(const int64_t* __restrict__ secrets, uint64_t D,
+                                               const int64_t* __restrict__ draws, OT* __restrict__ out, uint32_t k,
+                                               uint32_t t, uint64_t B, uint64_t n_vec, int L, int N3,
+                                               const GenTables* __restrict__ T, GenFixupLog log, int canonical) {
     const uint32_t n = *log.count;
     if (n == 0) return;
     const bool all = n > log.cap;
@@ -693,12 +799,31 @@ __global__ __launch_bounds__(64) void packed_gen_fixup_kernel(const int64_t* __r
         }
         __syncthreads();
         // shares = points[1..=n], clerk-major; CANONICAL: the exact share's canonical residue
-        int64_t* ob = out + vec * (uint64_t)(N3 - 1) * B + b;
+        OT* ob = out + vec * (uint64_t)(N3 - 1) * B + b;
         for (int j = lane + 1; j < N3; j += 64) {
             const int64_t v = ya[cur][j];
-            ob[(uint64_t)(j - 1) * B] = (canonical && v < 0) ? v + (int64_t)T->M.p : v;
+            ob[(uint64_t)(j - 1) * B] = (OT)((canonical && v < 0) ? v + (int64_t)T->M.p : v);   // |v| < p < 2^31
         }
     }
+}
+
+__global__ __launch_bounds__(64) void packed_gen_fixup_kernel(const int64_t* __restrict__ secrets, uint64_t D,
+                                                              const int64_t* __restrict__ draws,
+                                                              int64_t* __restrict__ out, uint32_t k, uint32_t t,
+                                                              uint64_t B, uint64_t n_vec, int L, int N3,
+                                                              const GenTables* __restrict__ T, GenFixupLog log,
+                                                              int canonical) {
+    gen_fixup_body(secrets, D, draws, out, k, t, B, n_vec, L, N3, T, log, canonical);
+}
+
+// the same fix-up writing int32 shares (every share is a `% p` result, so it fits)
+__global__ __launch_bounds__(64) void packed_gen32_fixup_kernel(const int64_t* __restrict__ secrets, uint64_t D,
+                                                                const int64_t* __restrict__ draws,
+                                                                int32_t* __restrict__ out, uint32_t k, uint32_t t,
+                                                                uint64_t B, uint64_t n_vec, int L, int N3,
+                                                                const GenTables* __restrict__ T, GenFixupLog log,
+                                                                int canonical) {
+    gen_fixup_body(secrets, D, draws, out, k, t, B, n_vec, L, N3, T, log, canonical);
 }
 
 }  // namespace
@@ -713,6 +838,21 @@ bool xcd_order_enabled() {
 
 size_t packed_gen_log_bytes() { return 64 + (size_t)kGenLogCap * sizeof(uint64_t); }
 
+// the register kernels' variant: WIDE stores need even B and a 16-byte aligned output (the caller's int32 buffer,
+// when the i64 kernels run into scratch for it); lazy truncation p >= 2^24
+static bool gen_takes_register_path(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p) {
+    const uint64_t B = (a.dimension + k - 1) / k;
+    const void* o = a.out32 ? (const void*)a.out32 : a.align_as ? a.align_as : (const void*)a.out;
+    const bool exact_nonlazy = !a.canonical && !(B % 2 == 0 && ((uintptr_t)o % 16) == 0 && p >= kLazyTruncMinP);
+    return gen_register_path(k + t + 1, n + 1, exact_nonlazy);
+}
+
+size_t packed_gen32_scratch_bytes(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p) {
+    if (n + 1 <= 27 || !gen_takes_register_path(a, k, t, n, p)) return 0;
+    const uint64_t B = (a.dimension + k - 1) / k;
+    return (size_t)(a.n_vectors * n * B) * sizeof(int64_t);
+}
+
 hipError_t launch_packed_generate(const PackedGenArgs& args, uint32_t k, uint32_t t, uint32_t n, uint32_t p,
                                   uint32_t omega_secrets, uint32_t omega_shares, DeviceTable& tab, void* log_buf,
                                   hipStream_t s, bool* logged) {
@@ -721,11 +861,23 @@ hipError_t launch_packed_generate(const PackedGenArgs& args, uint32_t k, uint32_
     a.prime = p;
     const uint32_t L = k + t + 1, N3 = n + 1;
     const uint64_t B = (a.dimension + k - 1) / k;
-    // the register kernels' variant: WIDE stores need even B and 16-byte aligned out; lazy truncation p >= 2^24
-    const bool exact_nonlazy = !a.canonical && !(B % 2 == 0 && ((uintptr_t)a.out % 16) == 0 && p >= kLazyTruncMinP);
-    if (!gen_register_path(L, N3, exact_nonlazy))            // past the register kernels: packed_wide.hip
+    if (!gen_takes_register_path(a, k, t, n, p))             // past the register kernels: packed_wide.hip
         return launch_packed_generate_wide(a, k, t, n, p, omega_secrets, omega_shares, tab, s);
     if (B == 0 || a.n_vectors == 0) return hipSuccess;
+    if (a.out32 && N3 > 27) {
+        // int32 shares at n + 1 = 81: the i64 register kernels into the caller's scratch, chosen as the i64 call
+        // with an output of a.out32's alignment would choose them, then one narrowing pass (no value is lost:
+        // every share is a `% p` result)
+        if (!a.scratch || !a.flag) return hipErrorInvalidValue;
+        PackedGenArgs b = a;
+        b.out = a.scratch;
+        b.align_as = a.out32;
+        b.out32 = nullptr;
+        const hipError_t e = launch_packed_generate(b, k, t, n, p, omega_secrets, omega_shares, tab, log_buf, s, logged);
+        if (e != hipSuccess) return e;
+        const uint64_t rows = a.n_vectors * n;
+        return launch_narrow32(a.scratch, rows, B, B, a.out32, B, a.flag, s);
+    }
     const uint32_t kv[5] = {L, N3, p, omega_secrets, omega_shares};
     std::vector<uint8_t> key((const uint8_t*)kv, (const uint8_t*)kv + sizeof(kv));
     if (tab.key != key) {
@@ -739,6 +891,10 @@ hipError_t launch_packed_generate(const PackedGenArgs& args, uint32_t k, uint32_
     const char* sb = getenv("SDA_GEN_SIGNBIT");                 // A/B knob: 0 = the mad_i64 sign kernel
     a.signbit = (tab.flags & 1u) && !(sb && sb[0] == '0');
     a.xcd_order = xcd_order_enabled();
+    if (a.out32) {
+        const char* st = getenv("SDA_GEN32_STORE");             // A/B knob, builds with SDA_GEN32_QUAD: 16 = quad store
+        a.store32 = st && st[0] == '1' && st[1] == '6' ? 2 : 0;
+    }
     const GenTables* T = static_cast<const GenTables*>(tab.dev);
     GenFixupLog log{static_cast<unsigned int*>(log_buf),
                     reinterpret_cast<uint64_t*>(static_cast<unsigned int*>(log_buf) + 16), kGenLogCap};
@@ -756,8 +912,12 @@ hipError_t launch_packed_generate(const PackedGenArgs& args, uint32_t k, uint32_
         default: e = hipErrorInvalidValue;
     }
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(packed_gen_fixup_kernel, dim3(512), dim3(64), 0, s, a.secrets, a.dimension, a.draws, a.out,
-                       k, t, B, a.n_vectors, (int)L, (int)N3, T, log, a.canonical ? 1 : 0);
+    if (a.out32)
+        hipLaunchKernelGGL(packed_gen32_fixup_kernel, dim3(512), dim3(64), 0, s, a.secrets, a.dimension, a.draws,
+                           a.out32, k, t, B, a.n_vectors, (int)L, (int)N3, T, log, a.canonical ? 1 : 0);
+    else
+        hipLaunchKernelGGL(packed_gen_fixup_kernel, dim3(512), dim3(64), 0, s, a.secrets, a.dimension, a.draws, a.out,
+                           k, t, B, a.n_vectors, (int)L, (int)N3, T, log, a.canonical ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -65,19 +65,30 @@ __device__ __forceinline__ void reveal_flush(int64_t* lds_o, int64_t* o, uint64_
 // branch-free indices, so every load can be issued before the first wait; each share is turned into
 // its (sign, residue) pair as it lands, so no i64 copy stays live.  Returns whether every share lies
 // in (-p, p).
-template <int MMAX, bool EAGER>
-__device__ __forceinline__ bool load_points(const int64_t* __restrict__ sh, uint64_t B, uint32_t m, uint32_t p,
+// v in (-p, p).  An int32 share is checked in 32 bits: v + (p - 1) mod 2^32 lies in [0, 2p - 2] exactly for those
+// v (above p - 1 the sum stays below 2^32, below -(p - 1) it is at least 2^31 + p - 1 > 2p - 2, as p < 2^31).
+__device__ __forceinline__ bool share_in_range(int64_t v, uint32_t, int64_t P) {
+    return (uint64_t)(v + (P - 1)) < (uint64_t)(2 * P - 1);
+}
+__device__ __forceinline__ bool share_in_range(int32_t v, uint32_t p, int64_t) {
+    return (uint32_t)v + (p - 1) <= 2 * p - 2;
+}
+
+// ST is the share type, int64_t or int32_t (sda_packed_reconstruct32_dev): an int32 share is sign-extended as it
+// lands and takes the same range check -- for small p most of the int32 range lies outside (-p, p).
+template <int MMAX, bool EAGER, class ST>
+__device__ __forceinline__ bool load_points(const ST* __restrict__ sh, uint64_t B, uint32_t m, uint32_t p,
                                             FE (&s)[MMAX]) {
     const int64_t P = (int64_t)p;
     s[0] = FE{0, 0};
     bool in_range = true;
-    auto take = [&](auto i, int64_t v) {
-        in_range = in_range && ((uint32_t)i >= m || (uint64_t)(v + (P - 1)) < (uint64_t)(2 * P - 1));
+    auto take = [&](auto i, ST v) {
+        in_range = in_range && ((uint32_t)i >= m || share_in_range(v, p, P));
         const int32_t x = (uint32_t)i < m ? (int32_t)v : 0;
         s[i] = FE{x, canon32(x, p)};
     };
     if constexpr (EAGER) {               // every load first (all in flight), then convert
-        int64_t v[MMAX];
+        ST v[MMAX];
         static_for<1, MMAX>([&](auto i) { v[i] = sh[(uint64_t)((uint32_t)i < m ? i - 1 : 0) * B]; });
         static_for<1, MMAX>([&](auto i) { take(i, v[i]); });
     } else {                             // convert as they land (no i64 copies live: fewer VGPRs)
@@ -235,13 +246,11 @@ __device__ __forceinline__ bool newton_reveal(FE (&s)[MMAX], uint32_t m, uint32_
 // i64 input) logs the batch and stores garbage; packed_reveal_fixup_kernel, launched right after on the same stream,
 // recomputes the logged batches (exact truncation in registers, or the generic i64 path).  Keeping
 // the generic path (a 128-entry i64 array per lane) out of this kernel keeps it free of scratch.
-template <int MMAX, bool STAGED, int KU, bool LAZY, bool FULL = false>
-__global__ __launch_bounds__(256) void packed_reveal_exact_kernel(const int64_t* __restrict__ shares, uint64_t B,
-                                                                  uint64_t D, int64_t* __restrict__ out,
-                                                                  uint32_t n_idx, uint32_t k,
-                                                                  const uint32_t* __restrict__ tab, MontP M,
-                                                                  unsigned int* __restrict__ log, int xcd) {
-    extern __shared__ int64_t lds_o[];
+template <class ST, int MMAX, bool STAGED, int KU, bool LAZY, bool FULL>
+__device__ __forceinline__ void reveal_exact_body(const ST* __restrict__ shares, uint64_t B, uint64_t D,
+                                                  int64_t* __restrict__ out, uint32_t n_idx, uint32_t k,
+                                                  const uint32_t* __restrict__ tab, const MontP& M,
+                                                  unsigned int* __restrict__ log, int xcd, int64_t* lds_o) {
     const uint32_t tid = threadIdx.x;
     // XCD-chunked tile order (xcd.h), for the point counts up to 16 (the benchmarked sizes; the wide
     // instantiations keep the natural order's code unchanged)
@@ -252,7 +261,7 @@ __global__ __launch_bounds__(256) void packed_reveal_exact_kernel(const int64_t*
     const uint64_t b0 = (uint64_t)tile * 256, b = b0 + tid;
     const bool live = b < B;
     const uint64_t vec = vy;
-    const int64_t* sh = shares + vec * (uint64_t)n_idx * B + (live ? b : B - 1);
+    const ST* sh = shares + vec * (uint64_t)n_idx * B + (live ? b : B - 1);
     int64_t* o = out + vec * D;
     const uint32_t m = FULL ? (uint32_t)MMAX : n_idx + 1;
     int64_t* dst = STAGED ? lds_o + tid * k : o + b * k;
@@ -268,15 +277,36 @@ __global__ __launch_bounds__(256) void packed_reveal_exact_kernel(const int64_t*
     reveal_flush<STAGED>(lds_o, o, b0, B, D, k);
 }
 
+template <int MMAX, bool STAGED, int KU, bool LAZY, bool FULL = false>
+__global__ __launch_bounds__(256) void packed_reveal_exact_kernel(const int64_t* __restrict__ shares, uint64_t B,
+                                                                  uint64_t D, int64_t* __restrict__ out,
+                                                                  uint32_t n_idx, uint32_t k,
+                                                                  const uint32_t* __restrict__ tab, MontP M,
+                                                                  unsigned int* __restrict__ log, int xcd) {
+    extern __shared__ int64_t lds_o[];
+    reveal_exact_body<int64_t, MMAX, STAGED, KU, LAZY, FULL>(shares, B, D, out, n_idx, k, tab, M, log, xcd, lds_o);
+}
+
+template <int MMAX, bool STAGED, int KU, bool LAZY, bool FULL = false>
+__global__ __launch_bounds__(256) void packed_reveal32_exact_kernel(const int32_t* __restrict__ shares, uint64_t B,
+                                                                    uint64_t D, int64_t* __restrict__ out,
+                                                                    uint32_t n_idx, uint32_t k,
+                                                                    const uint32_t* __restrict__ tab, MontP M,
+                                                                    unsigned int* __restrict__ log, int xcd) {
+    extern __shared__ int64_t lds_o[];
+    reveal_exact_body<int32_t, MMAX, STAGED, KU, LAZY, FULL>(shares, B, D, out, n_idx, k, tab, M, log, xcd, lds_o);
+}
+
 // Generic exact reveal of one batch (shares outside (-p, p)): tss' Newton divided differences and
 // evaluation with wrapping i64 arithmetic and truncated `%`, reading the batch's shares from global
 // memory.  Writes its first `lim` secrets to dst[0..lim).
-__device__ void reveal_exact_generic(const int64_t* __restrict__ sh, uint64_t B, uint32_t m, uint32_t k,
+template <class ST>
+__device__ void reveal_exact_generic(const ST* __restrict__ sh, uint64_t B, uint32_t m, uint32_t k,
                                      const uint32_t* __restrict__ tab, uint32_t p, int64_t* dst, uint32_t lim) {
     const Mod64 P = make_mod64((int64_t)p);
     int64_t s[TS];
     s[0] = 0;
-    for (uint32_t i = 1; i < m; ++i) s[i] = sh[(uint64_t)(i - 1) * B];
+    for (uint32_t i = 1; i < m; ++i) s[i] = (int64_t)sh[(uint64_t)(i - 1) * B];
     for (uint32_t j = 1; j < m; ++j)
         for (uint32_t i = m - 1; i >= j; --i) {
             const int64_t cd = trem64(wsub(s[i], s[i - 1]), P);
@@ -296,8 +326,8 @@ __device__ void reveal_exact_generic(const int64_t* __restrict__ sh, uint64_t B,
 // register path with tss' truncation verbatim; out-of-range ones take the generic i64 path.  If the
 // log overflowed, every batch of the launch is recomputed (correct and slow; only reachable with raw
 // i64 shares).  One wave per workgroup: a logged batch is rare, so few lanes are busy.
-template <int MMAX, int KU>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void packed_reveal_fixup_kernel(const int64_t* __restrict__ shares, uint64_t B,
+template <int MMAX, int KU, class ST = int64_t>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void packed_reveal_fixup_kernel(const ST* __restrict__ shares, uint64_t B,
                                                                  uint64_t D, uint64_t n_vec, int64_t* __restrict__ out,
                                                                  uint32_t n_idx, uint32_t k,
                                                                  const uint32_t* __restrict__ tab, MontP M,
@@ -312,7 +342,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         const uint64_t gb = all ? i : list[i];
         const uint64_t vec = gb / B, b = gb - vec * B;
         const uint32_t lim = b * k < D ? (uint32_t)(D - b * k < k ? D - b * k : k) : 0u;
-        const int64_t* sh = shares + vec * (uint64_t)n_idx * B + b;
+        const ST* sh = shares + vec * (uint64_t)n_idx * B + b;
         int64_t* dst = out + vec * D + b * k;
         FE s[MMAX];
         if (load_points<MMAX, false>(sh, B, m, M.p, s)) newton_reveal<MMAX, KU, false, false>(s, m, k, tab, M, dst, lim);
@@ -351,12 +381,11 @@ __device__ __forceinline__ int32_t trem_small(int64_t v, uint32_t p) {
 // Shares in (-p, p) keep every tss intermediate in (-p, p): 32-bit values, `%` of products through
 // trem_prod; otherwise (raw i64 shares) the generic i64 arithmetic.  A trapped batch is a serial
 // latency chain for one lane on the register path (~40 us); spread over the wave it is m + k short steps.
-template <int MMAX>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void packed_reveal_fixup_wave_kernel(const int64_t* __restrict__ shares, uint64_t B,
-                                                                      uint64_t D, uint64_t n_vec,
-                                                                      int64_t* __restrict__ out, uint32_t n_idx,
-                                                                      uint32_t k, const uint32_t* __restrict__ tab,
-                                                                      uint32_t p, const unsigned int* __restrict__ log) {
+template <int MMAX, class ST>
+__device__ __forceinline__ void reveal_fixup_wave_body(const ST* __restrict__ shares, uint64_t B, uint64_t D,
+                                                       uint64_t n_vec, int64_t* __restrict__ out, uint32_t n_idx,
+                                                       uint32_t k, const uint32_t* __restrict__ tab, uint32_t p,
+                                                       const unsigned int* __restrict__ log) {
     static_assert(MMAX <= 64, "one lane per Newton point");
     const uint32_t n = *log;
     if (n == 0) return;
@@ -392,7 +421,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         const uint64_t gb = all ? w : list[w];
         const uint64_t vec = gb / B, b = gb - vec * B;
         // point 0 is the inserted (1, 0); point i >= 1 is clerk share i - 1 (batched.rs:83-85)
-        int64_t s = (lane >= 1 && lane < m) ? shares[vec * (uint64_t)n_idx * B + (uint64_t)(lane - 1) * B + b] : 0;
+        int64_t s = (lane >= 1 && lane < m) ? (int64_t)shares[vec * (uint64_t)n_idx * B + (uint64_t)(lane - 1) * B + b] : 0;
         const bool small = __all((uint64_t)(s + (int64_t)p - 1) < (uint64_t)(2 * (int64_t)p - 1));
         const uint32_t lim = b * k < D ? (uint32_t)(D - b * k < k ? D - b * k : k) : 0u;
         int64_t acc = 0;
@@ -428,12 +457,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     }
 }
 
-template <int NMAX, bool STAGED>
-__global__ __launch_bounds__(256) void packed_reveal_canon_kernel(const int64_t* __restrict__ shares, uint64_t B,
-                                                                  uint64_t D, int64_t* __restrict__ out,
-                                                                  uint32_t n_idx, uint32_t k,
-                                                                  const uint32_t* __restrict__ tab, MontP M, int xcd) {
-    extern __shared__ int64_t lds_o[];
+template <int MMAX>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void packed_reveal_fixup_wave_kernel(const int64_t* __restrict__ shares, uint64_t B,
+                                                                      uint64_t D, uint64_t n_vec,
+                                                                      int64_t* __restrict__ out, uint32_t n_idx,
+                                                                      uint32_t k, const uint32_t* __restrict__ tab,
+                                                                      uint32_t p, const unsigned int* __restrict__ log) {
+    reveal_fixup_wave_body<MMAX>(shares, B, D, n_vec, out, n_idx, k, tab, p, log);
+}
+
+template <int MMAX>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void packed_reveal32_fixup_wave_kernel(const int32_t* __restrict__ shares, uint64_t B,
+                                                                      uint64_t D, uint64_t n_vec,
+                                                                      int64_t* __restrict__ out, uint32_t n_idx,
+                                                                      uint32_t k, const uint32_t* __restrict__ tab,
+                                                                      uint32_t p, const unsigned int* __restrict__ log) {
+    reveal_fixup_wave_body<MMAX>(shares, B, D, n_vec, out, n_idx, k, tab, p, log);
+}
+
+template <class ST, int NMAX, bool STAGED>
+__device__ __forceinline__ void reveal_canon_body(const ST* __restrict__ shares, uint64_t B, uint64_t D,
+                                                  int64_t* __restrict__ out, uint32_t n_idx, uint32_t k,
+                                                  const uint32_t* __restrict__ tab, const MontP& M, int xcd,
+                                                  int64_t* lds_o) {
     const uint32_t tid = threadIdx.x;
     uint32_t tile = blockIdx.x, vy = blockIdx.y;
     if constexpr (NMAX <= 16) {
@@ -442,7 +488,7 @@ __global__ __launch_bounds__(256) void packed_reveal_canon_kernel(const int64_t*
     const uint64_t b0 = (uint64_t)tile * 256, b = b0 + tid;
     const bool live = b < B;
     const uint64_t vec = vy;
-    const int64_t* sh = shares + vec * (uint64_t)n_idx * B + (live ? b : B - 1);
+    const ST* sh = shares + vec * (uint64_t)n_idx * B + (live ? b : B - 1);
     int64_t* o = out + vec * D;
     const uint32_t p = M.p;
     const int64_t P = (int64_t)p;
@@ -451,12 +497,12 @@ __global__ __launch_bounds__(256) void packed_reveal_canon_kernel(const int64_t*
 
     uint32_t S[NMAX];
     bool in_range = true;
-    auto take = [&](auto i, int64_t v) {
-        in_range = in_range && ((uint32_t)i >= n_idx || (uint64_t)(v + (P - 1)) < (uint64_t)(2 * P - 1));
+    auto take = [&](auto i, ST v) {
+        in_range = in_range && ((uint32_t)i >= n_idx || share_in_range(v, p, P));
         S[i] = (uint32_t)i < n_idx ? canon32((int32_t)v, p) : 0u;
     };
     if constexpr (NMAX <= 32) {          // every load first (all in flight), then convert
-        int64_t v[NMAX];
+        ST v[NMAX];
         static_for<0, NMAX>([&](auto i) { v[i] = sh[(uint64_t)((uint32_t)i < n_idx ? i : 0) * B]; });
         static_for<0, NMAX>([&](auto i) { take(i, v[i]); });
     } else {                             // wide sets: convert as they land (no i64 copies live)
@@ -465,7 +511,7 @@ __global__ __launch_bounds__(256) void packed_reveal_canon_kernel(const int64_t*
     if (!in_range) {                    // raw i64 shares: exact canonical residues (rare; reloaded)
         const Mod64 PM = make_mod64(P);
         static_for<0, NMAX>([&](auto i) {
-            const int64_t r = trem64(sh[(uint64_t)((uint32_t)i < n_idx ? i : 0) * B], PM);
+            const int64_t r = trem64((int64_t)sh[(uint64_t)((uint32_t)i < n_idx ? i : 0) * B], PM);
             S[i] = (uint32_t)i < n_idx ? (uint32_t)(r < 0 ? r + P : r) : 0u;
         });
     }
@@ -485,31 +531,60 @@ __global__ __launch_bounds__(256) void packed_reveal_canon_kernel(const int64_t*
     reveal_flush<STAGED>(lds_o, o, b0, B, D, k);
 }
 
+template <int NMAX, bool STAGED>
+__global__ __launch_bounds__(256) void packed_reveal_canon_kernel(const int64_t* __restrict__ shares, uint64_t B,
+                                                                  uint64_t D, int64_t* __restrict__ out,
+                                                                  uint32_t n_idx, uint32_t k,
+                                                                  const uint32_t* __restrict__ tab, MontP M, int xcd) {
+    extern __shared__ int64_t lds_o[];
+    reveal_canon_body<int64_t, NMAX, STAGED>(shares, B, D, out, n_idx, k, tab, M, xcd, lds_o);
+}
+
+template <int NMAX, bool STAGED>
+__global__ __launch_bounds__(256) void packed_reveal32_canon_kernel(const int32_t* __restrict__ shares, uint64_t B,
+                                                                    uint64_t D, int64_t* __restrict__ out,
+                                                                    uint32_t n_idx, uint32_t k,
+                                                                    const uint32_t* __restrict__ tab, MontP M, int xcd) {
+    extern __shared__ int64_t lds_o[];
+    reveal_canon_body<int32_t, NMAX, STAGED>(shares, B, D, out, n_idx, k, tab, M, xcd, lds_o);
+}
+
 }  // namespace
 
-template <int MM>
-hipError_t reveal_launch(int mode, const PackedRevealArgs& a, uint64_t B, uint32_t n_idx, uint32_t k, bool lazy,
-                         const uint32_t* tab, const MontP& M, unsigned int* log, hipStream_t s) {
+// The launches of one bucket for share type ST: the i64 kernels, or their int32 twins by the same rules.
+#define SDA_REVEAL_K(NAME, NAME32, LDS, ...)                                                                   \
+    do {                                                                                                       \
+        if constexpr (sizeof(ST) == 8)                                                                         \
+            hipLaunchKernelGGL((NAME<__VA_ARGS__>), grid, dim3(256), LDS, s, sh, B, a.dimension, a.out, n_idx, k, tab, M, \
+                               SDA_REVEAL_TAIL);                                                               \
+        else                                                                                                   \
+            hipLaunchKernelGGL((NAME32<__VA_ARGS__>), grid, dim3(256), LDS, s, sh, B, a.dimension, a.out, n_idx, k, tab, \
+                               M, SDA_REVEAL_TAIL);                                                            \
+    } while (0)
+#define SDA_REVEAL_EXACT(LDS, ...) SDA_REVEAL_K(packed_reveal_exact_kernel, packed_reveal32_exact_kernel, LDS, __VA_ARGS__)
+#define SDA_REVEAL_CANON(LDS, ...) SDA_REVEAL_K(packed_reveal_canon_kernel, packed_reveal32_canon_kernel, LDS, __VA_ARGS__)
+
+template <int MM, class ST>
+static hipError_t reveal_launch_t(int mode, const PackedRevealArgs& a, const ST* sh, uint64_t B, uint32_t n_idx,
+                                  uint32_t k, bool lazy, const uint32_t* tab, const MontP& M, unsigned int* log,
+                                  hipStream_t s) {
     dim3 grid((unsigned)((B + 255) / 256), (unsigned)a.n_vectors);
     const bool staged = k <= 16;                      // LDS stage: 256 * k * 8 B <= 32 KiB
     const size_t lds = staged ? (size_t)256 * k * sizeof(int64_t) : 0;
     const int xcd = xcd_order_enabled() && (uint64_t)grid.x * grid.y < (1ull << 32) ? 1 : 0;
     if (mode == 0) {
+#define SDA_REVEAL_TAIL log, xcd
         bool done = false;
         if constexpr (MM <= 16) {
             // lazy (launch_packed_reveal): p >= kLazyTruncMinP and exactly t + k shares, so n_idx + 1 = k + t + 1 is a
             // power of 2: 16 points are this bucket's FULL kernel, 2 or 4 the 8-point bucket's partial one
             done = staged && k <= 8;
             if (done && lazy && n_idx + 1 == MM)
-                hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, true, 8, true, true>), grid, dim3(256), lds, s,
-                                   a.shares, B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
+                SDA_REVEAL_EXACT(lds, MM, true, 8, true, true);
             else if (done && lazy && MM == 8) {
-                if constexpr (MM == 8)
-                    hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, true, 8, true>), grid, dim3(256), lds, s,
-                                       a.shares, B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
+                if constexpr (MM == 8) SDA_REVEAL_EXACT(lds, MM, true, 8, true);
             } else if (done)
-                hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, true, 8, false>), grid, dim3(256), lds, s,
-                                   a.shares, B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
+                SDA_REVEAL_EXACT(lds, MM, true, 8, false);
         }
         // A reveal takes at least k shares (n_idx >= t + k: sda_packed_reconstruct_dev), so k < MM: the staged
         // kernel without the unrolled evaluation (8 < k <= 16) exists from MM = 16, the unstaged one (k > 16)
@@ -517,42 +592,56 @@ hipError_t reveal_launch(int mode, const PackedRevealArgs& a, uint64_t B, uint32
         if (done) {
         } else if (staged) {
             if constexpr (MM > 8)
-                hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, true, 0, false>), grid, dim3(256), lds, s,
-                                   a.shares, B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
+                SDA_REVEAL_EXACT(lds, MM, true, 0, false);
             else
                 return hipErrorInvalidValue;
         } else {
             if constexpr (MM > 16)
-                hipLaunchKernelGGL((packed_reveal_exact_kernel<MM, false, 0, false>), grid, dim3(256), 0, s,
-                                   a.shares, B, a.dimension, a.out, n_idx, k, tab, M, log, xcd);
+                SDA_REVEAL_EXACT(0, MM, false, 0, false);
             else
                 return hipErrorInvalidValue;
         }
+#undef SDA_REVEAL_TAIL
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
+        bool wave = false;
         if constexpr (MM <= 64) {
-            if (k <= 64)
-                hipLaunchKernelGGL((packed_reveal_fixup_wave_kernel<MM>), dim3(1024), dim3(64), 0, s, a.shares, B,
-                                   a.dimension, a.n_vectors, a.out, n_idx, k, tab, M.p, log);
-            else
-                hipLaunchKernelGGL((packed_reveal_fixup_kernel<MM, 0>), dim3(64), dim3(64), 0, s, a.shares, B,
-                                   a.dimension, a.n_vectors, a.out, n_idx, k, tab, M, log);
-        } else
-            hipLaunchKernelGGL((packed_reveal_fixup_kernel<MM, 0>), dim3(64), dim3(64), 0, s, a.shares, B,
+            wave = k <= 64;
+            if (wave) {
+                if constexpr (sizeof(ST) == 8)
+                    hipLaunchKernelGGL((packed_reveal_fixup_wave_kernel<MM>), dim3(1024), dim3(64), 0, s, sh, B,
+                                       a.dimension, a.n_vectors, a.out, n_idx, k, tab, M.p, log);
+                else
+                    hipLaunchKernelGGL((packed_reveal32_fixup_wave_kernel<MM>), dim3(1024), dim3(64), 0, s, sh, B,
+                                       a.dimension, a.n_vectors, a.out, n_idx, k, tab, M.p, log);
+            }
+        }
+        if (!wave)
+            hipLaunchKernelGGL((packed_reveal_fixup_kernel<MM, 0, ST>), dim3(64), dim3(64), 0, s, sh, B,
                                a.dimension, a.n_vectors, a.out, n_idx, k, tab, M, log);
     } else if constexpr (MM <= 32) {
+#define SDA_REVEAL_TAIL xcd
         if (staged)
-            hipLaunchKernelGGL((packed_reveal_canon_kernel<MM, true>), grid, dim3(256), lds, s, a.shares, B,
-                               a.dimension, a.out, n_idx, k, tab, M, xcd);
+            SDA_REVEAL_CANON(lds, MM, true);
         else if constexpr (MM > 16)                   // k <= n_idx <= MM: unstaged (k > 16) only at MM = 32
-            hipLaunchKernelGGL((packed_reveal_canon_kernel<MM, false>), grid, dim3(256), 0, s, a.shares, B,
-                               a.dimension, a.out, n_idx, k, tab, M, xcd);
+            SDA_REVEAL_CANON(0, MM, false);
         else
             return hipErrorInvalidValue;
+#undef SDA_REVEAL_TAIL
     } else {
         return hipErrorInvalidValue;                  // launch_packed_reveal runs these as exact + canonical
     }
     return hipGetLastError();
+}
+#undef SDA_REVEAL_EXACT
+#undef SDA_REVEAL_CANON
+#undef SDA_REVEAL_K
+
+template <int MM>
+hipError_t reveal_launch(int mode, const PackedRevealArgs& a, uint64_t B, uint32_t n_idx, uint32_t k, bool lazy,
+                         const uint32_t* tab, const MontP& M, unsigned int* log, hipStream_t s) {
+    return a.shares32 ? reveal_launch_t<MM>(mode, a, a.shares32, B, n_idx, k, lazy, tab, M, log, s)
+                      : reveal_launch_t<MM>(mode, a, a.shares, B, n_idx, k, lazy, tab, M, log, s);
 }
 template hipError_t reveal_launch<SDA_REVEAL_PART>(int, const PackedRevealArgs&, uint64_t, uint32_t, uint32_t, bool,
                                                    const uint32_t*, const MontP&, unsigned int*, hipStream_t);

@@ -30,12 +30,13 @@ __device__ __forceinline__ uint32_t rev_trits_rt(uint32_t i, uint32_t ndig) {
 // Device table of the wide share-gen (i64 words): tw2[L-1] (radix-2 level len: entries
 // [len/2 - 1, len - 1)), linv, tw3[W3] and sq3[W3] (radix-3 level len: entries [(len-3)/2, (len-3)/2 +
 // len)), W3 = (3 (n+1) - 3) / 2 -- the layout of GenTables without its size caps.
-__global__ __launch_bounds__(256) void packed_gen_wide_kernel(const int64_t* __restrict__ secrets, uint64_t D,
-                                                              const int64_t* __restrict__ draws,
-                                                              int64_t* __restrict__ out, uint32_t k, uint32_t t,
-                                                              uint64_t B, uint64_t n_vec, uint32_t L, uint32_t N3,
-                                                              const int64_t* __restrict__ tab, int64_t p,
-                                                              int64_t* __restrict__ ws, uint64_t lanes, int canonical) {
+// (OT: the share type of out, i64 or int32 -- every share is a `% p` result, p < 2^31.)
+template <class OT>
+__device__ __forceinline__ void gen_wide_body(const int64_t* __restrict__ secrets, uint64_t D,
+                                              const int64_t* __restrict__ draws, OT* __restrict__ out, uint32_t k,
+                                              uint32_t t, uint64_t B, uint64_t n_vec, uint32_t L, uint32_t N3,
+                                              const int64_t* __restrict__ tab, int64_t p, int64_t* __restrict__ ws,
+                                              uint64_t lanes, int canonical) {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= lanes) return;
     const Mod64 P = make_mod64(p);
@@ -90,24 +91,42 @@ __global__ __launch_bounds__(256) void packed_gen_wide_kernel(const int64_t* __r
                 }
         }
         // shares = points[1..=n], clerk-major (batched.rs:46-48)
-        int64_t* o = out + vec * (uint64_t)(N3 - 1) * B + b;
+        OT* o = out + vec * (uint64_t)(N3 - 1) * B + b;
         for (uint32_t j = 1; j < N3; ++j) {
             const int64_t v = y(j);
-            o[(uint64_t)(j - 1) * B] = canonical && v < 0 ? v + p : v;
+            o[(uint64_t)(j - 1) * B] = (OT)(canonical && v < 0 ? v + p : v);
         }
     }
+}
+
+__global__ __launch_bounds__(256) void packed_gen_wide_kernel(const int64_t* __restrict__ secrets, uint64_t D,
+                                                              const int64_t* __restrict__ draws,
+                                                              int64_t* __restrict__ out, uint32_t k, uint32_t t,
+                                                              uint64_t B, uint64_t n_vec, uint32_t L, uint32_t N3,
+                                                              const int64_t* __restrict__ tab, int64_t p,
+                                                              int64_t* __restrict__ ws, uint64_t lanes, int canonical) {
+    gen_wide_body(secrets, D, draws, out, k, t, B, n_vec, L, N3, tab, p, ws, lanes, canonical);
+}
+
+__global__ __launch_bounds__(256) void packed_gen32_wide_kernel(const int64_t* __restrict__ secrets, uint64_t D,
+                                                                const int64_t* __restrict__ draws,
+                                                                int32_t* __restrict__ out, uint32_t k, uint32_t t,
+                                                                uint64_t B, uint64_t n_vec, uint32_t L, uint32_t N3,
+                                                                const int64_t* __restrict__ tab, int64_t p,
+                                                                int64_t* __restrict__ ws, uint64_t lanes, int canonical) {
+    gen_wide_body(secrets, D, draws, out, k, t, B, n_vec, L, N3, tab, p, ws, lanes, canonical);
 }
 
 // Wide reveal: tss' Newton divided differences over the m = n_idx + 1 points (the inserted (1, 0)
 // first), then newton_evaluate at omega_secrets^(e+1).  inv[j m + i] = mod_inverse(points[i] -
 // points[i-j]); np[e m + i] = the signed Newton basis at omega_secrets^(e+1) (as packed_reveal.hip's
 // host tables, stride m).  CANONICAL: the exact value's canonical residue (= positive()).
-__global__ __launch_bounds__(256) void packed_reveal_wide_kernel(const int64_t* __restrict__ shares, uint64_t B,
-                                                                 uint64_t D, uint64_t n_vec, int64_t* __restrict__ out,
-                                                                 uint32_t n_idx, uint32_t k,
-                                                                 const int64_t* __restrict__ inv,
-                                                                 const int64_t* __restrict__ np, int64_t p,
-                                                                 int64_t* __restrict__ ws, uint64_t lanes, int canonical) {
+// (ST: the share type, i64 or int32 sign-extended as it is read.)
+template <class ST>
+__device__ __forceinline__ void reveal_wide_body(const ST* __restrict__ shares, uint64_t B, uint64_t D, uint64_t n_vec,
+                                                 int64_t* __restrict__ out, uint32_t n_idx, uint32_t k,
+                                                 const int64_t* __restrict__ inv, const int64_t* __restrict__ np,
+                                                 int64_t p, int64_t* __restrict__ ws, uint64_t lanes, int canonical) {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= lanes) return;
     const Mod64 P = make_mod64(p);
@@ -117,9 +136,9 @@ __global__ __launch_bounds__(256) void packed_reveal_wide_kernel(const int64_t* 
     const uint64_t total = B * n_vec;
     for (uint64_t gb = gid; gb < total; gb += lanes) {
         const uint64_t vec = gb / B, b = gb - vec * B;
-        const int64_t* sh = shares + vec * (uint64_t)n_idx * B + b;
+        const ST* sh = shares + vec * (uint64_t)n_idx * B + b;
         s(0) = 0;
-        for (uint32_t i = 1; i < m; ++i) s(i) = sh[(uint64_t)(i - 1) * B];     // batched.rs:83-85
+        for (uint32_t i = 1; i < m; ++i) s(i) = (int64_t)sh[(uint64_t)(i - 1) * B];     // batched.rs:83-85
         for (uint32_t j = 1; j < m; ++j) {
             const int64_t* invj = inv + (uint64_t)j * m;
             int64_t hi = s(m - 1);                       // s[i] of this level, walking i downwards
@@ -137,6 +156,25 @@ __global__ __launch_bounds__(256) void packed_reveal_wide_kernel(const int64_t* 
             out[vec * D + base + e] = canonical && acc < 0 ? acc + p : acc;     // batched.rs:94
         }
     }
+}
+
+__global__ __launch_bounds__(256) void packed_reveal_wide_kernel(const int64_t* __restrict__ shares, uint64_t B,
+                                                                 uint64_t D, uint64_t n_vec, int64_t* __restrict__ out,
+                                                                 uint32_t n_idx, uint32_t k,
+                                                                 const int64_t* __restrict__ inv,
+                                                                 const int64_t* __restrict__ np, int64_t p,
+                                                                 int64_t* __restrict__ ws, uint64_t lanes, int canonical) {
+    reveal_wide_body(shares, B, D, n_vec, out, n_idx, k, inv, np, p, ws, lanes, canonical);
+}
+
+__global__ __launch_bounds__(256) void packed_reveal32_wide_kernel(const int32_t* __restrict__ shares, uint64_t B,
+                                                                   uint64_t D, uint64_t n_vec,
+                                                                   int64_t* __restrict__ out, uint32_t n_idx, uint32_t k,
+                                                                   const int64_t* __restrict__ inv,
+                                                                   const int64_t* __restrict__ np, int64_t p,
+                                                                   int64_t* __restrict__ ws, uint64_t lanes,
+                                                                   int canonical) {
+    reveal_wide_body(shares, B, D, n_vec, out, n_idx, k, inv, np, p, ws, lanes, canonical);
 }
 
 // Lanes in flight: enough to fill the chip, few enough that the workspace stays <= ~256 MiB.
@@ -199,9 +237,16 @@ hipError_t launch_packed_generate_wide(const PackedGenArgs& a, uint32_t k, uint3
     const uint64_t lanes = wide_lanes(B * a.n_vectors, (uint64_t)L + N3);
     hipError_t e = ensure_ws(tab, lanes * ((uint64_t)L + N3) * sizeof(int64_t));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(packed_gen_wide_kernel, dim3((unsigned)(lanes / 256)), dim3(256), 0, s, a.secrets, a.dimension,
-                       a.draws, a.out, k, t, B, a.n_vectors, L, N3, static_cast<const int64_t*>(tab.dev), (int64_t)p,
-                       static_cast<int64_t*>(tab.ws), lanes, a.canonical ? 1 : 0);
+    if (a.out32)
+        hipLaunchKernelGGL(packed_gen32_wide_kernel, dim3((unsigned)(lanes / 256)), dim3(256), 0, s, a.secrets,
+                           a.dimension, a.draws, a.out32, k, t, B, a.n_vectors, L, N3,
+                           static_cast<const int64_t*>(tab.dev), (int64_t)p, static_cast<int64_t*>(tab.ws), lanes,
+                           a.canonical ? 1 : 0);
+    else
+        hipLaunchKernelGGL(packed_gen_wide_kernel, dim3((unsigned)(lanes / 256)), dim3(256), 0, s, a.secrets,
+                           a.dimension, a.draws, a.out, k, t, B, a.n_vectors, L, N3,
+                           static_cast<const int64_t*>(tab.dev), (int64_t)p, static_cast<int64_t*>(tab.ws), lanes,
+                           a.canonical ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -247,9 +292,14 @@ hipError_t launch_packed_reveal_wide(const PackedRevealArgs& a, const uint64_t* 
     hipError_t e = ensure_ws(tab, lanes * (uint64_t)m * sizeof(int64_t));
     if (e != hipSuccess) return e;
     const int64_t* inv = static_cast<const int64_t*>(tab.dev);
-    hipLaunchKernelGGL(packed_reveal_wide_kernel, dim3((unsigned)(lanes / 256)), dim3(256), 0, s, a.shares, B,
-                       a.dimension, a.n_vectors, a.out, n_idx, k, inv, inv + (uint64_t)m * m, P,
-                       static_cast<int64_t*>(tab.ws), lanes, mode == 1 ? 1 : 0);
+    if (a.shares32)
+        hipLaunchKernelGGL(packed_reveal32_wide_kernel, dim3((unsigned)(lanes / 256)), dim3(256), 0, s, a.shares32, B,
+                           a.dimension, a.n_vectors, a.out, n_idx, k, inv, inv + (uint64_t)m * m, P,
+                           static_cast<int64_t*>(tab.ws), lanes, mode == 1 ? 1 : 0);
+    else
+        hipLaunchKernelGGL(packed_reveal_wide_kernel, dim3((unsigned)(lanes / 256)), dim3(256), 0, s, a.shares, B,
+                           a.dimension, a.n_vectors, a.out, n_idx, k, inv, inv + (uint64_t)m * m, P,
+                           static_cast<int64_t*>(tab.ws), lanes, mode == 1 ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -98,6 +98,10 @@ SIGNATURES = [
                                            _vp, C.c_int32, _vp]),
     ("sda_packed_reconstruct_dev", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.c_uint64,
                                          C.c_uint64, _vp, _vp, C.c_int32, _vp]),
+    ("sda_packed_generate32_dev", _st, [_vp, C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, C.c_uint64, _vp,
+                                        _vp, C.c_int32, _vp]),
+    ("sda_packed_reconstruct32_dev", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.c_uint64,
+                                           C.c_uint64, _vp, _vp, C.c_int32, _vp]),
     ("sda_additive_generate_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp]),
     ("sda_chacha_mask_combine_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
     ("sda_synth_fill_dev", _st, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, _vp]),
@@ -467,6 +471,20 @@ class Engine:
         idx = _arr(indices, np.uint64)
         _check(self.lib.sda_packed_reconstruct_dev(self.h, C.byref(s), dimension, _ptr(idx, _u64p), idx.size,
                                                    n_vectors, shares_ptr, out_ptr, mode, stream))
+
+    # int32 share rows: out / shares are device int32 [n_vectors][n][B]; the values are those of the i64 twins
+    def packed_generate32_dev(self, scheme, secrets_ptr, dimension, n_vectors, draws_ptr, out_ptr, mode,
+                              stream=None):
+        s = scheme.c()
+        _check(self.lib.sda_packed_generate32_dev(self.h, C.byref(s), secrets_ptr, dimension, n_vectors, draws_ptr,
+                                                  out_ptr, mode, stream))
+
+    def packed_reconstruct32_dev(self, scheme, dimension, indices, n_vectors, shares_ptr, out_ptr,
+                                 mode=REVEAL_EXACT, stream=None):
+        s = scheme.c()
+        idx = _arr(indices, np.uint64)
+        _check(self.lib.sda_packed_reconstruct32_dev(self.h, C.byref(s), dimension, _ptr(idx, _u64p), idx.size,
+                                                     n_vectors, shares_ptr, out_ptr, mode, stream))
 
     def additive_generate_dev(self, modulus, share_count, secrets_ptr, dimension, draws_ptr, out_ptr, stream=None):
         _check(self.lib.sda_additive_generate_dev(self.h, modulus, share_count, secrets_ptr, dimension, draws_ptr,
