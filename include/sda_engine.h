@@ -225,6 +225,25 @@ sda_status sda_host_stream_stats(const sda_engine* h, uint64_t* tiles_i32, uint6
  * bytes per device; summed over a multi-device handle's devices. */
 sda_status sda_packed_fixup_count(sda_engine* h, uint64_t* batches);
 
+/* Diagnostic (read-only): how the handle's most recent ChaCha launch ran -- a mask combine (sda_mask_combine,
+ * sda_chacha_mask_combine_dev, the recipient pipeline's mask) or a participant's mask (sda_secret_mask,
+ * sda_participant_share_dev).  A call of dimension 0 launches nothing and leaves the record.
+ *   path    0  no ChaCha launch yet
+ *           1  fast path, direct: one chunk, the kernel stores the results
+ *           2  fast path, chunked: grid_y chunks of seeds merged with atomics
+ *           3  fast path, stream-K over grid_y workgroups
+ *           4  single-stream mask add (sda_participant_share_dev's masked secrets)
+ *           5  exact stream path
+ *           6  fast path whose rejection log overflowed, rerun on the stream path
+ *   grid_y  the number of chunks (1 for paths 1 and 4), or the stream-K grid size; 0 for path 5; for path 6
+ *           that of the fast attempt
+ *   fixups  fix-up kernel launches, one per stream with a rejected draw below the dimension (a pipeline's
+ *           late resolve included; after a participant's redo, those of the redone mask)
+ * Host-side records: nothing is waited for or copied.  On a multi-device handle whose last mask combine split
+ * its seeds over the devices, path and grid_y are the first device's and fixups is summed over the devices.
+ * No pointer may be NULL. */
+sda_status sda_chacha_last_launch(sda_engine* h, uint32_t* path, uint64_t* grid_y, uint64_t* fixups);
+
 /* Multi-GPU finalize: `sums` are the int64 sums (RCCL-reduced; |sum| <= 2^63 - 1, signed allowed)
  * of per-GPU combine results; out = their canonical residue in [0, m).  Exact w.r.t. the reference
  * when all combined inputs were non-negative. */

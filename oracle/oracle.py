@@ -60,6 +60,8 @@ def lib():
         L.or_chacha_next_u64.argtypes = [C.POINTER(ChaChaRng)]
         L.or_chacha_gen_range.restype = C.c_int64
         L.or_chacha_gen_range.argtypes = [C.POINTER(ChaChaRng), C.c_int64, C.c_int64]
+        L.or_chacha_first_reject.restype = C.c_size_t
+        L.or_chacha_first_reject.argtypes = [C.c_int64, _u32p, C.c_size_t, C.c_size_t]
         L.or_chacha_mask.argtypes = [C.c_int64, _u32p, C.c_size_t, _i64p, C.c_size_t, _i64p]
         L.or_chacha_mask_combine.argtypes = [C.c_int64, C.c_size_t, _i64p, C.c_size_t, C.c_size_t, _i64p]
         L.or_unmask.argtypes = [C.c_int64, _i64p, _i64p, C.c_size_t, _i64p]
@@ -181,6 +183,12 @@ class Rng:
 
     def gen_range(self, low: int, high: int) -> int:
         return lib().or_chacha_gen_range(C.byref(self._st), low, high)
+
+
+def chacha_first_reject(m: int, seed_words, n_pairs: int) -> int:
+    """The first of the stream's first n_pairs u64 draws that gen_range(0, m) rejects; n_pairs if none."""
+    sw, swp = _u32(seed_words)
+    return lib().or_chacha_first_reject(m, swp, sw.size, n_pairs)
 
 
 def chacha_mask(m: int, seed_words, secrets) -> np.ndarray:

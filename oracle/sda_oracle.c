@@ -372,6 +372,16 @@ int64_t or_chacha_gen_range(or_chacha_rng* r, int64_t low, int64_t high) {
     }
 }
 
+size_t or_chacha_first_reject(int64_t m, const uint32_t* seed, size_t n_words, size_t n_pairs) {
+    /* the first of the stream's first n_pairs next_u64 values that gen_range(0, m) rejects */
+    or_chacha_rng r;
+    or_chacha_rng_from_seed(&r, seed, n_words);
+    uint64_t zone = UINT64_MAX - UINT64_MAX % (uint64_t)m;
+    for (size_t i = 0; i < n_pairs; ++i)
+        if (or_chacha_next_u64(&r) >= zone) return i;
+    return n_pairs;
+}
+
 /* ------------------------------------------------------------------------ */
 /* masking -- client/src/crypto/masking/{chacha,full}.rs, receive.rs        */
 /* ------------------------------------------------------------------------ */

@@ -90,6 +90,9 @@ void or_chacha_rng_from_seed(or_chacha_rng* r, const uint32_t* seed, size_t n_wo
 uint32_t or_chacha_next_u32(or_chacha_rng* r);
 uint64_t or_chacha_next_u64(or_chacha_rng* r);
 int64_t or_chacha_gen_range(or_chacha_rng* r, int64_t low, int64_t high);
+/* index of the first of the stream's first n_pairs next_u64 values that gen_range(0, m) rejects
+ * (v >= u64::MAX - u64::MAX % m), or n_pairs when it rejects none of them */
+size_t or_chacha_first_reject(int64_t m, const uint32_t* seed, size_t n_words, size_t n_pairs);
 
 /* ---- masking: client/src/crypto/masking/{chacha,full}.rs ---- */
 /* chacha.rs:25-53 with the OsRng seed replaced by `seed` */

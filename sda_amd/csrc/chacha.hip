@@ -640,7 +640,8 @@ static int resident_wgs(int which, const void* kernel) {
 // secrets != nullptr (one seed): out = (secrets + draw) % m, the masked secrets (chacha_mask_add_kernel).
 static hipError_t chacha_fast_enqueue(int64_t modulus, uint64_t D, const uint32_t* seeds_dev, uint32_t w,
                                       uint64_t n_seeds, int64_t* out, void* work, hipStream_t s,
-                                      unsigned long long* count_host, const int64_t* secrets = nullptr) {
+                                      unsigned long long* count_host, const int64_t* secrets = nullptr,
+                                      ChachaLaunchInfo* info = nullptr) {
     const Mod64 M = make_mod64(modulus);
     const uint64_t zone = UINT64_MAX - UINT64_MAX % (uint64_t)modulus;
     char* base = static_cast<char*>(work);
@@ -684,6 +685,11 @@ static hipError_t chacha_fast_enqueue(int64_t modulus, uint64_t D, const uint32_
     const uint64_t per = n_seeds ? (n_seeds + chunks - 1) / chunks : 0;
     const bool direct = chunks == 1;             // results stored straight into `out`
     unsigned long long* dst = direct ? reinterpret_cast<unsigned long long*>(out) : acc;
+    if (info) {                                  // the plan as decided above (sda_chacha_last_launch)
+        info->path = sk ? kChachaStreamK : secrets ? kChachaMaskAdd : direct ? kChachaDirect : kChachaChunked;
+        info->grid_y = sk ? G : chunks;
+        info->fixups = 0;
+    }
     if ((e = hipMemsetAsync(count, 0, 16, s)) != hipSuccess) return e;
     if (!direct && (e = hipMemsetAsync(acc, 0, D * 8, s)) != hipSuccess) return e;
     RejectLog log{count, seed_of, pair_of, kRejectCap};
@@ -796,31 +802,35 @@ static hipError_t chacha_fast_resolve(int64_t modulus, uint64_t D, const uint32_
 
 hipError_t launch_chacha_mask_combine(int64_t modulus, uint64_t dimension, const uint32_t* seeds, uint32_t w,
                                       uint64_t n_seeds, int64_t* out, void* work, hipStream_t s, bool* overflow,
-                                      int* fixups_out) {
+                                      int* fixups_out, ChachaLaunchInfo* info) {
     *overflow = false;
     if (fixups_out) *fixups_out = 0;
     if (dimension == 0) return hipSuccess;
     unsigned long long n_rej = 0;      // pageable: the copy completes before the sync returns
-    hipError_t e = chacha_fast_enqueue(modulus, dimension, seeds, w, n_seeds, out, work, s, &n_rej);
+    hipError_t e = chacha_fast_enqueue(modulus, dimension, seeds, w, n_seeds, out, work, s, &n_rej, nullptr, info);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
-    return chacha_fast_resolve(modulus, dimension, seeds, w, n_seeds, out, work, s, n_rej, overflow, fixups_out);
+    int fixups = 0;
+    e = chacha_fast_resolve(modulus, dimension, seeds, w, n_seeds, out, work, s, n_rej, overflow, &fixups);
+    if (fixups_out) *fixups_out = fixups;
+    if (info) info->fixups = (uint64_t)fixups;
+    return e;
 }
 
 hipError_t launch_chacha_mask_combine_async(int64_t modulus, uint64_t dimension, const uint32_t* seeds, uint32_t w,
                                             uint64_t n_seeds, int64_t* out, void* work, hipStream_t s,
-                                            unsigned long long* count_host) {
+                                            unsigned long long* count_host, ChachaLaunchInfo* info) {
     *count_host = 0;
     if (dimension == 0) return hipSuccess;
-    return chacha_fast_enqueue(modulus, dimension, seeds, w, n_seeds, out, work, s, count_host);
+    return chacha_fast_enqueue(modulus, dimension, seeds, w, n_seeds, out, work, s, count_host, nullptr, info);
 }
 
 hipError_t launch_chacha_mask_add_async(int64_t modulus, uint64_t dimension, const uint32_t* seed, uint32_t w,
                                         const int64_t* secrets, int64_t* masked, void* work, hipStream_t s,
-                                        unsigned long long* count_host) {
+                                        unsigned long long* count_host, ChachaLaunchInfo* info) {
     *count_host = 0;
     if (dimension == 0) return hipSuccess;
-    return chacha_fast_enqueue(modulus, dimension, seed, w, 1, masked, work, s, count_host, secrets);
+    return chacha_fast_enqueue(modulus, dimension, seed, w, 1, masked, work, s, count_host, secrets, info);
 }
 
 hipError_t resolve_chacha_mask_combine(int64_t modulus, uint64_t dimension, const uint32_t* seeds, uint32_t w,

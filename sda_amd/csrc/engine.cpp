@@ -53,6 +53,10 @@ struct sda_engine {
     hipEvent_t order_ev = nullptr;
     bool order_ok = true;         // order_ev was recorded when the last call ended (else: host sync)
     unsigned long long* rej_host = nullptr;   // pinned: the ChaCha rejection count of a pipeline's mask
+    // sda_chacha_last_launch: how the last mask combine or participant mask on this handle ran; chacha_split:
+    // that call split its seeds over the handle's devices (chacha_combine_multi), each recording its own part
+    sda::ChachaLaunchInfo chacha_last;
+    bool chacha_split = false;
     // streaming host path (host rows -> HBM in row tiles, host_path section): pinned staging and device
     // tiles, double buffered, and a copy stream so a tile's upload overlaps the previous tile's combine
     hipStream_t copy_stream = nullptr;
@@ -252,9 +256,16 @@ size_t rup(size_t b) { return (b + 255) & ~(size_t)255; }
 // chacha.rs:57-76: combine of n seed streams ([n][w] u32 words on the device) into out (device, D
 // values).  The fast counter-mode kernel where its rejection log suffices; otherwise (moduli above
 // 2^62, high rejection rates, or a log overflow) the exact stream path.
+// Every ChaCha launch leaves how it ran in the handle (sda_chacha_last_launch).
+void record_chacha(sda_engine* h, const sda::ChachaLaunchInfo& info) {
+    h->chacha_last = info;
+    h->chacha_split = false;
+}
+
 sda_status chacha_combine(sda_engine* h, int64_t m, uint64_t D, const uint32_t* seeds, uint32_t w, uint64_t n,
                           int64_t* out, hipStream_t st) {
     if (D == 0) return SDA_OK;
+    sda::ChachaLaunchInfo info;
     // SDA_CHACHA_PATH=stream: test hook forcing the stream path (both paths are exact; the tests
     // compare them at sizes the oracle cannot finish)
     const char* force = getenv("SDA_CHACHA_PATH");
@@ -262,11 +273,16 @@ sda_status chacha_combine(sda_engine* h, int64_t m, uint64_t D, const uint32_t* 
         if (sda_status e = ensure(&h->work, &h->work_bytes, sda::chacha_work_bytes(D, n))) return e;
         bool overflow = false;
         int fixups = 0;
-        HIP_TRY(sda::launch_chacha_mask_combine(m, D, seeds, w, n, out, h->work, st, &overflow, &fixups));
+        HIP_TRY(sda::launch_chacha_mask_combine(m, D, seeds, w, n, out, h->work, st, &overflow, &fixups, &info));
+        record_chacha(h, info);
         if (!overflow) return SDA_OK;
+        info.path = sda::kChachaOverflow;        // grid_y and fixups stay those of the fast attempt
+    } else {
+        info.path = sda::kChachaStream;
     }
     if (sda_status e = ensure(&h->work, &h->work_bytes, sda::chacha_stream_work_bytes(D, n, m))) return e;
     HIP_TRY(sda::launch_chacha_streams_combine(m, D, seeds, w, n, out, h->work, st));
+    record_chacha(h, info);
     return SDA_OK;
 }
 
@@ -291,7 +307,9 @@ sda_status chacha_combine_begin(sda_engine* h, int64_t m, uint64_t D, const uint
     if (sda::chacha_needs_stream_path(m) || (force && strcmp(force, "stream") == 0) || n == 0)
         return chacha_combine(h, m, D, seeds, w, n, out, st);
     if (sda_status e = ensure(&h->work, &h->work_bytes, sda::chacha_work_bytes(D, n))) return e;
-    HIP_TRY(sda::launch_chacha_mask_combine_async(m, D, seeds, w, n, out, h->work, st, h->rej_host));
+    sda::ChachaLaunchInfo info;
+    HIP_TRY(sda::launch_chacha_mask_combine_async(m, D, seeds, w, n, out, h->work, st, h->rej_host, &info));
+    record_chacha(h, info);
     *pc = PendingChacha{true, m, D, n, seeds, w, out};
     return SDA_OK;
 }
@@ -300,11 +318,14 @@ sda_status chacha_combine_end(sda_engine* h, const PendingChacha& pc, hipStream_
     if (!pc.pending || *h->rej_host == 0) return SDA_OK;
     *changed = true;
     bool overflow = false;
+    int fixups = 0;
     HIP_TRY(sda::resolve_chacha_mask_combine(pc.m, pc.D, pc.seeds, pc.w, pc.n, pc.out, h->work, st, *h->rej_host,
-                                             &overflow, nullptr));
+                                             &overflow, &fixups));
+    h->chacha_last.fixups = (uint64_t)fixups;    // the late resolve of the plan chacha_combine_begin recorded
     if (!overflow) return SDA_OK;
     if (sda_status e = ensure(&h->work, &h->work_bytes, sda::chacha_stream_work_bytes(pc.D, pc.n, pc.m))) return e;
     HIP_TRY(sda::launch_chacha_streams_combine(pc.m, pc.D, pc.seeds, pc.w, pc.n, pc.out, h->work, st));
+    h->chacha_last.path = sda::kChachaOverflow;
     return SDA_OK;
 }
 
@@ -826,6 +847,19 @@ sda_status sda_packed_fixup_count(sda_engine* h, uint64_t* batches) {
         if (sda_status st = add(e)) return st;
     if (!h->sub.empty()) HIP_TRY(hipSetDevice(h->device));
     *batches = total;
+    return ok();
+}
+
+sda_status sda_chacha_last_launch(sda_engine* h, uint32_t* path, uint64_t* grid_y, uint64_t* fixups) {
+    SDA_ENTRY;
+    if (!h || !path || !grid_y || !fixups) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    // host-side records, final when the call that made them returned: nothing to wait for
+    *path = h->chacha_last.path;
+    *grid_y = h->chacha_last.grid_y;
+    uint64_t total = h->chacha_last.fixups;
+    if (h->chacha_split)
+        for (size_t g = 1; g < h->sub.size(); ++g) total += h->sub[g]->chacha_last.fixups;   // sub[0] is the handle
+    *fixups = total;
     return ok();
 }
 
@@ -2010,8 +2044,10 @@ sda_status sda_participant_share_dev(sda_engine* h, const sda_masking_scheme* ms
             const char* force = getenv("SDA_CHACHA_PATH");
             if (!sda::chacha_needs_stream_path(ms->modulus) && !(force && strcmp(force, "stream") == 0)) {
                 if (sda_status e = ensure(&h->work, &h->work_bytes, sda::chacha_work_bytes(D, 0))) return e;
+                sda::ChachaLaunchInfo info;
                 HIP_TRY(sda::launch_chacha_mask_add_async(ms->modulus, D, dseed, w, secrets, dm, h->work, st,
-                                                          h->rej_host));
+                                                          h->rej_host, &info));
+                record_chacha(h, info);
                 mask_pending = true;
             } else {
                 if (sda_status e = chacha_combine(h, ms->modulus, D, dseed, w, 1, dmask, st)) return e;
@@ -2059,6 +2095,11 @@ sda_status sda_participant_share_dev(sda_engine* h, const sda_masking_scheme* ms
         HIP_TRY(hipStreamSynchronize(st));
         if (*h->rej_host) {
             if (sda_status e = chacha_combine(h, ms->modulus, D, cseed, cw, 1, cmask, st)) return e;
+            // the record stays the mask add's, with the redo's fix-up count (or its log overflow)
+            if (h->chacha_last.path != sda::kChachaOverflow) {
+                h->chacha_last.path = sda::kChachaMaskAdd;
+                h->chacha_last.grid_y = 1;
+            }
             HIP_TRY(sda::launch_addsub_trem(secrets, cmask, +1, D, const_cast<int64_t*>(masked), ms->modulus, st));
             if (sda_status e = share_and_encode()) return e;
         }
@@ -2348,6 +2389,7 @@ sda_status chacha_combine_multi(sda_engine* h, int64_t m, uint64_t D, const std:
     if (st) return st;
     HIP_TRY(hipSetDevice(h->device));
     if (!split) return SDA_OK;
+    h->chacha_split = true;                      // every device recorded its part (sda_chacha_last_launch)
     if (sda_status e = ensure_comms(h)) return e;
     Rccl& r = rccl();
     NCCL_TRY(r.group_start());

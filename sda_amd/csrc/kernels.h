@@ -196,26 +196,44 @@ hipError_t launch_varint_encode(const int64_t* vals, uint64_t rows, uint64_t len
 //  * stream path: the draws of a tile of streams expanded exactly (any rejection rate) into rows,
 //    then the exact sequential combine recurrence (wrapping i64 add for m > 2^62, as the reference).
 //    `work` must hold chacha_stream_work_bytes(D, n_seeds, m).  Host-synchronous per tile.
+// How a ChaCha launch ran (sda_chacha_last_launch reports the handle's last one).  The fast path's plan is
+// recorded where it is decided (chacha_fast_enqueue); the engine adds the stream path and the fix-up count.
+enum ChachaPath : uint32_t {
+    kChachaNone = 0,          // no ChaCha launch yet
+    kChachaDirect = 1,        // fast path, one chunk: chacha_combine_kernel<*, DIRECT> stores the results
+    kChachaChunked = 2,       // fast path, grid_y chunks of seeds merged with atomics
+    kChachaStreamK = 3,       // fast path, chacha_combine_sk_kernel over grid_y workgroups
+    kChachaMaskAdd = 4,       // one stream's masked secrets (chacha_mask_add_kernel)
+    kChachaStream = 5,        // exact stream path
+    kChachaOverflow = 6,      // fast path whose rejection log overflowed: rerun on the stream path
+};
+struct ChachaLaunchInfo {
+    uint32_t path = kChachaNone;
+    uint64_t grid_y = 0;      // chunks (direct, mask add: 1) or the stream-K grid size G; 0 on the stream path
+    uint64_t fixups = 0;      // chacha_fix_kernel launches: one per stream with a rejection below D
+};
 size_t chacha_work_bytes(uint64_t dimension, uint64_t n_seeds);
 bool chacha_needs_stream_path(int64_t modulus);
 size_t chacha_stream_work_bytes(uint64_t dimension, uint64_t n_seeds, int64_t modulus);
 hipError_t launch_chacha_mask_combine(int64_t modulus, uint64_t dimension, const uint32_t* seeds,
                                       uint32_t w, uint64_t n_seeds, int64_t* out, void* work,
-                                      hipStream_t s, bool* overflow, int* fixups_out);
+                                      hipStream_t s, bool* overflow, int* fixups_out,
+                                      ChachaLaunchInfo* info = nullptr);
 // The same fast path in two halves, for pipelines that keep queueing work behind it: _async enqueues
 // the combine (canonical draws' sums in out, before any fix-up) and copies its rejection count to
 // count_host (PINNED host memory, valid once the stream has drained); resolve_ then applies the
 // fix-ups for that count (host-synchronous, rare) or sets *overflow (rerun on the stream path).  The
-// caller redoes whatever it queued on `out` when the count was nonzero.
+// caller redoes whatever it queued on `out` when the count was nonzero.  *info (optional, every launcher
+// below): the plan of the launch, its fixups 0 until a resolve_ counts them (fixups_out).
 hipError_t launch_chacha_mask_combine_async(int64_t modulus, uint64_t dimension, const uint32_t* seeds, uint32_t w,
                                             uint64_t n_seeds, int64_t* out, void* work, hipStream_t s,
-                                            unsigned long long* count_host);
+                                            unsigned long long* count_host, ChachaLaunchInfo* info = nullptr);
 // One stream's masked secrets in one pass (chacha.rs:36-45): masked = (secrets + draw) % m, the rejection
 // count to count_host (pinned).  A nonzero count means `masked` used rejected draws: the caller redoes
 // the mask exactly (launch_chacha_mask_combine, then the add).
 hipError_t launch_chacha_mask_add_async(int64_t modulus, uint64_t dimension, const uint32_t* seed, uint32_t w,
                                         const int64_t* secrets, int64_t* masked, void* work, hipStream_t s,
-                                        unsigned long long* count_host);
+                                        unsigned long long* count_host, ChachaLaunchInfo* info = nullptr);
 hipError_t resolve_chacha_mask_combine(int64_t modulus, uint64_t dimension, const uint32_t* seeds, uint32_t w,
                                        uint64_t n_seeds, int64_t* out, void* work, hipStream_t s,
                                        unsigned long long n_rej, bool* overflow, int* fixups_out);

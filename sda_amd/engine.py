@@ -43,6 +43,15 @@ ERR_OUT_OF_MEMORY = 68
 REVEAL_EXACT = 0
 REVEAL_CANONICAL = 1
 
+# sda_chacha_last_launch's path codes
+CHACHA_NONE = 0
+CHACHA_DIRECT = 1
+CHACHA_CHUNKED = 2
+CHACHA_STREAM_K = 3
+CHACHA_MASK_ADD = 4
+CHACHA_STREAM = 5
+CHACHA_OVERFLOW = 6
+
 _i64p = C.POINTER(C.c_int64)
 _u64p = C.POINTER(C.c_uint64)
 _u32p = C.POINTER(C.c_uint32)
@@ -86,6 +95,7 @@ SIGNATURES = [
     ("sda_narrow32_dev", _st, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
     ("sda_host_stream_stats", _st, [_vp, _u64p, _u64p, _u64p]),
     ("sda_packed_fixup_count", _st, [_vp, _u64p]),
+    ("sda_chacha_last_launch", _st, [_vp, _u32p, _u64p, _u64p]),
     ("sda_combine_split_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     ("sda_combine_split_prefix_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp,
                                            _vp]),
@@ -432,6 +442,13 @@ class Engine:
         v = C.c_uint64()
         _check(self.lib.sda_packed_fixup_count(self.h, C.byref(v)))
         return int(v.value)
+
+    def chacha_last_launch(self):
+        """(path, grid_y, fixups) of the handle's last ChaCha launch: path is one of the CHACHA_* codes, grid_y
+        the chunks or the stream-K grid size, fixups the fix-up kernel launches (sda_chacha_last_launch)."""
+        path, grid_y, fixups = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _check(self.lib.sda_chacha_last_launch(self.h, C.byref(path), C.byref(grid_y), C.byref(fixups)))
+        return int(path.value), int(grid_y.value), int(fixups.value)
 
     def combine_finalize_dev(self, modulus, sums_ptr, dim, out_ptr, stream=None):
         _check(self.lib.sda_combine_finalize_dev(self.h, modulus, sums_ptr, dim, out_ptr, stream))

@@ -255,10 +255,13 @@ def test_packed_errors(engine):
 
 
 # ------------------------------------------------------------------ masking (north-star kernel 3)
-# (1 << 62) + 1: ~25 % of draws rejected; 0x5555555555555556: ~33 % rejected and, above 2^62, the
-# reference's `result[i] += m` wraps i64 (chacha.rs:70), so the combine is signed and order
-# dependent; I64_MAX: wrapping with almost no rejections
-@pytest.mark.parametrize("m", [433, 2147482801, (1 << 40) + 7, (1 << 62) + 1, 0x5555555555555556, I64_MAX])
+# Both sides of every path boundary.  Fast path, lazy sums (m <= 2^32): 1, 2, 433, 2147482801, 2^32; fast path,
+# Barrett: 2^32 + 1, 2^40 - 87, 2^61 - 1, 2^62 - 57.  Stream path: (1 << 40) + 7 (2^40 of the 2^64 values are
+# rejected, above the fast path's 2^36); (1 << 62) + 1: ~25 % of draws rejected; 0x5555555555555556: ~33 %
+# rejected and, above 2^62, the reference's `result[i] += m` wraps i64 (chacha.rs:70), so the combine is signed
+# and order dependent; I64_MAX: wrapping with almost no rejections
+@pytest.mark.parametrize("m", [433, 2147482801, (1 << 40) + 7, (1 << 62) + 1, 0x5555555555555556, I64_MAX,
+                               (1 << 40) - 87, (1 << 61) - 1, (1 << 62) - 57, 1 << 32, (1 << 32) + 1, 1, 2])
 @pytest.mark.parametrize("words", [0, 1, 4, 8, 10])
 def test_chacha_mask_and_combine(engine, oracle, m, words):
     rng = np.random.default_rng(m % 991 + words)

@@ -74,20 +74,25 @@ def test_stream_destroyed_between_calls(engine, oracle):
         assert_same(r.cpu().numpy(), exp)
 
 
-@pytest.mark.parametrize("m", [2147482801, (1 << 40) + 7])
+@pytest.mark.parametrize("m", [2147482801, (1 << 40) - 87])
 def test_chacha_stream_path_equals_fast_path(engine, m, monkeypatch):
     """Both exact ChaCha implementations (counter mode + rejection fix-up, and per-stream expansion +
-    the sequential combine) agree on a size the oracle cannot finish quickly (96 seeds x 1M)."""
+    the sequential combine) agree on a size the oracle cannot finish quickly (96 seeds x 1M), for a lazy
+    and a Barrett fast-path modulus (2^64 mod (2^40 - 87) = 87 * 2^24 rejected values, below the stream
+    path's 2^36 threshold).  sda_chacha_last_launch tells that the two calls really took the two paths."""
     N, D = 96, 1_000_003
+    monkeypatch.delenv("SDA_CHACHA_PATH", raising=False)
     seeds = torch.randint(0, 2**31 - 1, (N, 4), dtype=torch.int32, device="cuda",
                           generator=torch.Generator(device="cuda").manual_seed(m % 1000))
     fast = torch.empty(D, dtype=torch.int64, device="cuda")
     slow = torch.empty(D, dtype=torch.int64, device="cuda")
     engine.chacha_mask_combine_dev(m, D, seeds.data_ptr(), 4, N, fast.data_ptr())
     torch.cuda.synchronize()
+    assert engine.chacha_last_launch()[0] in (E.CHACHA_DIRECT, E.CHACHA_CHUNKED, E.CHACHA_STREAM_K)
     monkeypatch.setenv("SDA_CHACHA_PATH", "stream")
     engine.chacha_mask_combine_dev(m, D, seeds.data_ptr(), 4, N, slow.data_ptr())
     torch.cuda.synchronize()
+    assert engine.chacha_last_launch()[0] == E.CHACHA_STREAM
     assert torch.equal(fast, slow)
 
 

@@ -242,3 +242,22 @@ def test_chacha_reject_seeds_reject_where_found(oracle):
         for s, pair in hits:
             r = oracle.Rng([s, 0x5DA, 7, 11])
             assert [i for i in range(pair + 1) if r.next_u64() >= zone] == [pair]
+
+
+def test_chacha_first_reject_matches_the_stream_walk(oracle):
+    """oracle.chacha_first_reject (the bulk walk tests/test_gpu_chacha_matrix.py counts rejecting streams
+    with) against next_u64 call by call: the listed pair for the golden seeds, n_pairs when the prefix ends
+    before it or the stream (m = 2^62 + 1 rejects ~25 %: checked against the walk) has none."""
+    g = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "chacha_rejects.json")))
+    for m, hits in g["moduli"].items():
+        for s, pair in hits:
+            seed = [s, 0x5DA, 7, 11]
+            assert oracle.chacha_first_reject(int(m), seed, 65536) == pair
+            assert oracle.chacha_first_reject(int(m), seed, pair + 1) == pair
+            assert oracle.chacha_first_reject(int(m), seed, pair) == pair       # none among the first `pair`
+    m = (1 << 62) + 1
+    zone = (2**64 - 1) - (2**64 - 1) % m
+    for s in range(8):
+        r = oracle.Rng([s])
+        walk = [r.next_u64() >= zone for _ in range(40)]
+        assert oracle.chacha_first_reject(m, [s], 40) == (walk.index(True) if True in walk else 40)
