@@ -115,6 +115,8 @@ extern "C" {
     pub fn sda_packed_fixup_count(h: *mut SdaEngine, batches: *mut u64) -> SdaStatus;
     pub fn sda_chacha_last_launch(h: *mut SdaEngine, path: *mut u32, grid_y: *mut u64, fixups: *mut u64)
                                   -> SdaStatus;
+    pub fn sda_codec_last_launch(h: *mut SdaEngine, path: *mut u32, width: *mut u32, fell_back: *mut u32,
+                                 passes: *mut u64) -> SdaStatus;
     pub fn sda_combine_finalize_dev(h: *mut SdaEngine, modulus: i64, sums: *const i64, dim: u64, out: *mut i64,
                                     stream: *mut c_void) -> SdaStatus;
     pub fn sda_combine_split_dev(h: *mut SdaEngine, modulus: i64, shares: *const i64, n: u64, dim: u64,

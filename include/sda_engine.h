@@ -244,6 +244,30 @@ sda_status sda_packed_fixup_count(sda_engine* h, uint64_t* batches);
  * No pointer may be NULL. */
 sda_status sda_chacha_last_launch(sda_engine* h, uint32_t* path, uint64_t* grid_y, uint64_t* fixups);
 
+/* Diagnostic (read-only): how the handle's most recent sda_clerk_decode_combine_dev produced its result.  The
+ * record is NONE from the call's entry until it returns SDA_OK, so a failed call leaves NONE; the host streaming
+ * entry point (sda_clerk_decode_combine) keeps no record and leaves NONE as well, and so does a job whose
+ * payloads decode to no element after its count pass (nothing is launched).
+ *   path       0  NONE
+ *              1  SLOTS          one decode into int32 slots per 16 KiB region + the combine over the slots
+ *              2  SLOTS_GROUPED  the same, `passes` groups of blobs through one reused slot buffer (SDA_CODEC_GROUP)
+ *              3  FUSED          the column-tile decode -> combine (SDA_CODEC_PATH=fused)
+ *              4  FUSED_MULTI    its multi-round variant (the job has an element of >= 6 bytes)
+ *              5  MATRIX32       count pass + int32 matrix + combine
+ *              6  MATRIX64       count pass + i64 matrix + combine
+ *   width      columns per lane of the slot combine (1, 2 or 4: SDA_SLOT_CPL) for paths 1 and 2; blobs the fused
+ *              kernel prefetches ahead (2, 4 or 8: SDA_DC_DEPTH; always 2 for path 4) for paths 3 and 4; else 0
+ *   fell_back  bits: 1  the slot attempt raised its wide flag (an element longer than 5 bytes or outside int32, or
+ *                       more than 4096 elements in a region) and was abandoned for the count pass
+ *                    2  fused was asked for but a blob is irregular (a run of >= 11 continuation bytes)
+ *                    4  the int32 matrix decode met a value outside int32 and was abandoned for the i64 one
+ *                    8  the sequential decoder ran (irregular blobs)
+ *   passes     path 2: the blob groups; else the grid slices of at most 65,535 blobs of the decode pass that
+ *              produced the result (paths 3 and 4: of the tile plan, the fused kernel's grid being column tiles)
+ * A host-side record: nothing is waited for or copied.  No pointer may be NULL. */
+sda_status sda_codec_last_launch(sda_engine* h, uint32_t* path, uint32_t* width, uint32_t* fell_back,
+                                 uint64_t* passes);
+
 /* Multi-GPU finalize: `sums` are the int64 sums (RCCL-reduced; |sum| <= 2^63 - 1, signed allowed)
  * of per-GPU combine results; out = their canonical residue in [0, m).  Exact w.r.t. the reference
  * when all combined inputs were non-negative. */

@@ -1154,18 +1154,21 @@ hipError_t launch_varint_count(const uint8_t* bytes, const uint64_t* blob_off_ho
 
 hipError_t launch_varint_decode(const uint8_t* bytes, uint64_t n_blobs, const VarintPlan& plan, void* work,
                                 int64_t* out, uint64_t out_stride, uint64_t len, bool irregular_any,
-                                hipStream_t s) {
+                                hipStream_t s, CodecLaunchInfo* info) {
     const size_t R = plan.regions;
     DecodeWork w = carve(work, R, n_blobs);
     hipError_t e;
+    if (info) info->passes = 0;
     for (uint64_t y0 = 0; R && y0 < n_blobs; y0 += 65535) {
         const unsigned ny = (unsigned)(n_blobs - y0 < 65535 ? n_blobs - y0 : 65535);
         hipLaunchKernelGGL(dec_kernel<int64_t>(), dim3((unsigned)plan.max_regions, ny), dim3(kThreads), 0, s,
                            bytes, w.blob_region, w.blob_off, (uint32_t)y0, w.region_base, w.irregular, out, out_stride,
                            w.wide, (uint32_t*)nullptr, (const uint32_t*)nullptr);
         if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (info) ++info->passes;
     }
     if (irregular_any) {
+        if (info) info->fell_back |= kCodecSequential;
         hipLaunchKernelGGL(varint_sequential_kernel, dim3((unsigned)((n_blobs + 63) / 64)), dim3(64), 0, s, bytes,
                            w.blob_off, (uint32_t)n_blobs, w.irregular, w.blob_count, out, out_stride, len);
         if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -1219,17 +1222,20 @@ hipError_t launch_varint_decode_one_wait(const uint8_t* bytes, const uint64_t* b
 }
 
 hipError_t launch_varint_decode_narrow(const uint8_t* bytes, uint64_t n_blobs, const VarintPlan& plan, void* work,
-                                       int32_t* out, uint64_t out_stride, bool* wide_host, hipStream_t s) {
+                                       int32_t* out, uint64_t out_stride, bool* wide_host, hipStream_t s,
+                                       CodecLaunchInfo* info) {
     const size_t R = plan.regions;
     DecodeWork w = carve(work, R, n_blobs);
     hipError_t e;
     if ((e = hipMemsetAsync(w.wide, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
+    if (info) info->passes = 0;
     for (uint64_t y0 = 0; R && y0 < n_blobs; y0 += 65535) {
         const unsigned ny = (unsigned)(n_blobs - y0 < 65535 ? n_blobs - y0 : 65535);
         hipLaunchKernelGGL(dec_kernel<int32_t>(), dim3((unsigned)plan.max_regions, ny), dim3(kThreads), 0, s,
                            bytes, w.blob_region, w.blob_off, (uint32_t)y0, w.region_base, w.irregular, out, out_stride,
                            w.wide, (uint32_t*)nullptr, (const uint32_t*)nullptr);
         if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (info) ++info->passes;
     }
     uint32_t flag = 0;
     if ((e = hipMemcpyAsync(&flag, w.wide, sizeof(flag), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
@@ -1278,13 +1284,18 @@ size_t varint_slot_bytes(const VarintPlan& plan, uint64_t n_blobs, uint64_t dim)
 hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64_t* blob_off_host, uint64_t n_blobs,
                                               const VarintPlan& plan, void* work, void* slot_buf, int64_t* out,
                                               uint64_t out_cap, int64_t modulus, uint64_t* counts_host,
-                                              uint32_t* flags_host, hipStream_t s) {
+                                              uint32_t* flags_host, hipStream_t s, CodecLaunchInfo* info) {
     const size_t R = plan.regions;
     DecodeWork w = carve(work, R, n_blobs);
     const SlotGroups sg = slot_groups(plan, n_blobs);
+    if (info) {                                  // as decided here (sda_codec_last_launch)
+        info->path = sg.G ? kCodecSlotsGrouped : kCodecSlots;
+        info->passes = 0;
+    }
     int32_t* slots = static_cast<int32_t*>(slot_buf);
     uint64_t* tplan = reinterpret_cast<uint64_t*>(static_cast<char*>(slot_buf) + slot_area_bytes(sg.regions));
     const uint32_t cpl = slot_cpl(), tile = cpl * kThreads;
+    if (info) info->width = cpl;
     // the grid's bound: blob 0 decodes to at most one element per byte
     const uint64_t ntiles = (blob_off_host[1] - blob_off_host[0] + tile - 1) / tile;
     if (ntiles > 0x7FFFFFFFull || R * kSlotCap >= (1ull << 39)) return hipErrorInvalidValue;
@@ -1312,6 +1323,7 @@ hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64
         for (uint64_t g0 = 0; g0 < n_blobs; g0 += sg.G) {
             const uint64_t g1 = g0 + sg.G < n_blobs ? g0 + sg.G : n_blobs;
             const uint64_t ng = g1 - g0, R0 = plan.blob_region[g0];
+            if (info) ++info->passes;
             if (plan.blob_region[g1] > R0) {
                 hipLaunchKernelGGL((dec_kernel<int32_t, true>()), dim3((unsigned)plan.max_regions, (unsigned)ng),
                                    dim3(kThreads), 0, s, bytes, w.blob_region, w.blob_off, (uint32_t)g0,
@@ -1349,6 +1361,7 @@ hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64
                            0, s, bytes, w.blob_region, w.blob_off, (uint32_t)y0, (const uint64_t*)nullptr,
                            (const uint32_t*)nullptr, slots, 0, w.wide, w.region_count, (const uint32_t*)nullptr);
         if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (info) ++info->passes;
     }
     hipLaunchKernelGGL(varint_scan_kernel, dim3((unsigned)n_blobs), dim3(kThreads), 0, s, w.region_count,
                        w.blob_region, w.region_base, w.blob_count);
@@ -1376,15 +1389,17 @@ hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64
 
 hipError_t launch_varint_decode_combine(const uint8_t* bytes, uint64_t n_blobs, const VarintPlan& plan, void* work,
                                         uint64_t* tile_plan, uint64_t dim, int64_t* out, int64_t modulus,
-                                        bool multi, hipStream_t s) {
+                                        bool multi, hipStream_t s, CodecLaunchInfo* info) {
     if (dim == 0 || n_blobs == 0) return hipSuccess;
     const size_t R = plan.regions;
     DecodeWork w = carve(work, R, n_blobs);
     const uint64_t ntiles = varint_fused_tiles(dim);
     if (ntiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipError_t e;
+    if (info) info->passes = 0;
     for (uint64_t y0 = 0; y0 < n_blobs; y0 += 65535) {
         const unsigned ny = (unsigned)(n_blobs - y0 < 65535 ? n_blobs - y0 : 65535);
+        if (info) ++info->passes;
         hipLaunchKernelGGL(varint_tile_plan_kernel, dim3((unsigned)((plan.max_regions + kThreads - 1) / kThreads), ny),
                            dim3(kThreads), 0, s, w.blob_off, w.blob_region, w.region_base, w.sub_count, (uint32_t)y0,
                            n_blobs, ntiles, tile_plan);
@@ -1396,18 +1411,28 @@ hipError_t launch_varint_decode_combine(const uint8_t* bytes, uint64_t n_blobs, 
     const int depth = env ? atoi(env) : 4;
     const dim3 grid((unsigned)ntiles), block(kDcThreads);
     const uint64_t* tp = tile_plan;
-    if (multi)
+    uint32_t ran = 0;                            // the DEPTH of the instantiation launched
+    if (multi) {
+        ran = 2;
         hipLaunchKernelGGL((varint_decode_combine_kernel<2, true>), grid, block, 0, s, bytes, w.blob_off, n_blobs,
                            tp, ntiles, dim, out, M, small_m);
-    else if (depth == 2)
+    } else if (depth == 2) {
+        ran = 2;
         hipLaunchKernelGGL((varint_decode_combine_kernel<2, false>), grid, block, 0, s, bytes, w.blob_off, n_blobs,
                            tp, ntiles, dim, out, M, small_m);
-    else if (depth == 8)
+    } else if (depth == 8) {
+        ran = 8;
         hipLaunchKernelGGL((varint_decode_combine_kernel<8, false>), grid, block, 0, s, bytes, w.blob_off, n_blobs,
                            tp, ntiles, dim, out, M, small_m);
-    else
+    } else {
+        ran = 4;
         hipLaunchKernelGGL((varint_decode_combine_kernel<4, false>), grid, block, 0, s, bytes, w.blob_off, n_blobs,
                            tp, ntiles, dim, out, M, small_m);
+    }
+    if (info) {
+        info->path = multi ? kCodecFusedMulti : kCodecFused;
+        info->width = ran;
+    }
     return hipGetLastError();
 }
 

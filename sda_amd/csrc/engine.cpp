@@ -57,6 +57,8 @@ struct sda_engine {
     // that call split its seeds over the handle's devices (chacha_combine_multi), each recording its own part
     sda::ChachaLaunchInfo chacha_last;
     bool chacha_split = false;
+    // sda_codec_last_launch: how the last decode -> combine on this handle produced its result (decode_combine)
+    sda::CodecLaunchInfo codec_last;
     // streaming host path (host rows -> HBM in row tiles, host_path section): pinned staging and device
     // tiles, double buffered, and a copy stream so a tile's upload overlaps the previous tile's combine
     hipStream_t copy_stream = nullptr;
@@ -863,6 +865,18 @@ sda_status sda_chacha_last_launch(sda_engine* h, uint32_t* path, uint64_t* grid_
     return ok();
 }
 
+sda_status sda_codec_last_launch(sda_engine* h, uint32_t* path, uint32_t* width, uint32_t* fell_back,
+                                 uint64_t* passes) {
+    SDA_ENTRY;
+    if (!h || !path || !width || !fell_back || !passes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    // a host-side record, final when the call that made it returned: nothing to wait for
+    *path = h->codec_last.path;
+    *width = h->codec_last.width;
+    *fell_back = h->codec_last.fell_back;
+    *passes = h->codec_last.passes;
+    return ok();
+}
+
 sda_status sda_combine_finalize_dev(sda_engine* h, int64_t modulus, const int64_t* sums, uint64_t dim, int64_t* out,
                                     void* stream) {
     SDA_ENTRY;
@@ -1477,6 +1491,9 @@ sda_status codec_count(sda_engine* h, const uint8_t* bytes, const uint64_t* blob
 sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const uint64_t* blob_off, uint64_t n_blobs,
                           int64_t* out, uint64_t out_cap, uint64_t* out_len, hipStream_t st) {
     *out_len = 0;
+    // sda_codec_last_launch: NONE until this call returns SDA_OK; `info` collects each decision where it is taken
+    h->codec_last = sda::CodecLaunchInfo();
+    sda::CodecLaunchInfo info;
     if (n_blobs == 0) return ok();                                  // combiner.rs:17: empty input
     // SDA_CODEC_PATH=fused (A/B and test knob) runs the column-tile decode+combine, which reads the payload
     // once instead of writing and re-reading an int32 matrix but measured slower (VALU-bound: 3.4 ms per
@@ -1509,7 +1526,7 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
         uint32_t flags = 0;
         HIP_TRY(sda::launch_varint_decode_slots_combine(bytes, blob_off, n_blobs, plan, h->codec_work, h->codec_mat,
                                                         out, out_cap, m_ok ? (m < 0 ? -m : m) : 0, counts.data(),
-                                                        &flags, st));
+                                                        &flags, st, &info));
         if (!(flags & 1u)) {
             const uint64_t dim = counts[0];
             int64_t mm = 1;
@@ -1524,8 +1541,11 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
             }
             if (out_cap < dim) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
             *out_len = dim;
+            h->codec_last = info;
             return SDA_OK;
         }
+        info = sda::CodecLaunchInfo();                 // the slot attempt wrote nothing: the count pass takes over
+        info.fell_back = sda::kCodecSlotWide;
     }
     bool irregular = false, long_elems = false;
     if (sda_status e = codec_count(h, bytes, blob_off, n_blobs, &plan, counts.data(), &irregular, st, !force_matrix,
@@ -1544,12 +1564,15 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
     if (out_cap < dim) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
     *out_len = dim;
     if (dim == 0) return ok();
+    if (force_fused && irregular) info.fell_back |= sda::kCodecFusedIrregular;
     if (!irregular && force_fused) {
         // one pass over the payload: no [N][dim] matrix (the matrix buffer holds the tile plan)
         if (sda_status e = ensure(&h->codec_mat, &h->codec_mat_bytes, sda::varint_tile_plan_bytes(n_blobs, dim)))
             return e;
         HIP_TRY(sda::launch_varint_decode_combine(bytes, n_blobs, plan, h->codec_work,
-                                                  static_cast<uint64_t*>(h->codec_mat), dim, out, mm, long_elems, st));
+                                                  static_cast<uint64_t*>(h->codec_mat), dim, out, mm, long_elems, st,
+                                                  &info));
+        h->codec_last = info;
         return SDA_OK;
     }
     if (sda_status e = ensure(&h->codec_mat, &h->codec_mat_bytes, n_blobs * dim * 8)) return e;
@@ -1559,15 +1582,21 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
     if (narrow_ok && !irregular) {
         bool wide = false;
         int32_t* mat32 = static_cast<int32_t*>(h->codec_mat);
-        HIP_TRY(sda::launch_varint_decode_narrow(bytes, n_blobs, plan, h->codec_work, mat32, dim, &wide, st));
+        HIP_TRY(sda::launch_varint_decode_narrow(bytes, n_blobs, plan, h->codec_work, mat32, dim, &wide, st,
+                                                 &info));
         if (!wide) {
             HIP_TRY(sda::launch_combine_exact32(mat32, n_blobs, dim, dim, out, mm, st));
+            info.path = sda::kCodecMatrix32;
+            h->codec_last = info;
             return SDA_OK;
         }
+        info.fell_back |= sda::kCodecNarrowWide;
     }
     int64_t* mat = static_cast<int64_t*>(h->codec_mat);
-    HIP_TRY(sda::launch_varint_decode(bytes, n_blobs, plan, h->codec_work, mat, dim, dim, irregular, st));
+    HIP_TRY(sda::launch_varint_decode(bytes, n_blobs, plan, h->codec_work, mat, dim, dim, irregular, st, &info));
     HIP_TRY(sda::launch_combine_exact(mat, n_blobs, dim, dim, out, mm, st));
+    info.path = sda::kCodecMatrix64;
+    h->codec_last = info;
     return SDA_OK;
 }
 
@@ -2433,6 +2462,7 @@ sda_status host_chacha_combine(sda_engine* h, int64_t m, uint64_t D, const std::
 sda_status host_decode_combine(sda_engine* h, int64_t m, const uint8_t* const* blobs, const uint64_t* lens, uint64_t n,
                                int64_t* out, uint64_t out_cap, uint64_t* out_len) {
     *out_len = 0;
+    h->codec_last = sda::CodecLaunchInfo();     // this path keeps no record: a stale one must not be read
     if (n == 0) return SDA_OK;                                        // combiner.rs:17: empty input
     const uint64_t stage = host_stage_bytes();
     struct Group { uint64_t b0, nb, bytes; };

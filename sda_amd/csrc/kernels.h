@@ -143,6 +143,31 @@ struct VarintPlan {
     uint64_t max_regions = 0;            // regions of the largest blob (grid.x)
 };
 void varint_plan(const uint64_t* blob_off, uint64_t n_blobs, VarintPlan* plan);
+// How the clerk's decode -> combine produced its result (sda_codec_last_launch reports the handle's last one).
+// The launchers below fill the part they decide (the slot combine's columns per lane and groups, the fused
+// kernel's prefetch depth and variant, the grid slices of a decode pass, the sequential decoder); the engine's
+// decode_combine() adds the path it settled on and the attempts it abandoned.
+enum CodecPath : uint32_t {
+    kCodecNone = 0,           // no decode -> combine yet (or the last one failed, or ran the host streaming path)
+    kCodecSlots = 1,          // slot decode + slot_combine_kernel, the whole job in one pass
+    kCodecSlotsGrouped = 2,   // the same through one reused slot buffer, `passes` groups of blobs
+    kCodecFused = 3,          // varint_decode_combine_kernel<DEPTH, false>
+    kCodecFusedMulti = 4,     // varint_decode_combine_kernel<2, true> (an element of >= 6 bytes)
+    kCodecMatrix32 = 5,       // count pass + int32 matrix + combine
+    kCodecMatrix64 = 6,       // count pass + i64 matrix + combine
+};
+enum CodecFellBack : uint32_t {
+    kCodecSlotWide = 1,       // the slot attempt raised its wide flag and was abandoned
+    kCodecFusedIrregular = 2, // fused was asked for but a blob is irregular
+    kCodecNarrowWide = 4,     // the int32 matrix decode met a value outside int32 and was abandoned
+    kCodecSequential = 8,     // varint_sequential_kernel decoded the irregular blobs
+};
+struct CodecLaunchInfo {
+    uint32_t path = kCodecNone;
+    uint32_t width = 0;       // columns per lane of the slot combine (1/2/4) or the fused kernel's DEPTH (2/4/8)
+    uint32_t fell_back = 0;   // CodecFellBack bits
+    uint64_t passes = 0;      // blob groups (grouped slot path), else <= 65,535-blob grid slices of the decode pass
+};
 size_t varint_decode_work_bytes(size_t regions, uint64_t n_blobs);
 // element count of every blob (synchronous: copies n_blobs counts to the host); long_any: some element
 // has >= 6 bytes (sub_counts: also the 256-byte sub-chunk counts of the fused decode -> combine)
@@ -152,7 +177,7 @@ hipError_t launch_varint_count(const uint8_t* bytes, const uint64_t* blob_off_ho
 // decode every blob into out + blob * out_stride (after launch_varint_count on the same work)
 hipError_t launch_varint_decode(const uint8_t* bytes, uint64_t n_blobs, const VarintPlan& plan, void* work,
                                 int64_t* out, uint64_t out_stride, uint64_t len, bool irregular_any,
-                                hipStream_t s);
+                                hipStream_t s, CodecLaunchInfo* info = nullptr);
 // the same decode into int32 (regular blobs only: the caller checked irregular_any == false); *wide_host
 // (synchronous) tells whether some value did not fit, in which case out holds garbage
 // sda_varint_decode_dev in one pass of launches: count, scan, a device capacity check (some blob
@@ -162,15 +187,18 @@ hipError_t launch_varint_decode_one_wait(const uint8_t* bytes, const uint64_t* b
                                         const VarintPlan& plan, void* work, int64_t* out, uint64_t out_stride,
                                         uint64_t* counts_host, bool* too_long, hipStream_t s);
 hipError_t launch_varint_decode_narrow(const uint8_t* bytes, uint64_t n_blobs, const VarintPlan& plan, void* work,
-                                       int32_t* out, uint64_t out_stride, bool* wide_host, hipStream_t s);
+                                       int32_t* out, uint64_t out_stride, bool* wide_host, hipStream_t s,
+                                       CodecLaunchInfo* info = nullptr);
 // The clerk's fused decode -> combine (after launch_varint_count with sub_counts on the same work; regular
 // blobs of equal element count dim): out[dim] = combiner.rs:16-28 over the decoded blobs in order, each
-// payload read once.  tile_plan: device scratch of varint_tile_plan_bytes(n_blobs, dim).
+// payload read once.  tile_plan: device scratch of varint_tile_plan_bytes(n_blobs, dim).  *info (optional, this
+// launcher and the decode launchers around it): the part of the record each decides (CodecLaunchInfo); the
+// fused kernel's grid is over column tiles, so its `passes` are the grid slices of its tile plan.
 uint64_t varint_tile_plan_bytes(uint64_t n_blobs, uint64_t dim);
 uint64_t varint_fused_tiles(uint64_t dim);
 hipError_t launch_varint_decode_combine(const uint8_t* bytes, uint64_t n_blobs, const VarintPlan& plan, void* work,
                                         uint64_t* tile_plan, uint64_t dim, int64_t* out, int64_t modulus,
-                                        bool multi, hipStream_t s);
+                                        bool multi, hipStream_t s, CodecLaunchInfo* info = nullptr);
 // The clerk's decode -> combine over region slots (no count pass), in one pass of launches: the payload is
 // decoded once into int32 slots per 16 KiB region (slot buffer: varint_slot_bytes), region counts are
 // scanned, and combiner.rs:16-28 runs over the slots into out -- unless *flags_host comes back nonzero
@@ -181,7 +209,7 @@ size_t varint_slot_bytes(const VarintPlan& plan, uint64_t n_blobs, uint64_t dim)
 hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64_t* blob_off_host, uint64_t n_blobs,
                                               const VarintPlan& plan, void* work, void* slot_buf, int64_t* out,
                                               uint64_t out_cap, int64_t modulus, uint64_t* counts_host,
-                                              uint32_t* flags_host, hipStream_t s);
+                                              uint32_t* flags_host, hipStream_t s, CodecLaunchInfo* info = nullptr);
 size_t varint_encode_work_bytes(uint64_t rows, uint64_t len);
 // encode rows [rows][stride] (first len elements) back to back into dst; row_bytes_host gets each
 // row's byte count (synchronous).  hipErrorInvalidValue if dst_cap is too small.

@@ -52,6 +52,19 @@ CHACHA_MASK_ADD = 4
 CHACHA_STREAM = 5
 CHACHA_OVERFLOW = 6
 
+# sda_codec_last_launch's path codes and fell_back bits
+CODEC_NONE = 0
+CODEC_SLOTS = 1
+CODEC_SLOTS_GROUPED = 2
+CODEC_FUSED = 3
+CODEC_FUSED_MULTI = 4
+CODEC_MATRIX32 = 5
+CODEC_MATRIX64 = 6
+CODEC_FB_SLOT_WIDE = 1
+CODEC_FB_FUSED_IRREGULAR = 2
+CODEC_FB_NARROW_WIDE = 4
+CODEC_FB_SEQUENTIAL = 8
+
 _i64p = C.POINTER(C.c_int64)
 _u64p = C.POINTER(C.c_uint64)
 _u32p = C.POINTER(C.c_uint32)
@@ -96,6 +109,7 @@ SIGNATURES = [
     ("sda_host_stream_stats", _st, [_vp, _u64p, _u64p, _u64p]),
     ("sda_packed_fixup_count", _st, [_vp, _u64p]),
     ("sda_chacha_last_launch", _st, [_vp, _u32p, _u64p, _u64p]),
+    ("sda_codec_last_launch", _st, [_vp, _u32p, _u32p, _u32p, _u64p]),
     ("sda_combine_split_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     ("sda_combine_split_prefix_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp,
                                            _vp]),
@@ -449,6 +463,14 @@ class Engine:
         path, grid_y, fixups = C.c_uint32(), C.c_uint64(), C.c_uint64()
         _check(self.lib.sda_chacha_last_launch(self.h, C.byref(path), C.byref(grid_y), C.byref(fixups)))
         return int(path.value), int(grid_y.value), int(fixups.value)
+
+    def codec_last_launch(self):
+        """(path, width, fell_back, passes) of the handle's last clerk_decode_combine_dev: path is one of the CODEC_*
+        codes, width the slot combine's columns per lane or the fused kernel's prefetch depth, fell_back the
+        CODEC_FB_* bits, passes the blob groups or grid slices (sda_codec_last_launch)."""
+        path, width, fb, passes = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        _check(self.lib.sda_codec_last_launch(self.h, C.byref(path), C.byref(width), C.byref(fb), C.byref(passes)))
+        return int(path.value), int(width.value), int(fb.value), int(passes.value)
 
     def combine_finalize_dev(self, modulus, sums_ptr, dim, out_ptr, stream=None):
         _check(self.lib.sda_combine_finalize_dev(self.h, modulus, sums_ptr, dim, out_ptr, stream))

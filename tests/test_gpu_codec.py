@@ -11,6 +11,7 @@ import pytest
 
 from sda_amd import SdaError, schemes as S
 from sda_amd import engine as E
+from tests import codec_dispatch as CD
 from tests.util import assert_same
 
 pytestmark = pytest.mark.gpu
@@ -200,6 +201,8 @@ def test_continuation_runs_at_every_alignment(engine, oracle, monkeypatch, run):
         assert engine.clerk_decode_combine_dev(m, t.data_ptr(), off, res.data_ptr(), S) == S
         torch.cuda.synchronize()
         assert_same(res.cpu().numpy(), exp, f"{path} run={run}")
+        # runs of >= 5 send the slot path to the matrix one, runs of >= 11 the fused path too: the record tells
+        assert engine.codec_last_launch() == CD.predict_blobs(blobs, m, {"SDA_CODEC_PATH": path}), path
 
 
 @pytest.mark.parametrize("case", ["one_byte", "one_region", "exact_cap", "mixed_blobs"])
@@ -232,6 +235,10 @@ def test_slot_cap_overflow_falls_back(engine, oracle, monkeypatch, case):
         assert engine.clerk_decode_combine_dev(m, t.data_ptr(), off, res.data_ptr(), D) == D
         torch.cuda.synchronize()
         assert_same(res.cpu().numpy(), exp, f"{case} {path}")
+        record = engine.codec_last_launch()
+        assert record == CD.predict_blobs(blobs, m, {"SDA_CODEC_PATH": path}), path
+        if path == "slots":                      # exact_cap alone stays on the slots
+            assert record[:3] == ((CD.SLOTS, 4, 0) if case == "exact_cap" else (CD.MATRIX32, 0, CD.FB_SLOT_WIDE))
 
 
 def test_encode_dev_capacity(engine, oracle):

@@ -17,6 +17,7 @@ with the oracle on every case; elements longer than 5 bytes send the slot path t
 import numpy as np
 import pytest
 
+from tests import codec_dispatch as CD
 from tests.util import assert_same
 
 pytestmark = pytest.mark.gpu
@@ -43,6 +44,9 @@ def _run(engine, m, blobs, dim, path, monkeypatch):
     n = engine.clerk_decode_combine_dev(m, t.data_ptr(), off, out.data_ptr(), out.numel())
     torch.cuda.synchronize()
     assert n == dim
+    # the kernel the dispatcher's rules give for these bytes is the one that ran (sda_codec_last_launch): a slot or
+    # fused request that fell back to the matrix path is told apart from one that ran
+    assert engine.codec_last_launch() == CD.predict_blobs(blobs, m, {"SDA_CODEC_PATH": path}), path
     return out[:dim].cpu().numpy()
 
 
