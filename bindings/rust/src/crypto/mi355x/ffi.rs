@@ -167,6 +167,8 @@ extern "C" {
                                         stream: *mut c_void) -> SdaStatus;
     pub fn sda_varint_encode_dev(h: *mut SdaEngine, vals: *const i64, rows: u64, len: u64, stride: u64,
                                  dst: *mut u8, dst_cap: u64, row_bytes: *mut u64, stream: *mut c_void) -> SdaStatus;
+    pub fn sda_varint_encode32_dev(h: *mut SdaEngine, vals: *const i32, rows: u64, len: u64, stride: u64,
+                                   dst: *mut u8, dst_cap: u64, row_bytes: *mut u64, stream: *mut c_void) -> SdaStatus;
 
     // ---- snapshot transposition (server/src/stores.rs:86-101) ----
     pub fn sda_snapshot_transpose_dev(h: *mut SdaEngine, src: *const u8, part_off: *const u64,
@@ -190,6 +192,11 @@ extern "C" {
                                      secrets: *const i64, dimension: u64, draws: *const i64, mode: i32,
                                      shares_out: *mut i64, payload: *mut u8, payload_cap: u64,
                                      payload_row_bytes: *mut u64, stream: *mut c_void) -> SdaStatus;
+    pub fn sda_participant_share32_dev(h: *mut SdaEngine, ms: *const SdaMaskingScheme, seed: *const u32,
+                                       seed_words: u64, full_masks: *const i64, ss: *const SdaSharingScheme,
+                                       secrets: *const i64, dimension: u64, draws: *const i64, mode: i32,
+                                       shares_out: *mut i32, payload: *mut u8, payload_cap: u64,
+                                       payload_row_bytes: *mut u64, stream: *mut c_void) -> SdaStatus;
 
     // ---- synthetic benchmark input ----
     pub fn sda_synth_fill_dev(h: *mut SdaEngine, dst: *mut i64, rows: u64, cols: u64, seed: u64, lo: i64, hi: i64,

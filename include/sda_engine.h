@@ -322,7 +322,8 @@ sda_status sda_packed_reconstruct_dev(sda_engine* h, const sda_sharing_scheme* s
 /* ---- int32 share rows through the packed-Shamir data flow ----
  * check_packed admits only primes p < 2^31 and every share is a `% p` result, so |share| <= p - 1 < 2^31: half
  * of an i64 share is sign extension.  With these two entry points the device-resident chain generate ->
- * sda_combine32_dev -> sda_narrow32_dev (of the n clerk results) -> reveal stays in int32 rows end to end
+ * sda_combine32_dev -> sda_narrow32_dev (of the n clerk results) -> reveal stays in int32 rows end to end, and so
+ * does the participant's generate -> sda_varint_encode32_dev (or sda_participant_share32_dev) -> clerk decode
  * (INTEGRATION.md).  Argument checks, error codes, the 65,535-vector and 1,023-share limits, the stream ordering
  * on the handle and sda_packed_fixup_count afterwards are those of the i64 entry points; on a multi-device handle
  * they run on ordinals[0].  out / shares need only 4-byte alignment and any B works; the fast stores need a
@@ -393,6 +394,14 @@ sda_status sda_clerk_decode_combine_dev(sda_engine* h, int64_t modulus, const ui
 sda_status sda_varint_encode_dev(sda_engine* h, const int64_t* vals, uint64_t rows, uint64_t len,
                                  uint64_t stride, uint8_t* dst, uint64_t dst_cap,
                                  uint64_t* row_bytes, void* stream);
+/* The same from int32 rows (a share below 2^31 in magnitude, e.g. sda_packed_generate32_dev's output): stride is
+ * in int32 elements and vals needs only 4-byte alignment.  The bytes written and row_bytes are identical to
+ * sign-extending the rows and calling sda_varint_encode_dev (an element takes at most 5 bytes); argument checks,
+ * status codes, the 65,535-row limit, the stream ordering on the handle and the wait for the row sizes are those
+ * of sda_varint_encode_dev.  A dst_cap below the total returns SDA_ERR_INVALID_ARGUMENT and writes nothing. */
+sda_status sda_varint_encode32_dev(sda_engine* h, const int32_t* vals, uint64_t rows, uint64_t len,
+                                   uint64_t stride, uint8_t* dst, uint64_t dst_cap,
+                                   uint64_t* row_bytes, void* stream);
 
 /* ---------------- snapshot transposition ----------------
  * Replaces AggregationsStore::iter_snapshot_clerk_jobs_data (server/src/stores.rs:86-101; the Mongo
@@ -452,6 +461,23 @@ sda_status sda_participant_share_dev(sda_engine* h, const sda_masking_scheme* ms
                                      const sda_sharing_scheme* ss, const int64_t* secrets, uint64_t dimension,
                                      const int64_t* draws, int32_t mode, int64_t* shares_out, uint8_t* payload,
                                      uint64_t payload_cap, uint64_t* payload_row_bytes, void* stream);
+
+/* sda_participant_share_dev with the shares as int32 rows: shares_out [n][B] int32, dense (4-byte alignment is
+ * enough), generated by what sda_packed_generate32_dev launches and encoded by sda_varint_encode32_dev's kernels,
+ * so a share stays 4 bytes wide from share generation to the clerk's sda_clerk_decode_combine_dev.  shares_out is
+ * bit-identical to (int32_t) of the i64 pipeline's shares, payload and payload_row_bytes are byte-identical to
+ * the i64 pipeline's, in both modes and for every packed scheme in the engine's domain.  Masking (the ChaCha
+ * rejection check and its redo of every later step included), sda_chacha_last_launch, sda_packed_fixup_count,
+ * payload == NULL and the waits are those of sda_participant_share_dev.
+ * PackedShamir only: an Additive scheme returns SDA_ERR_UNSUPPORTED, because its first n - 1 shares are the
+ * caller's draws copied verbatim and the engine does not range-check them, so they need not fit int32.
+ * At n + 1 = 81 the SDA_ERR_OUT_OF_MEMORY contract of sda_packed_generate32_dev applies (n * B * 8 bytes of
+ * handle-owned scratch; shares_out and payload are untouched when it cannot be allocated). */
+sda_status sda_participant_share32_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                       uint64_t seed_words, const int64_t* full_masks,
+                                       const sda_sharing_scheme* ss, const int64_t* secrets, uint64_t dimension,
+                                       const int64_t* draws, int32_t mode, int32_t* shares_out, uint8_t* payload,
+                                       uint64_t payload_cap, uint64_t* payload_row_bytes, void* stream);
 
 /* Synthetic benchmark input: dst[r*cols + c] = lo + splitmix64(seed, r, c) % (hi - lo). */
 sda_status sda_synth_fill_dev(sda_engine* h, int64_t* dst, uint64_t rows, uint64_t cols,

@@ -1017,6 +1017,162 @@ __global__ __launch_bounds__(kThreads) void varint_write_kernel(const int64_t* _
     }
 }
 
+// ---------------- encode, int32 rows ----------------
+// The same byte stream from int32 rows (a field share below 2^31): an element takes at most 5 bytes, so the
+// zigzag, the size and the byte image stay in 32-bit registers, an element touches at most two LDS dwords, and
+// the chunk's LDS image is 5 bytes per element instead of 10.
+#ifndef SDA_ENC32_CHUNK
+#define SDA_ENC32_CHUNK 2048                  // A/B against 4096: DESIGN.md §4.5
+#endif
+constexpr uint32_t kEnc32Chunk = SDA_ENC32_CHUNK;   // elements per int32 encode block
+constexpr uint32_t kEnc32Epl = 4;             // adjacent elements per lane per round: one 16-byte load
+constexpr uint32_t kEnc32Rounds = kEnc32Chunk / (kEnc32Epl * kThreads);
+static_assert(kEnc32Chunk % (kEnc32Epl * kThreads) == 0 && kEnc32Chunk * 5 / 16 <= kEncChunk * 10 / 16,
+              "int32 encode chunk: whole rounds, and an LDS image no larger than the i64 kernel's");
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ uint32_t zigzag32(int32_t v) { return ((uint32_t)v << 1) ^ (uint32_t)(v >> 31); }
+__device__ __forceinline__ uint32_t varint_size32(uint32_t z) { return (uint32_t)(32 - __builtin_clz(z | 1) + 6) / 7; }
+// A full chunk whose first element is 16-byte aligned is read as element quads.  A row of int32 starts 0, 4, 8
+// or 12 bytes off a 16-byte boundary (stride and base are only 4-byte aligned), and every chunk of the row
+// shares that offset (the chunk is a multiple of 4 elements): only offset 0 takes the 16-byte loads.
+__device__ __forceinline__ bool enc32_quads_ok(const int32_t* rowp, uint64_t e0, uint64_t len) {
+    return e0 + kEnc32Chunk <= len && ((uintptr_t)(rowp + e0) & 15) == 0;
+}
+
+__global__ __launch_bounds__(kThreads) void varint_size32_kernel(const int32_t* __restrict__ vals, uint64_t len,
+                                                                 uint64_t stride, uint32_t chunks,
+                                                                 uint64_t* __restrict__ chunk_bytes) {
+    const uint32_t c = blockIdx.x, row = blockIdx.y;
+    const uint64_t e0 = (uint64_t)c * kEnc32Chunk;
+    const int32_t* rowp = vals + (uint64_t)row * stride;
+    uint32_t n = 0;                                          // <= 5 * kEnc32Chunk
+    if (enc32_quads_ok(rowp, e0, len)) {
+#pragma unroll
+        for (uint32_t q = 0; q < kEnc32Rounds; ++q) {
+            const i32x4 x = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(rowp + e0) + q * kThreads + threadIdx.x);
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) n += varint_size32(zigzag32(x[j]));
+        }
+    } else {
+#pragma unroll
+        for (uint32_t q = 0; q < kEnc32Chunk / kThreads; ++q) {
+            const uint64_t e = e0 + q * kThreads + threadIdx.x;
+            if (e < len) n += varint_size32(zigzag32(rowp[e]));
+        }
+    }
+    __shared__ uint32_t red[kThreads / 64];
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+        for (int i = 0; i < kThreads / 64; ++i) s += red[i];
+        chunk_bytes[(uint64_t)row * chunks + c] = s;
+    }
+}
+
+// write: varint_write_kernel's structure (rounds of coalesced loads, one block-wide scan of the lane sizes per
+// round, a zeroed LDS image aligned to the chunk's global byte offset mod 16, 16-byte interior stores and
+// byte-wise partial end words).  Per element: groups 0..3 spread into one dword, group 4 in a fifth byte; the 40
+// bits shifted to the byte offset are one or two ds_or_b32.  The image is lead (< 16) + at most
+// 5 * kEnc32Chunk bytes; a dword past an element's last byte is never touched (o1 == 0 is skipped).
+template <bool NT>
+__global__ __launch_bounds__(kThreads) void varint_write32_kernel(const int32_t* __restrict__ vals, uint64_t len,
+                                                                  uint64_t stride, uint32_t chunks,
+                                                                  const uint64_t* __restrict__ chunk_off,
+                                                                  const uint64_t* __restrict__ row_base,
+                                                                  const uint32_t* __restrict__ too_big,
+                                                                  uint8_t* __restrict__ dst) {
+    const uint32_t c = blockIdx.x, row = blockIdx.y;
+    if (*too_big) return;
+    const uint64_t e0 = (uint64_t)c * kEnc32Chunk;
+    constexpr uint32_t kBufQuads = (kEnc32Chunk * 5 + 15 + 15) / 16;     // lead <= 15, rounded up to a quad
+    __shared__ uint4 buf4[kBufQuads];
+    __shared__ uint32_t wsum[kThreads / 64];
+    uint32_t* buf = reinterpret_cast<uint32_t*>(buf4);
+    const uint8_t* b8 = reinterpret_cast<const uint8_t*>(buf4);
+    uint8_t* gdst = dst + row_base[row] + chunk_off[(uint64_t)row * chunks + c];
+    const uint32_t lead = (uint32_t)((uintptr_t)gdst & 15);
+    for (uint32_t k = threadIdx.x; k < kBufQuads; k += kThreads) buf4[k] = make_uint4(0, 0, 0, 0);
+    // round q: lane t owns the 4 adjacent elements e0 + 1024 q + 4 t + j
+    const int32_t* rowp = vals + (uint64_t)row * stride;
+    uint32_t z[kEnc32Rounds][kEnc32Epl];
+    const bool full = e0 + kEnc32Chunk <= len;
+    if (enc32_quads_ok(rowp, e0, len)) {
+#pragma unroll
+        for (uint32_t q = 0; q < kEnc32Rounds; ++q) {
+            const i32x4 x = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(rowp + e0) + q * kThreads + threadIdx.x);
+#pragma unroll
+            for (uint32_t j = 0; j < kEnc32Epl; ++j) z[q][j] = zigzag32(x[j]);
+        }
+    } else {
+#pragma unroll
+        for (uint32_t q = 0; q < kEnc32Rounds; ++q)
+#pragma unroll
+            for (uint32_t j = 0; j < kEnc32Epl; ++j) {
+                const uint64_t e = e0 + kEnc32Epl * (q * kThreads + threadIdx.x) + j;
+                z[q][j] = e < len ? zigzag32(rowp[e]) : 0u;
+            }
+    }
+    uint32_t base = lead;
+#pragma unroll
+    for (uint32_t q = 0; q < kEnc32Rounds; ++q) {
+        const uint64_t e = e0 + kEnc32Epl * (q * kThreads + threadIdx.x);
+        uint32_t ns[kEnc32Epl], pre[kEnc32Epl], np = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kEnc32Epl; ++j) {
+            ns[j] = (full || e + j < len) ? varint_size32(z[q][j]) : 0u;
+            pre[j] = np;
+            np += ns[j];
+        }
+        const uint32_t incl = wave_incl_scan(np);
+        __syncthreads();                                     // wsum of the previous q consumed (and, at
+        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;    // q = 0, the zeroed image visible)
+        __syncthreads();
+        uint32_t off0 = base + incl - np, total = 0;
+        for (uint32_t w = 0; w < kThreads / 64; ++w) {
+            if (w < (threadIdx.x >> 6)) off0 += wsum[w];
+            total += wsum[w];
+        }
+        base += total;
+#pragma unroll
+        for (uint32_t h = 0; h < kEnc32Epl; ++h) {
+            const uint32_t n = ns[h], off = off0 + pre[h], zz = z[q][h];
+            if (n) {
+                // bytes 0..3: groups 0..3, continuation bit on every byte but the element's last; byte 4: group 4
+                uint32_t x = zz & 0x0FFFFFFFu;
+                x = (x & 0x00003FFFu) | ((x & 0x0FFFC000u) << 2);
+                x = (x & 0x007F007Fu) | ((x & 0x3F803F80u) << 1);
+                const uint32_t nc = n - 1;
+                const uint32_t lo = x | (nc >= 4 ? 0x80808080u : (0x80808080u & ((1u << (8 * nc)) - 1)));
+                const uint32_t hi = zz >> 28;                                // 0 unless n == 5
+                const uint32_t sh = (off & 3) * 8, dw = off >> 2;
+                const uint32_t o0 = lo << sh;
+                const uint32_t o1 = sh ? __builtin_amdgcn_alignbit(hi, lo, 32 - sh) : hi;
+                atomicOr(&buf[dw], o0);                                      // ds_or_b32
+                if (o1) atomicOr(&buf[dw + 1], o1);
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t end = base;                               // lead + chunk bytes
+    uint4* d128 = reinterpret_cast<uint4*>(gdst - lead);
+    uint8_t* d8 = gdst - lead;
+    const uint32_t nq = (end + 15) / 16;
+    for (uint32_t k = threadIdx.x; k < nq; k += kThreads) {
+        const uint32_t lo = k * 16, hi = lo + 16;
+        if (lo >= lead && hi <= end) {
+            if constexpr (NT)
+                __builtin_nontemporal_store(reinterpret_cast<const u32x4*>(buf4)[k], reinterpret_cast<u32x4*>(d128) + k);
+            else d128[k] = buf4[k];
+        } else {
+            for (uint32_t i = lo; i < hi; ++i)
+                if (i >= lead && i < end) d8[i] = b8[i];
+        }
+    }
+}
+
 // exclusive scan of chunk_bytes per row (one block per row) + row base; row_bytes = total
 // One workgroup: rows placed back to back -- row_base = exclusive scan of row_bytes; *too_big = the total
 // exceeds cap (the write pass then writes nothing and the host reports it).
@@ -1477,6 +1633,51 @@ hipError_t launch_varint_encode(const int64_t* vals, uint64_t rows, uint64_t len
         hipLaunchKernelGGL(varint_write_kernel<false>, dim3((unsigned)chunks, (unsigned)rows), dim3(kThreads), 0, s,
                            vals, len, stride, (uint32_t)chunks, (const uint64_t*)chunk_off,
                            (const uint64_t*)row_base, (const uint32_t*)too_big, dst);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(row_bytes_host, rbytes, rows * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+    uint64_t acc = 0;
+    for (uint64_t r = 0; r < rows; ++r) acc += row_bytes_host[r];
+    return acc > dst_cap ? hipErrorInvalidValue : hipSuccess;     // nothing was written (too_big)
+}
+
+// int32 rows: launch_varint_encode's work-buffer layout with chunks of kEnc32Chunk elements, its three scan
+// kernels, its one wait and its SDA_ENC_NT knob
+size_t varint_encode32_work_bytes(uint64_t rows, uint64_t len) {
+    const uint64_t chunks = (len + kEnc32Chunk - 1) / kEnc32Chunk;
+    return 2 * rows * (chunks ? chunks : 1) * 8 + 2 * rows * 8 + 1024 + 256;
+}
+
+hipError_t launch_varint_encode32(const int32_t* vals, uint64_t rows, uint64_t len, uint64_t stride, uint8_t* dst,
+                                  uint64_t dst_cap, void* work, uint64_t* row_bytes_host, hipStream_t s) {
+    const uint64_t chunks = (len + kEnc32Chunk - 1) / kEnc32Chunk;
+    if (rows == 0) return hipSuccess;
+    if (chunks == 0) {
+        for (uint64_t r = 0; r < rows; ++r) row_bytes_host[r] = 0;
+        return hipSuccess;
+    }
+    uint64_t* chunk_bytes = static_cast<uint64_t*>(work);
+    uint64_t* chunk_off = chunk_bytes + rows * chunks;
+    uint64_t* row_base = chunk_off + rows * chunks;
+    uint64_t* rbytes = row_base + rows;
+    uint32_t* too_big = reinterpret_cast<uint32_t*>(rbytes + rows);
+    const dim3 grid((unsigned)chunks, (unsigned)rows), block(kThreads);
+    hipError_t e;
+    hipLaunchKernelGGL(varint_size32_kernel, grid, block, 0, s, vals, len, stride, (uint32_t)chunks, chunk_bytes);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(varint_offsets_kernel, dim3((unsigned)rows), block, 0, s, (const uint64_t*)chunk_bytes,
+                       (uint32_t)chunks, (const uint64_t*)nullptr, chunk_off, rbytes);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(varint_rows_kernel, dim3(1), block, 0, s, (const uint64_t*)rbytes, rows, dst_cap, row_base,
+                       too_big);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const char* nt = getenv("SDA_ENC_NT");
+    if (!(nt && nt[0] == '0'))
+        hipLaunchKernelGGL(varint_write32_kernel<true>, grid, block, 0, s, vals, len, stride, (uint32_t)chunks,
+                           (const uint64_t*)chunk_off, (const uint64_t*)row_base, (const uint32_t*)too_big, dst);
+    else
+        hipLaunchKernelGGL(varint_write32_kernel<false>, grid, block, 0, s, vals, len, stride, (uint32_t)chunks,
+                           (const uint64_t*)chunk_off, (const uint64_t*)row_base, (const uint32_t*)too_big, dst);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(row_bytes_host, rbytes, rows * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;

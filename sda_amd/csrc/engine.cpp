@@ -1737,6 +1737,21 @@ sda_status sda_varint_encode_dev(sda_engine* h, const int64_t* vals, uint64_t ro
     return ok();
 }
 
+sda_status sda_varint_encode32_dev(sda_engine* h, const int32_t* vals, uint64_t rows, uint64_t len, uint64_t stride,
+                                   uint8_t* dst, uint64_t dst_cap, uint64_t* row_bytes, void* stream) {
+    SDA_ENTRY;
+    if (!h || !row_bytes || (rows && len && (!vals || !dst))) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (rows > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 rows per call");
+    if (stride < len) return fail(SDA_ERR_INVALID_ARGUMENT, "stride < len");
+    HIP_TRY(hipSetDevice(h->device));
+    if (sda_status e = ensure(&h->codec_work, &h->codec_work_bytes, sda::varint_encode32_work_bytes(rows, len))) return e;
+    hipError_t e = sda::launch_varint_encode32(vals, rows, len, stride, dst, dst_cap, h->codec_work, row_bytes,
+                                               pick(h, stream));
+    if (e == hipErrorInvalidValue) return fail(SDA_ERR_INVALID_ARGUMENT, "dst_cap too small");
+    HIP_TRY(e);
+    return ok();
+}
+
 // ---------------- snapshot transposition (stores.rs:86-101) ----------------
 // Offsets are a host-side plan (like the codec's blob_off); the bytes move on the device.
 sda_status sda_snapshot_transpose_dev(sda_engine* h, const uint8_t* src, const uint64_t* part_off,
@@ -2023,20 +2038,23 @@ sda_status sda_recipient_reveal(sda_engine* h, const sda_masking_scheme* ms, con
     return finish(h);
 }
 
-// participate.rs:53-76 (+ the encoding step of Encryptor::encrypt, sodium.rs:36-41) on device.
-sda_status sda_participant_share_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
-                                     uint64_t seed_words, const int64_t* full_masks, const sda_sharing_scheme* ss,
-                                     const int64_t* secrets, uint64_t dimension, const int64_t* draws,
-                                     int32_t mode, int64_t* shares_out, uint8_t* payload, uint64_t payload_cap,
-                                     uint64_t* payload_row_bytes, void* stream) {
-    SDA_ENTRY;
-    if (!h || !ms || !ss || (dimension && (!secrets || !shares_out)) || (payload && !payload_row_bytes))
+// The participant pipeline behind sda_participant_share_dev and sda_participant_share32_dev.  One of shares64 /
+// shares32 is the [n][B] output (shares32: int32 rows, PackedShamir only, encoded by the int32 encoder).
+static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                    uint64_t seed_words, const int64_t* full_masks, const sda_sharing_scheme* ss,
+                                    const int64_t* secrets, uint64_t dimension, const int64_t* draws, int32_t mode,
+                                    int64_t* shares64, int32_t* shares32, uint8_t* payload, uint64_t payload_cap,
+                                    uint64_t* payload_row_bytes, void* stream) {
+    if (!h || !ms || !ss || (dimension && (!secrets || (!shares64 && !shares32))) || (payload && !payload_row_bytes))
         return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = pick(h, stream);
     const uint64_t D = dimension;
     const bool packed = ss->kind == SDA_SHARING_PACKED_SHAMIR;
     if (!packed && ss->kind != SDA_SHARING_ADDITIVE) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown sharing scheme kind");
+    if (!packed && shares32)
+        return fail(SDA_ERR_UNSUPPORTED, "int32 shares need a PackedShamir scheme: an additive scheme's first n - 1 "
+                                         "shares are the caller's draws, copied unchecked");
     if (mode != SDA_REVEAL_EXACT && mode != SDA_REVEAL_CANONICAL) return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
     if (packed) {
         if (sda_status e = check_packed(ss)) return e;
@@ -2099,21 +2117,33 @@ sda_status sda_participant_share_dev(sda_engine* h, const sda_masking_scheme* ms
         if (B) {
             if (packed) {
                 if (sda_status e = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
-                sda::PackedGenArgs ga{masked, D, 1, draws, shares_out, mode == SDA_REVEAL_CANONICAL};
-                HIP_TRY(sda::launch_packed_generate(ga, (uint32_t)ss->secret_count, (uint32_t)ss->privacy_threshold,
-                                                    (uint32_t)n, (uint32_t)ss->modulus, (uint32_t)ss->omega_secrets,
-                                                    (uint32_t)ss->omega_shares, h->gen_tab, h->gen_log, st,
-                                                    &h->gen_log_used));
+                sda::PackedGenArgs ga{masked, D, 1, draws, shares64, mode == SDA_REVEAL_CANONICAL};
+                const uint32_t k = (uint32_t)ss->secret_count, t = (uint32_t)ss->privacy_threshold;
+                if (shares32) {                  // as sda_packed_generate32_dev: scratch + narrowing at n + 1 = 81
+                    ga.out32 = shares32;
+                    if (const size_t tmp = sda::packed_gen32_scratch_bytes(ga, k, t, (uint32_t)n, (uint32_t)ss->modulus)) {
+                        if (sda_status e = ensure(&h->gen32_tmp, &h->gen32_tmp_bytes, tmp + 64)) return e;
+                        ga.scratch = static_cast<int64_t*>(h->gen32_tmp);
+                        ga.flag = ga.scratch + tmp / sizeof(int64_t);
+                    }
+                }
+                HIP_TRY(sda::launch_packed_generate(ga, k, t, (uint32_t)n, (uint32_t)ss->modulus,
+                                                    (uint32_t)ss->omega_secrets, (uint32_t)ss->omega_shares,
+                                                    h->gen_tab, h->gen_log, st, &h->gen_log_used));
             } else {
-                HIP_TRY(sda::launch_additive_generate(masked, D, draws, n, shares_out, ss->modulus, st));
+                HIP_TRY(sda::launch_additive_generate(masked, D, draws, n, shares64, ss->modulus, st));
             }
         }
         // 3. per-clerk payload encoding (participate.rs:79-98 -> sodium.rs:36-41); sealing stays on the host
         if (payload) {
-            if (sda_status e = ensure(&h->codec_work, &h->codec_work_bytes, sda::varint_encode_work_bytes(n, B)))
+            if (sda_status e = ensure(&h->codec_work, &h->codec_work_bytes,
+                                      shares32 ? sda::varint_encode32_work_bytes(n, B)
+                                               : sda::varint_encode_work_bytes(n, B)))
                 return e;
-            hipError_t e = sda::launch_varint_encode(shares_out, n, B, B, payload, payload_cap, h->codec_work,
-                                                     payload_row_bytes, st);
+            hipError_t e = shares32 ? sda::launch_varint_encode32(shares32, n, B, B, payload, payload_cap,
+                                                                  h->codec_work, payload_row_bytes, st)
+                                    : sda::launch_varint_encode(shares64, n, B, B, payload, payload_cap,
+                                                                h->codec_work, payload_row_bytes, st);
             if (e == hipErrorInvalidValue) return fail(SDA_ERR_INVALID_ARGUMENT, "payload_cap too small");
             HIP_TRY(e);
         }
@@ -2134,6 +2164,28 @@ sda_status sda_participant_share_dev(sda_engine* h, const sda_masking_scheme* ms
         }
     }
     return ok();
+}
+
+// participate.rs:53-76 (+ the encoding step of Encryptor::encrypt, sodium.rs:36-41) on device.
+sda_status sda_participant_share_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                     uint64_t seed_words, const int64_t* full_masks, const sda_sharing_scheme* ss,
+                                     const int64_t* secrets, uint64_t dimension, const int64_t* draws,
+                                     int32_t mode, int64_t* shares_out, uint8_t* payload, uint64_t payload_cap,
+                                     uint64_t* payload_row_bytes, void* stream) {
+    SDA_ENTRY;
+    return participant_share(h, ms, seed, seed_words, full_masks, ss, secrets, dimension, draws, mode, shares_out,
+                             nullptr, payload, payload_cap, payload_row_bytes, stream);
+}
+
+// The same with the shares as int32 rows, from sda_packed_generate32_dev's kernels into the int32 encoder.
+sda_status sda_participant_share32_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                       uint64_t seed_words, const int64_t* full_masks, const sda_sharing_scheme* ss,
+                                       const int64_t* secrets, uint64_t dimension, const int64_t* draws, int32_t mode,
+                                       int32_t* shares_out, uint8_t* payload, uint64_t payload_cap,
+                                       uint64_t* payload_row_bytes, void* stream) {
+    SDA_ENTRY;
+    return participant_share(h, ms, seed, seed_words, full_masks, ss, secrets, dimension, draws, mode, nullptr,
+                             shares_out, payload, payload_cap, payload_row_bytes, stream);
 }
 
 }  // extern "C"

@@ -215,6 +215,10 @@ size_t varint_encode_work_bytes(uint64_t rows, uint64_t len);
 // row's byte count (synchronous).  hipErrorInvalidValue if dst_cap is too small.
 hipError_t launch_varint_encode(const int64_t* vals, uint64_t rows, uint64_t len, uint64_t stride, uint8_t* dst,
                                 uint64_t dst_cap, void* work, uint64_t* row_bytes_host, hipStream_t s);
+// The same from int32 rows (stride in int32 elements, vals 4-byte aligned): the bytes of the sign-extended rows.
+size_t varint_encode32_work_bytes(uint64_t rows, uint64_t len);
+hipError_t launch_varint_encode32(const int32_t* vals, uint64_t rows, uint64_t len, uint64_t stride, uint8_t* dst,
+                                  uint64_t dst_cap, void* work, uint64_t* row_bytes_host, hipStream_t s);
 
 // ---- chacha.hip ----
 // Combine of n_seeds ChaCha mask streams (chacha.rs:57-76), two implementations:

@@ -140,6 +140,7 @@ SIGNATURES = [
     ("sda_varint_decode_dev", _st, [_vp, _vp, _u64p, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
     ("sda_clerk_decode_combine_dev", _st, [_vp, C.c_int64, _vp, _u64p, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
     ("sda_varint_encode_dev", _st, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
+    ("sda_varint_encode32_dev", _st, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
     ("sda_snapshot_transpose_dev", _st, [_vp, _vp, _u64p, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _u64p, _u64p,
                                          _u64p, _vp]),
     ("sda_recipient_reveal_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _vp, C.c_uint64, C.c_uint64,
@@ -151,24 +152,28 @@ SIGNATURES = [
     ("sda_participant_share_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _u32p, C.c_uint64, _vp,
                                         C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, _vp, C.c_int32, _vp, _vp,
                                         C.c_uint64, _u64p, _vp]),
+    ("sda_participant_share32_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _u32p, C.c_uint64, _vp,
+                                          C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, _vp, C.c_int32, _vp, _vp,
+                                          C.c_uint64, _u64p, _vp]),
 ]
 
-_lib = None
+_libs = {}
 
 
-def load_library():
-    """Load the in-tree engine library; raises if it has not been built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"MI355X engine not built: {LIB_PATH} is missing (run `make` / __graft_entry__.build())")
-        lib = C.CDLL(LIB_PATH)
+def load_library(path: Optional[str] = None):
+    """Load the in-tree engine library (or another build of it at `path`, for an in-process A/B of two builds);
+    raises if it has not been built."""
+    path = path or LIB_PATH
+    if path not in _libs:
+        if not os.path.exists(path):
+            raise RuntimeError(f"MI355X engine not built: {path} is missing (run `make` / __graft_entry__.build())")
+        lib = C.CDLL(path)
         for name, res, args in SIGNATURES:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        _lib = lib
-    return _lib
+        _libs[path] = lib
+    return _libs[path]
 
 
 class SdaError(Exception):
@@ -232,15 +237,15 @@ class _HbmBlock:
 class Engine:
     """One engine handle = one HIP device + one stream (sda_engine_create), or, with `devices`, one handle over
     several devices (sda_engine_create_multi): the host trait calls then split over them; the `_dev` entry points
-    run on devices[0]."""
+    run on devices[0].  `lib_path` names another build of the library than the in-tree one."""
 
-    def __init__(self, device: int = 0, devices: Optional[Sequence[int]] = None):
+    def __init__(self, device: int = 0, devices: Optional[Sequence[int]] = None, lib_path: Optional[str] = None):
         # torch (when the caller uses it) ships its own HIP runtime; it has to open the device before
         # the engine's ROCm runtime does, or torch later reports "No HIP GPUs are available"
         t = sys.modules.get("torch")
         if t is not None and t.cuda.is_available():
             t.cuda.init()
-        self.lib = load_library()
+        self.lib = load_library(lib_path)
         h = _vp()
         if devices is None:
             _check(self.lib.sda_engine_create(device, C.byref(h)))
@@ -557,6 +562,13 @@ class Engine:
                                               _ptr(rb, _u64p), stream))
         return rb[:rows]
 
+    def varint_encode32_dev(self, vals_ptr, rows, length, stride, dst_ptr, dst_cap, stream=None) -> np.ndarray:
+        """varint_encode_dev from int32 rows (stride in int32 elements): the bytes of the sign-extended rows."""
+        rb = np.zeros(max(rows, 1), np.uint64)
+        _check(self.lib.sda_varint_encode32_dev(self.h, vals_ptr, rows, length, stride, dst_ptr, dst_cap,
+                                                _ptr(rb, _u64p), stream))
+        return rb[:rows]
+
     def snapshot_transpose_dev(self, src_ptr, part_off, n_participations, n_clerks, dst_ptr=None, dst_cap=0,
                                stream=None):
         """AggregationsStore::iter_snapshot_clerk_jobs_data (server/src/stores.rs:86-101) on device.
@@ -594,4 +606,18 @@ class Engine:
         _check(self.lib.sda_participant_share_dev(self.h, C.byref(ms), _ptr(sd, _u32p), sd.size, full_masks_ptr,
                                                   C.byref(ss), secrets_ptr, dimension, draws_ptr, mode, shares_ptr,
                                                   payload_ptr, payload_cap, _ptr(rb, _u64p), stream))
+        return rb[:n]
+
+    def participant_share32_dev(self, masking, sharing, secrets_ptr, dimension, draws_ptr, shares_ptr, seed=None,
+                                full_masks_ptr=None, payload_ptr=None, payload_cap=0, mode=REVEAL_EXACT,
+                                stream=None):
+        """participant_share_dev with shares_ptr as device int32 [n][B] (PackedShamir only) and the payload from
+        the int32 encoder; returns per-clerk payload byte counts."""
+        ms, ss = masking.c(), sharing.c()
+        sd = _arr(seed if seed is not None else [], np.uint32)
+        n = sharing.output_size()
+        rb = np.zeros(max(n, 1), np.uint64)
+        _check(self.lib.sda_participant_share32_dev(self.h, C.byref(ms), _ptr(sd, _u32p), sd.size, full_masks_ptr,
+                                                    C.byref(ss), secrets_ptr, dimension, draws_ptr, mode,
+                                                    shares_ptr, payload_ptr, payload_cap, _ptr(rb, _u64p), stream))
         return rb[:n]
