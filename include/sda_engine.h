@@ -268,6 +268,34 @@ sda_status sda_chacha_last_launch(sda_engine* h, uint32_t* path, uint64_t* grid_
 sda_status sda_codec_last_launch(sda_engine* h, uint32_t* path, uint32_t* width, uint32_t* fell_back,
                                  uint64_t* passes);
 
+/* Diagnostic (read-only): which share-combine kernel the handle launched most recently and on what grid -- by any
+ * entry point that ends in one: sda_combine_dev / sda_combine32_dev and their _accumulate forms, sda_combine_split_dev,
+ * sda_combine_split_replay_dev, the host entry points' streamed tiles (the last tile's launch), the matrix paths of
+ * the clerk's decode -> combine, the recipient pipeline.  A call that launches nothing (dim == 0, an accumulate,
+ * split or replay with n == 0) leaves the record, and so does a launch the runtime refuses (the call then returns
+ * SDA_ERR_DEVICE).  The ChaCha stream path's internal combine is not recorded here (sda_chacha_last_launch describes
+ * that launch).
+ *   kind        0  no combine launch yet
+ *               1  combine_exact_kernel
+ *               2  combine_replay_kernel (pass 2 of the participation split)
+ *   elem_bytes  the row element: 8 (i64) or 4 (int32)
+ *   vec         columns per lane: 1, 2 or 4 -- the widest the column count, row stride and pointers line up for
+ *   rows        rows loaded per batch: 2, 4 or 8
+ *   variant     bits: 1  m <= 2^62 (the kernel without the wrapping-add slow path)
+ *                     2  continues from the output's values (accumulate, split)
+ *                     4  raises the participation split's flags
+ *                     8  software-pipelined (off with SDA_COMBINE_PIPE=0)
+ *   grid        workgroups launched
+ *   wlo, nwide  the balanced grid: every workgroup owns wlo lanes, the first nwide of them 8 more; 0, 0 on the plain
+ *               grid of 256-lane workgroups
+ *   per_cu      resident workgroups per CU the runtime reported for the kernel, as handed to the balanced grid's
+ *               sizing; 0 when that grid was not considered (a kernel that is not pipelined, SDA_COMBINE_BALANCE=0)
+ * A host-side record: nothing is waited for or copied.  A multi-device handle reports its first device's record.
+ * No pointer may be NULL. */
+sda_status sda_combine_last_launch(sda_engine* h, uint32_t* kind, uint32_t* elem_bytes, uint32_t* vec, uint32_t* rows,
+                                   uint32_t* variant, uint64_t* grid, uint32_t* wlo, uint32_t* nwide,
+                                   uint32_t* per_cu);
+
 /* Multi-GPU finalize: `sums` are the int64 sums (RCCL-reduced; |sum| <= 2^63 - 1, signed allowed)
  * of per-GPU combine results; out = their canonical residue in [0, m).  Exact w.r.t. the reference
  * when all combined inputs were non-negative. */

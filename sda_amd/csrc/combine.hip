@@ -177,10 +177,12 @@ bool combine_grid(int per_cu, uint64_t n_lanes, uint64_t* G, uint32_t* wlo, uint
 
 template <typename T, int VEC, int UNROLL, bool ACC, bool FLAG = false, bool PIPE = false>
 hipError_t launch_vec(const T* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* out,
-                      const Mod64& M, bool small_m, hipStream_t s, int64_t* flags = nullptr) {
+                      const Mod64& M, bool small_m, hipStream_t s, CombineLaunchInfo* info,
+                      int64_t* flags = nullptr) {
     const uint64_t n_lanes = dim / VEC;
     uint64_t blocks = (n_lanes + 255) / 256;
     uint32_t wlo = 0, nwide = 0;
+    int per_cu = 0;
     if (PIPE && combine_balance()) {
         // resident workgroups per CU of this instantiation (the same on every MI355X): queried once
         static const int per_cu_small = [] {
@@ -196,7 +198,8 @@ hipError_t launch_vec(const T* in, uint64_t n, uint64_t dim, uint64_t stride, in
                        256, 0) == hipSuccess ? v : 0;
         }();
         uint64_t g;
-        if (combine_grid(small_m ? per_cu_small : per_cu_big, n_lanes, &g, &wlo, &nwide)) blocks = g;
+        per_cu = small_m ? per_cu_small : per_cu_big;
+        if (combine_grid(per_cu, n_lanes, &g, &wlo, &nwide)) blocks = g;
         else wlo = nwide = 0;
     }
     if (small_m)
@@ -205,7 +208,20 @@ hipError_t launch_vec(const T* in, uint64_t n, uint64_t dim, uint64_t stride, in
     else
         hipLaunchKernelGGL((combine_exact_kernel<T, VEC, UNROLL, false, ACC, FLAG, PIPE>), dim3((unsigned)blocks),
                            dim3(256), 0, s, in, n, n_lanes, stride, out, M, flags, wlo, nwide);
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (info && e == hipSuccess) {               // the instantiation and grid as decided here (sda_combine_last_launch)
+        info->kind = kCombineExact;
+        info->elem_bytes = (uint32_t)sizeof(T);
+        info->vec = VEC;
+        info->rows = UNROLL;
+        info->variant = (small_m ? kCombineSmallM : 0u) | (ACC ? kCombineAcc : 0u) | (FLAG ? kCombineFlag : 0u) |
+                        (PIPE ? kCombinePipe : 0u);
+        info->grid = blocks;
+        info->wlo = wlo;
+        info->nwide = nwide;
+        info->per_cu = (uint32_t)(per_cu > 0 ? per_cu : 0);
+    }
+    return e;
 }
 
 // The i64 kernels run software-pipelined, two buffers of 4 rows (PIPE): one process, one 80 GB buffer, the
@@ -338,7 +354,8 @@ __global__ __launch_bounds__(256) void split_resolve_kernel(const int64_t* __res
 }  // namespace
 
 hipError_t launch_combine_exact(const int64_t* in, uint64_t n, uint64_t dim, uint64_t stride,
-                                int64_t* out, int64_t modulus, hipStream_t s, bool accumulate) {
+                                int64_t* out, int64_t modulus, hipStream_t s, bool accumulate,
+                                CombineLaunchInfo* info) {
     if (dim == 0) return hipSuccess;
     const Mod64 M = make_mod64(modulus);
     const bool small_m = modulus <= ((int64_t)1 << 62);
@@ -347,30 +364,31 @@ hipError_t launch_combine_exact(const int64_t* in, uint64_t n, uint64_t dim, uin
     const bool v2 = dim % 2 == 0 && stride % 2 == 0 && (a % 16) == 0;
     const bool pipe = v2 && combine_pipe();
     if (accumulate) {
-        if (pipe) return launch_vec<int64_t, 2, 4, true, false, true>(in, n, dim, stride, out, M, small_m, s);
-        return v2 ? launch_vec<int64_t, 2, 8, true>(in, n, dim, stride, out, M, small_m, s)
-                  : launch_vec<int64_t, 1, 8, true>(in, n, dim, stride, out, M, small_m, s);
+        if (pipe) return launch_vec<int64_t, 2, 4, true, false, true>(in, n, dim, stride, out, M, small_m, s, info);
+        return v2 ? launch_vec<int64_t, 2, 8, true>(in, n, dim, stride, out, M, small_m, s, info)
+                  : launch_vec<int64_t, 1, 8, true>(in, n, dim, stride, out, M, small_m, s, info);
     }
-    if (pipe) return launch_vec<int64_t, 2, 4, false, false, true>(in, n, dim, stride, out, M, small_m, s);
-    return v2 ? launch_vec<int64_t, 2, 8, false>(in, n, dim, stride, out, M, small_m, s)
-              : launch_vec<int64_t, 1, 8, false>(in, n, dim, stride, out, M, small_m, s);
+    if (pipe) return launch_vec<int64_t, 2, 4, false, false, true>(in, n, dim, stride, out, M, small_m, s, info);
+    return v2 ? launch_vec<int64_t, 2, 8, false>(in, n, dim, stride, out, M, small_m, s, info)
+              : launch_vec<int64_t, 1, 8, false>(in, n, dim, stride, out, M, small_m, s, info);
 }
 
 hipError_t launch_combine_split(const int64_t* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* inout,
-                                int64_t modulus, int64_t* flags, hipStream_t s) {
+                                int64_t modulus, int64_t* flags, hipStream_t s, CombineLaunchInfo* info) {
     if (dim == 0 || n == 0) return hipSuccess;
     const Mod64 M = make_mod64(modulus);
     const bool small_m = modulus <= ((int64_t)1 << 62);
     const uintptr_t a = (uintptr_t)in | (uintptr_t)inout;
     const bool v2 = dim % 2 == 0 && stride % 2 == 0 && (a % 16) == 0;
     if (v2 && combine_pipe())
-        return launch_vec<int64_t, 2, 4, true, true, true>(in, n, dim, stride, inout, M, small_m, s, flags);
-    return v2 ? launch_vec<int64_t, 2, 8, true, true>(in, n, dim, stride, inout, M, small_m, s, flags)
-              : launch_vec<int64_t, 1, 8, true, true>(in, n, dim, stride, inout, M, small_m, s, flags);
+        return launch_vec<int64_t, 2, 4, true, true, true>(in, n, dim, stride, inout, M, small_m, s, info, flags);
+    return v2 ? launch_vec<int64_t, 2, 8, true, true>(in, n, dim, stride, inout, M, small_m, s, info, flags)
+              : launch_vec<int64_t, 1, 8, true, true>(in, n, dim, stride, inout, M, small_m, s, info, flags);
 }
 
 hipError_t launch_combine_replay(const int64_t* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* state,
-                                 int32_t* code, int32_t reset_code, int64_t modulus, hipStream_t s) {
+                                 int32_t* code, int32_t reset_code, int64_t modulus, hipStream_t s,
+                                 CombineLaunchInfo* info) {
     if (dim == 0 || n == 0) return hipSuccess;
     const Mod64 M = make_mod64(modulus);
     const bool small_m = modulus <= ((int64_t)1 << 62);
@@ -386,7 +404,17 @@ hipError_t launch_combine_replay(const int64_t* in, uint64_t n, uint64_t dim, ui
         if (small_m) hipLaunchKernelGGL((combine_replay_kernel<1, 8, true>), grid, dim3(256), 0, s, in, n, n_lanes, stride, state, code, reset_code, M);
         else hipLaunchKernelGGL((combine_replay_kernel<1, 8, false>), grid, dim3(256), 0, s, in, n, n_lanes, stride, state, code, reset_code, M);
     }
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (info && e == hipSuccess) {               // the replay kernel's own choice (sda_combine_last_launch)
+        *info = CombineLaunchInfo();
+        info->kind = kCombineReplay;
+        info->elem_bytes = 8;
+        info->vec = (uint32_t)vec;
+        info->rows = 8;
+        info->variant = small_m ? kCombineSmallM : 0u;
+        info->grid = grid.x;
+    }
+    return e;
 }
 
 hipError_t launch_split_prefix(const int64_t* gathered, uint64_t world, uint64_t rank, uint64_t dim, int64_t* c_in,
@@ -411,13 +439,14 @@ namespace {
 // SDA_COMBINE32_VEC=4 (A/B knob), 4 (16-byte loads, half the lanes); unpipelined, 8 rows per batch
 template <bool ACC>
 hipError_t combine32_narrow_lanes(const int32_t* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* out,
-                                  const Mod64& M, bool small_m, hipStream_t s, bool want4) {
+                                  const Mod64& M, bool small_m, hipStream_t s, bool want4,
+                                  CombineLaunchInfo* info) {
     const uintptr_t a = (uintptr_t)in, o = (uintptr_t)out;
     if (want4 && dim % 4 == 0 && stride % 4 == 0 && a % 16 == 0 && o % 32 == 0)
-        return launch_vec<int32_t, 4, 8, ACC>(in, n, dim, stride, out, M, small_m, s);
+        return launch_vec<int32_t, 4, 8, ACC>(in, n, dim, stride, out, M, small_m, s, info);
     const bool v2 = dim % 2 == 0 && stride % 2 == 0 && a % 8 == 0 && o % 16 == 0;
-    return v2 ? launch_vec<int32_t, 2, 8, ACC>(in, n, dim, stride, out, M, small_m, s)
-              : launch_vec<int32_t, 1, 8, ACC>(in, n, dim, stride, out, M, small_m, s);
+    return v2 ? launch_vec<int32_t, 2, 8, ACC>(in, n, dim, stride, out, M, small_m, s, info)
+              : launch_vec<int32_t, 1, 8, ACC>(in, n, dim, stride, out, M, small_m, s, info);
 }
 
 // The int32 share rows of the public entry points (sda_combine32_dev, the half-width host stream): 4 columns
@@ -431,13 +460,13 @@ hipError_t combine32_narrow_lanes(const int32_t* in, uint64_t n, uint64_t dim, u
 constexpr int kWide32Rows = 2;
 template <bool ACC>
 hipError_t combine32_wide_lanes(const int32_t* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* out,
-                                const Mod64& M, bool small_m, hipStream_t s) {
+                                const Mod64& M, bool small_m, hipStream_t s, CombineLaunchInfo* info) {
     const char* env = getenv("SDA_COMBINE32_VEC");
     const bool want4 = !(env && atoi(env) == 2);
     const uintptr_t a = (uintptr_t)in, o = (uintptr_t)out;
     if (want4 && combine_pipe() && dim % 4 == 0 && stride % 4 == 0 && a % 16 == 0 && o % 32 == 0)
-        return launch_vec<int32_t, 4, kWide32Rows, ACC, false, true>(in, n, dim, stride, out, M, small_m, s);
-    return combine32_narrow_lanes<ACC>(in, n, dim, stride, out, M, small_m, s, want4);
+        return launch_vec<int32_t, 4, kWide32Rows, ACC, false, true>(in, n, dim, stride, out, M, small_m, s, info);
+    return combine32_narrow_lanes<ACC>(in, n, dim, stride, out, M, small_m, s, want4, info);
 }
 
 // dst = (int32_t)src over [n][dim] (row strides in elements); flag[0] = 1 when a value does not fit (every
@@ -482,23 +511,24 @@ __global__ __launch_bounds__(256) void narrow32_kernel(const int64_t* __restrict
 }  // namespace
 
 hipError_t launch_combine_exact32(const int32_t* in, uint64_t n, uint64_t dim, uint64_t stride,
-                                  int64_t* out, int64_t modulus, hipStream_t s, bool accumulate) {
+                                  int64_t* out, int64_t modulus, hipStream_t s, bool accumulate,
+                                  CombineLaunchInfo* info) {
     if (dim == 0) return hipSuccess;
     const Mod64 M = make_mod64(modulus);
     const bool small_m = modulus <= ((int64_t)1 << 62);
     const char* env = getenv("SDA_COMBINE32_VEC");
     const bool want4 = env && atoi(env) == 4;
-    return accumulate ? combine32_narrow_lanes<true>(in, n, dim, stride, out, M, small_m, s, want4)
-                      : combine32_narrow_lanes<false>(in, n, dim, stride, out, M, small_m, s, want4);
+    return accumulate ? combine32_narrow_lanes<true>(in, n, dim, stride, out, M, small_m, s, want4, info)
+                      : combine32_narrow_lanes<false>(in, n, dim, stride, out, M, small_m, s, want4, info);
 }
 
 hipError_t launch_combine_wide32(const int32_t* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* out,
-                                 int64_t modulus, hipStream_t s, bool accumulate) {
+                                 int64_t modulus, hipStream_t s, bool accumulate, CombineLaunchInfo* info) {
     if (dim == 0) return hipSuccess;
     const Mod64 M = make_mod64(modulus);
     const bool small_m = modulus <= ((int64_t)1 << 62);
-    return accumulate ? combine32_wide_lanes<true>(in, n, dim, stride, out, M, small_m, s)
-                      : combine32_wide_lanes<false>(in, n, dim, stride, out, M, small_m, s);
+    return accumulate ? combine32_wide_lanes<true>(in, n, dim, stride, out, M, small_m, s, info)
+                      : combine32_wide_lanes<false>(in, n, dim, stride, out, M, small_m, s, info);
 }
 
 hipError_t launch_narrow32(const int64_t* src, uint64_t n, uint64_t dim, uint64_t src_stride, int32_t* dst,

@@ -59,6 +59,9 @@ struct sda_engine {
     bool chacha_split = false;
     // sda_codec_last_launch: how the last decode -> combine on this handle produced its result (decode_combine)
     sda::CodecLaunchInfo codec_last;
+    // sda_combine_last_launch: which combine kernel this handle (of a multi-device handle: this device) launched
+    // last and on what grid, filled by the launcher where it decides; a call that launches nothing leaves it
+    sda::CombineLaunchInfo combine_last;
     // streaming host path (host rows -> HBM in row tiles, host_path section): pinned staging and device
     // tiles, double buffered, and a copy stream so a tile's upload overlaps the previous tile's combine
     hipStream_t copy_stream = nullptr;
@@ -751,7 +754,8 @@ sda_status sda_combine_dev(sda_engine* h, int64_t modulus, const int64_t* shares
     int64_t m;
     if (sda_status st = modulus_abs(modulus, &m)) return st;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(sda::launch_combine_exact(shares, n, dim, n > 1 ? row_stride : dim, out, m, pick(h, stream)));
+    HIP_TRY(sda::launch_combine_exact(shares, n, dim, n > 1 ? row_stride : dim, out, m, pick(h, stream), false,
+                                      &h->combine_last));
     return ok();
 }
 
@@ -764,7 +768,8 @@ sda_status sda_combine_accumulate_dev(sda_engine* h, int64_t modulus, const int6
     if (sda_status st = modulus_abs(modulus, &m)) return st;
     HIP_TRY(hipSetDevice(h->device));
     if (n == 0) return ok();
-    HIP_TRY(sda::launch_combine_exact(shares, n, dim, n > 1 ? row_stride : dim, inout, m, pick(h, stream), true));
+    HIP_TRY(sda::launch_combine_exact(shares, n, dim, n > 1 ? row_stride : dim, inout, m, pick(h, stream), true,
+                                      &h->combine_last));
     return ok();
 }
 
@@ -778,7 +783,8 @@ sda_status sda_combine32_dev(sda_engine* h, int64_t modulus, const int32_t* shar
     int64_t m;
     if (sda_status st = modulus_abs(modulus, &m)) return st;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(sda::launch_combine_wide32(shares, n, dim, n > 1 ? row_stride : dim, out, m, pick(h, stream)));
+    HIP_TRY(sda::launch_combine_wide32(shares, n, dim, n > 1 ? row_stride : dim, out, m, pick(h, stream), false,
+                                       &h->combine_last));
     return ok();
 }
 
@@ -791,7 +797,8 @@ sda_status sda_combine32_accumulate_dev(sda_engine* h, int64_t modulus, const in
     if (sda_status st = modulus_abs(modulus, &m)) return st;
     HIP_TRY(hipSetDevice(h->device));
     if (n == 0) return ok();
-    HIP_TRY(sda::launch_combine_wide32(shares, n, dim, n > 1 ? row_stride : dim, inout, m, pick(h, stream), true));
+    HIP_TRY(sda::launch_combine_wide32(shares, n, dim, n > 1 ? row_stride : dim, inout, m, pick(h, stream), true,
+                                       &h->combine_last));
     return ok();
 }
 
@@ -877,6 +884,27 @@ sda_status sda_codec_last_launch(sda_engine* h, uint32_t* path, uint32_t* width,
     return ok();
 }
 
+sda_status sda_combine_last_launch(sda_engine* h, uint32_t* kind, uint32_t* elem_bytes, uint32_t* vec, uint32_t* rows,
+                                   uint32_t* variant, uint64_t* grid, uint32_t* wlo, uint32_t* nwide,
+                                   uint32_t* per_cu) {
+    SDA_ENTRY;
+    if (!h || !kind || !elem_bytes || !vec || !rows || !variant || !grid || !wlo || !nwide || !per_cu)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    // a host-side record, final when the call that made it returned: nothing to wait for.  A multi-device handle
+    // is its own first device (sub[0]): its record is that device's
+    const sda::CombineLaunchInfo& c = h->combine_last;
+    *kind = c.kind;
+    *elem_bytes = c.elem_bytes;
+    *vec = c.vec;
+    *rows = c.rows;
+    *variant = c.variant;
+    *grid = c.grid;
+    *wlo = c.wlo;
+    *nwide = c.nwide;
+    *per_cu = c.per_cu;
+    return ok();
+}
+
 sda_status sda_combine_finalize_dev(sda_engine* h, int64_t modulus, const int64_t* sums, uint64_t dim, int64_t* out,
                                     void* stream) {
     SDA_ENTRY;
@@ -896,7 +924,8 @@ sda_status sda_combine_split_dev(sda_engine* h, int64_t modulus, const int64_t* 
     int64_t m;
     if (sda_status st = modulus_abs(modulus, &m)) return st;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(sda::launch_combine_split(shares, n, dim, n > 1 ? row_stride : dim, inout, m, flags, pick(h, stream)));
+    HIP_TRY(sda::launch_combine_split(shares, n, dim, n > 1 ? row_stride : dim, inout, m, flags, pick(h, stream),
+                                      &h->combine_last));
     return ok();
 }
 
@@ -927,7 +956,7 @@ sda_status sda_combine_split_replay_dev(sda_engine* h, int64_t modulus, const in
     if (sda_status st = modulus_abs(modulus, &m)) return st;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(sda::launch_combine_replay(shares, n, dim, n > 1 ? row_stride : dim, state, code, (int32_t)(2 * rank + 1),
-                                       m, pick(h, stream)));
+                                       m, pick(h, stream), &h->combine_last));
     return ok();
 }
 
@@ -1585,7 +1614,7 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
         HIP_TRY(sda::launch_varint_decode_narrow(bytes, n_blobs, plan, h->codec_work, mat32, dim, &wide, st,
                                                  &info));
         if (!wide) {
-            HIP_TRY(sda::launch_combine_exact32(mat32, n_blobs, dim, dim, out, mm, st));
+            HIP_TRY(sda::launch_combine_exact32(mat32, n_blobs, dim, dim, out, mm, st, false, &h->combine_last));
             info.path = sda::kCodecMatrix32;
             h->codec_last = info;
             return SDA_OK;
@@ -1594,7 +1623,7 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
     }
     int64_t* mat = static_cast<int64_t*>(h->codec_mat);
     HIP_TRY(sda::launch_varint_decode(bytes, n_blobs, plan, h->codec_work, mat, dim, dim, irregular, st, &info));
-    HIP_TRY(sda::launch_combine_exact(mat, n_blobs, dim, dim, out, mm, st));
+    HIP_TRY(sda::launch_combine_exact(mat, n_blobs, dim, dim, out, mm, st, false, &h->combine_last));
     info.path = sda::kCodecMatrix64;
     h->codec_last = info;
     return SDA_OK;
@@ -1883,7 +1912,8 @@ sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const
     // 1. masks (receive.rs:101-117)
     if (ms->kind == SDA_MASKING_FULL) {
         if (sda_status e = modulus_abs(ms->modulus, &q)) return e;
-        HIP_TRY(sda::launch_combine_exact(static_cast<const int64_t*>(mask_in), n_masks, D, mask_width, dmask, q, st));
+        HIP_TRY(sda::launch_combine_exact(static_cast<const int64_t*>(mask_in), n_masks, D, mask_width, dmask, q, st,
+                                          false, &h->combine_last));
     }
     PendingChacha pc;                                       // ChaCha: its rejection count is checked at the end
     if (ms->kind == SDA_MASKING_CHACHA) {
@@ -1895,7 +1925,7 @@ sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const
     if (!packed) {
         int64_t m;
         if (sda_status e = modulus_abs(ss->modulus, &m)) return e;
-        HIP_TRY(sda::launch_combine_exact(shares, n_idx, D, share_len, dmasked, m, st));
+        HIP_TRY(sda::launch_combine_exact(shares, n_idx, D, share_len, dmasked, m, st, false, &h->combine_last));
     } else {
         const int64_t* src = shares;
         if (compact) {                                      // batched.rs:83-85 reads [clerk][0..B)
@@ -2304,9 +2334,9 @@ sda_status stream_combine_slice(sda_engine* h, int64_t m, const int64_t* const* 
             HIP_TRY(hipStreamWaitEvent(h->stream, h->h2d_done[b], 0));
             if (try32)
                 HIP_TRY(sda::launch_combine_wide32(reinterpret_cast<const int32_t*>(dt[b]), Ri, wc, wc, acc, m,
-                                                   h->stream, i > 0));
+                                                   h->stream, i > 0, &h->combine_last));
             else
-                HIP_TRY(sda::launch_combine_exact(dt[b], Ri, wc, wc, acc, m, h->stream, i > 0));
+                HIP_TRY(sda::launch_combine_exact(dt[b], Ri, wc, wc, acc, m, h->stream, i > 0, &h->combine_last));
             HIP_TRY(hipEventRecord(h->tile_free[b], h->stream));
             ++(try32 ? h->hs_tiles32 : h->hs_tiles64);
             h->hs_bytes_h2d += bytes;
@@ -2590,7 +2620,8 @@ sda_status host_decode_combine(sda_engine* h, int64_t m, const uint8_t* const* b
             if (counts[i] != dim)
                 return fail(SDA_ERR_WRONG_DIMENSION, "Wrong dimension (participation %llu decodes to %llu shares, expected %llu)",
                             (unsigned long long)(g.b0 + i), (unsigned long long)counts[i], (unsigned long long)dim);
-        if (dim) HIP_TRY(sda::launch_combine_exact(mat, g.nb, dim, stride, acc, mm, h->stream, gi > 0));
+        if (dim)
+            HIP_TRY(sda::launch_combine_exact(mat, g.nb, dim, stride, acc, mm, h->stream, gi > 0, &h->combine_last));
         if (gi == 0) stride = std::max<uint64_t>(dim, 1);            // later groups: rows of exactly dim values
     }
     if (dim) HIP_TRY(hipMemcpyAsync(out, acc, dim * 8, hipMemcpyDeviceToHost, h->stream));

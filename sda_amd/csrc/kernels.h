@@ -11,18 +11,49 @@
 namespace sda {
 
 // ---- combine.hip ----
+// Which combine kernel a launch ran and on what grid (sda_combine_last_launch reports the handle's last one).
+// Filled where each decision is taken: launch_vec for the combine_exact_kernel instantiation and its grid, the
+// replay launcher for its own, each once the runtime has accepted the launch.  A launcher that launches nothing
+// (dim == 0; the split and replay with n == 0) or whose launch is refused leaves *info untouched.  Every call site in engine.cpp passes the handle's record; chacha.hip's stream path
+// (launch_chacha_streams_combine) passes none: its combine is part of a ChaCha launch, which
+// sda_chacha_last_launch describes.
+enum CombineKind : uint32_t {
+    kCombineNone = 0,         // no combine launch yet
+    kCombineExact = 1,        // combine_exact_kernel
+    kCombineReplay = 2,       // combine_replay_kernel
+};
+enum CombineVariant : uint32_t {  // the kernels' bool template arguments
+    kCombineSmallM = 1,       // SMALL_M: m <= 2^62
+    kCombineAcc = 2,          // ACC: continues from `out`
+    kCombineFlag = 4,         // FLAG: pass 1 of the participation split
+    kCombinePipe = 8,         // PIPE: software-pipelined
+};
+struct CombineLaunchInfo {
+    uint32_t kind = kCombineNone;
+    uint32_t elem_bytes = 0;  // 8 (i64 rows) or 4 (int32 rows)
+    uint32_t vec = 0;         // columns per lane: 1, 2 or 4
+    uint32_t rows = 0;        // rows per batch (the UNROLL argument): 2, 4 or 8
+    uint32_t variant = 0;     // CombineVariant bits
+    uint64_t grid = 0;        // workgroups launched
+    uint32_t wlo = 0;         // balanced grid (combine_grid): lanes per workgroup, + 8 in the first nwide ones;
+    uint32_t nwide = 0;       // 0, 0 on the plain grid of 256-lane workgroups
+    uint32_t per_cu = 0;      // the occupancy handed to combine_grid; 0 when the balanced grid was not considered
+};
 // Exact clerk combine: out[j] = fold over rows of (r + v) % m  (combiner.rs:22-25).
 // accumulate: continue from the values in `out` (a previous result, |r| < m) instead of 0.
 hipError_t launch_combine_exact(const int64_t* in, uint64_t n, uint64_t dim, uint64_t stride,
-                                int64_t* out, int64_t modulus, hipStream_t s, bool accumulate = false);
+                                int64_t* out, int64_t modulus, hipStream_t s, bool accumulate = false,
+                                CombineLaunchInfo* info = nullptr);
 // The same recurrence over int32 rows (decoded field shares: the clerk's decode -> combine).
 hipError_t launch_combine_exact32(const int32_t* in, uint64_t n, uint64_t dim, uint64_t stride,
-                                  int64_t* out, int64_t modulus, hipStream_t s, bool accumulate = false);
+                                  int64_t* out, int64_t modulus, hipStream_t s, bool accumulate = false,
+                                  CombineLaunchInfo* info = nullptr);
 // int32 share rows as an input type of the combine (sda_combine32_dev, the half-width host stream): 16-byte
 // loads (4 columns per lane), software-pipelined on the balanced grid where the rows line up, else the
 // kernels above.  Sign-extends and runs the i64 recurrence: exact for every modulus.
 hipError_t launch_combine_wide32(const int32_t* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* out,
-                                 int64_t modulus, hipStream_t s, bool accumulate = false);
+                                 int64_t modulus, hipStream_t s, bool accumulate = false,
+                                 CombineLaunchInfo* info = nullptr);
 // dst[n][dim] (int32, row stride dst_stride) = (int32_t)src[n][dim] (row stride src_stride); flag[0] = 1 when
 // a value lies outside int32 (never cleared).
 hipError_t launch_narrow32(const int64_t* src, uint64_t n, uint64_t dim, uint64_t src_stride, int32_t* dst,
@@ -33,11 +64,12 @@ hipError_t launch_mod_canonical(const int64_t* sums, uint64_t dim, int64_t* out,
 // Participation split.  Pass 1: the exact recurrence continued from inout that also sets
 // flags[0] = 1 (an input < 0) / flags[1] = 1 (an input outside [-(2^63 - m), 2^63 - m]).
 hipError_t launch_combine_split(const int64_t* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* inout,
-                                int64_t modulus, int64_t* flags, hipStream_t s);
+                                int64_t modulus, int64_t* flags, hipStream_t s, CombineLaunchInfo* info = nullptr);
 // Pass 2 (signed inputs): replay the canonical trajectory from state (c_in), recording the last sign
 // event in code (reset_code = 2 rank + 1 on a reset, + 1 on a set; unchanged without an event).
 hipError_t launch_combine_replay(const int64_t* in, uint64_t n, uint64_t dim, uint64_t stride, int64_t* state,
-                                 int32_t* code, int32_t reset_code, int64_t modulus, hipStream_t s);
+                                 int32_t* code, int32_t reset_code, int64_t modulus, hipStream_t s,
+                                 CombineLaunchInfo* info = nullptr);
 hipError_t launch_split_prefix(const int64_t* gathered, uint64_t world, uint64_t rank, uint64_t dim, int64_t* c_in,
                                int64_t* total, int32_t* code, int64_t modulus, hipStream_t s);
 hipError_t launch_split_resolve(const int64_t* total, const int32_t* code, uint64_t dim, int64_t* out,

@@ -15,6 +15,7 @@ Trait mirrors (reference: client/src/crypto/{sharing,masking}/mod.rs):
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import sys
@@ -65,6 +66,17 @@ CODEC_FB_FUSED_IRREGULAR = 2
 CODEC_FB_NARROW_WIDE = 4
 CODEC_FB_SEQUENTIAL = 8
 
+# sda_combine_last_launch's kind codes and variant bits
+COMBINE_NONE = 0
+COMBINE_EXACT = 1
+COMBINE_REPLAY = 2
+COMBINE_SMALL_M = 1
+COMBINE_ACC = 2
+COMBINE_FLAG = 4
+COMBINE_PIPE = 8
+CombineLaunch = collections.namedtuple("CombineLaunch",
+                                       "kind elem_bytes vec rows variant grid wlo nwide per_cu")
+
 _i64p = C.POINTER(C.c_int64)
 _u64p = C.POINTER(C.c_uint64)
 _u32p = C.POINTER(C.c_uint32)
@@ -110,6 +122,7 @@ SIGNATURES = [
     ("sda_packed_fixup_count", _st, [_vp, _u64p]),
     ("sda_chacha_last_launch", _st, [_vp, _u32p, _u64p, _u64p]),
     ("sda_codec_last_launch", _st, [_vp, _u32p, _u32p, _u32p, _u64p]),
+    ("sda_combine_last_launch", _st, [_vp, _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, _u32p, _u32p, _u32p]),
     ("sda_combine_split_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     ("sda_combine_split_prefix_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp,
                                            _vp]),
@@ -476,6 +489,16 @@ class Engine:
         path, width, fb, passes = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
         _check(self.lib.sda_codec_last_launch(self.h, C.byref(path), C.byref(width), C.byref(fb), C.byref(passes)))
         return int(path.value), int(width.value), int(fb.value), int(passes.value)
+
+    def combine_last_launch(self):
+        """CombineLaunch(kind, elem_bytes, vec, rows, variant, grid, wlo, nwide, per_cu) of the handle's last
+        share-combine launch: kind is one of the COMBINE_* codes, vec the columns per lane, rows the rows per batch,
+        variant the COMBINE_SMALL_M / _ACC / _FLAG / _PIPE bits, (grid, wlo, nwide) the workgroups and the balanced
+        grid's widths (0, 0 on the plain grid), per_cu the occupancy that grid was sized with
+        (sda_combine_last_launch)."""
+        v = [C.c_uint32() for _ in range(5)] + [C.c_uint64()] + [C.c_uint32() for _ in range(3)]
+        _check(self.lib.sda_combine_last_launch(self.h, *[C.byref(x) for x in v]))
+        return CombineLaunch(*[int(x.value) for x in v])
 
     def combine_finalize_dev(self, modulus, sums_ptr, dim, out_ptr, stream=None):
         _check(self.lib.sda_combine_finalize_dev(self.h, modulus, sums_ptr, dim, out_ptr, stream))

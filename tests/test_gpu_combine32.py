@@ -98,11 +98,22 @@ def test_combine32_balanced_grid_and_pipe_knobs(engine, oracle, monkeypatch, D):
     xd = torch.from_numpy(x).cuda()
     exp = oracle.combine(P, x.astype(np.int64))
     assert_same(_combine32(engine, P, xd, N, D, D), exp, "default")
+    # the kernel and grid the ids name (sda_combine_last_launch): 1,048,588 columns line up for the pipelined
+    # 4-column kernel on the balanced grid; 100,003 is odd, which the 1-column kernel on the plain grid takes
+    wide = D % 4 == 0
+    rec = engine.combine_last_launch()
+    assert (rec.elem_bytes, rec.vec, rec.rows) == ((4, 4, 2) if wide else (4, 1, 8)), rec
+    assert bool(rec.variant & E.COMBINE_PIPE) == wide and (rec.wlo > 0) == wide and (rec.per_cu > 0) == wide, rec
     monkeypatch.setenv("SDA_COMBINE_BALANCE", "0")
     assert_same(_combine32(engine, P, xd, N, D, D), exp, "SDA_COMBINE_BALANCE=0")
+    rec = engine.combine_last_launch()
+    assert (rec.vec, rec.rows, rec.wlo, rec.nwide, rec.per_cu) == ((4, 2, 0, 0, 0) if wide else (1, 8, 0, 0, 0)), rec
     monkeypatch.delenv("SDA_COMBINE_BALANCE")
     monkeypatch.setenv("SDA_COMBINE_PIPE", "0")
     assert_same(_combine32(engine, P, xd, N, D, D), exp, "SDA_COMBINE_PIPE=0")
+    rec = engine.combine_last_launch()
+    assert (rec.vec, rec.rows, rec.wlo, rec.per_cu) == ((4, 8, 0, 0) if wide else (1, 8, 0, 0)), rec
+    assert not rec.variant & E.COMBINE_PIPE, rec
 
 
 # ---------------- sda_combine32_accumulate_dev ----------------

@@ -325,6 +325,8 @@ def test_participation_split_flags_on_the_balanced_grid(engine):
         return f.tolist(), acc
     f, acc = flags()
     assert f == [0, 0]
+    rec = engine.combine_last_launch()
+    assert rec.wlo > 0 and rec.variant & E.COMBINE_FLAG and rec.variant & E.COMBINE_PIPE, rec
     assert torch.equal(acc, torch.remainder(x.sum(dim=0), m))
     x[N - 1, D - 1] = (1 << 63) - m + 1     # just past the no-wrap range
     assert flags()[0] == [0, 1]
@@ -426,9 +428,14 @@ def test_combine_balanced_grid_widths(engine, oracle, monkeypatch, balance, dim)
     engine.synth_fill_dev(x.data_ptr(), N, dim, 0x5DA + dim, -(m - 1), m, _stream())
     out = torch.empty(dim, dtype=torch.int64, device="cuda")
     engine.combine_dev(m, x.data_ptr(), N, dim, dim, out.data_ptr(), _stream())
+    rec = engine.combine_last_launch()
     acc = x[0].clone()
     engine.combine_accumulate_dev(m, x[1].data_ptr(), N - 1, dim, dim, acc.data_ptr(), _stream())
+    rec_acc = engine.combine_last_launch()
     torch.cuda.synchronize()
+    # the grid the ids name (sda_combine_last_launch; tests/test_gpu_combine_matrix.py holds the exact geometry)
+    for r in (rec, rec_acc):
+        assert (r.wlo > 0) == (balance == "1") and (r.per_cu > 0) == (balance == "1"), r
     exp = oracle.combine(m, x.cpu().numpy())
     assert_same(out.cpu().numpy(), exp)
     assert_same(acc.cpu().numpy(), exp)
