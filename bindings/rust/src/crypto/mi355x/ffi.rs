@@ -81,6 +81,9 @@ extern "C" {
     // ---- trait mirrors (host buffers, synchronous) ----
     pub fn sda_share_generate(h: *mut SdaEngine, s: *const SdaSharingScheme, secrets: *const i64, dimension: u64,
                               draws: *const i64, n_draws: u64, out: *mut i64, out_cap: u64) -> SdaStatus;
+    pub fn sda_share_generate_keyed(h: *mut SdaEngine, s: *const SdaSharingScheme, secrets: *const i64,
+                                    dimension: u64, key: *const u32, stream_id: u32, out: *mut i64, out_cap: u64)
+                                    -> SdaStatus;
     pub fn sda_share_combine(h: *mut SdaEngine, s: *const SdaSharingScheme, rows: *const *const i64,
                              lens: *const u64, n_rows: u64, out: *mut i64, out_cap: u64, out_len: *mut u64)
                              -> SdaStatus;
@@ -90,6 +93,9 @@ extern "C" {
     pub fn sda_secret_mask(h: *mut SdaEngine, s: *const SdaMaskingScheme, secrets: *const i64, dimension: u64,
                            seed: *const u32, seed_words: u64, full_masks: *const i64, mask_out: *mut i64,
                            mask_cap: u64, mask_len: *mut u64, masked_out: *mut i64) -> SdaStatus;
+    pub fn sda_secret_mask_keyed(h: *mut SdaEngine, s: *const SdaMaskingScheme, secrets: *const i64, dimension: u64,
+                                 key: *const u32, stream_id: u32, mask_out: *mut i64, mask_cap: u64,
+                                 mask_len: *mut u64, masked_out: *mut i64) -> SdaStatus;
     pub fn sda_mask_combine(h: *mut SdaEngine, s: *const SdaMaskingScheme, rows: *const *const i64,
                             lens: *const u64, n_rows: u64, out: *mut i64, out_cap: u64, out_len: *mut u64)
                             -> SdaStatus;
@@ -153,6 +159,12 @@ extern "C" {
                                      -> SdaStatus;
     pub fn sda_chacha_mask_combine_dev(h: *mut SdaEngine, modulus: i64, dimension: u64, seeds: *const u32, w: u64,
                                        n_seeds: u64, out: *mut i64, stream: *mut c_void) -> SdaStatus;
+
+    // ---- device-side draws: one OS-RNG key per call, expanded with ChaCha20 on the device ----
+    pub fn sda_draws_dev(h: *mut SdaEngine, key: *const u32, stream_id: u32, first: u64, count: u64, bound: i64,
+                         out: *mut i64, stream: *mut c_void) -> SdaStatus;
+    pub fn sda_draws(h: *mut SdaEngine, key: *const u32, stream_id: u32, first: u64, count: u64, bound: i64,
+                     out: *mut i64, out_cap: u64) -> SdaStatus;
 
     // ---- share payload codec (sodium.rs:36-41, :82-88) ----
     pub fn sda_varint_encode(h: *mut SdaEngine, vals: *const i64, n: u64, out: *mut u8, out_cap: u64,

@@ -131,6 +131,17 @@ pub struct GpuSharing {
     scheme: LinearSecretSharingScheme,
     c: SdaSharingScheme,
     rng: OsRng,
+    device_draws: bool,
+}
+
+/// One 256-bit ChaCha20 key from the OS RNG: the whole randomness of one keyed engine call.  A key is read per
+/// call and never reused, which is the engine's (key, stream_id) contract (include/sda_engine.h).
+fn fresh_key(rng: &mut OsRng) -> [u32; 8] {
+    let mut key = [0_u32; 8];
+    for w in key.iter_mut() {
+        *w = rng.next_u32();
+    }
+    key
 }
 
 impl GpuSharing {
@@ -140,7 +151,17 @@ impl GpuSharing {
             scheme: scheme.clone(),
             c: sharing_c(scheme),
             rng: OsRng::new().expect("Unable to get randomness source"),
+            device_draws: false,
         }
+    }
+
+    /// Opt in to device-side draws: `generate` then reads 8 words from OsRng per call and the engine expands
+    /// them into the call's draws (sda_share_generate_keyed) instead of one OsRng read per draw on the host.
+    /// The draws are uniform on the same ranges and come from OS entropy, as the reference's do; the default
+    /// (off) keeps the per-draw host path.
+    pub fn device_draws(mut self, on: bool) -> GpuSharing {
+        self.device_draws = on;
+        self
     }
 
     /// The values the reference's RNG would draw for `dimension` secrets, in draw order:
@@ -165,13 +186,21 @@ impl ShareGenerator for GpuSharing {
     fn generate(&mut self, secrets: &[Secret]) -> SdaClientResult<Vec<Vec<Share>>> {
         let n = self.scheme.output_size();
         let len = unsafe { sda_share_length(&self.c, secrets.len() as u64) } as usize;
-        let draws = self.draws(secrets.len(), len);
         let mut flat = vec![0_i64; n * len];
         let c = self.c;
-        self.dev.call(|h| unsafe {
-            sda_share_generate(h, &c, secrets.as_ptr(), secrets.len() as u64, draws.as_ptr(), draws.len() as u64,
-                               flat.as_mut_ptr(), flat.len() as u64)
-        })?;
+        if self.device_draws {
+            let key = fresh_key(&mut self.rng);
+            self.dev.call(|h| unsafe {
+                sda_share_generate_keyed(h, &c, secrets.as_ptr(), secrets.len() as u64, key.as_ptr(), 0,
+                                         flat.as_mut_ptr(), flat.len() as u64)
+            })?;
+        } else {
+            let draws = self.draws(secrets.len(), len);
+            self.dev.call(|h| unsafe {
+                sda_share_generate(h, &c, secrets.as_ptr(), secrets.len() as u64, draws.as_ptr(),
+                                   draws.len() as u64, flat.as_mut_ptr(), flat.len() as u64)
+            })?;
+        }
         // [clerk][batch], batched.rs:25-28
         Ok((0..n).map(|j| flat[j * len..(j + 1) * len].to_vec()).collect())
     }
@@ -232,6 +261,7 @@ pub struct GpuMasker {
     scheme: LinearMaskingScheme,
     c: SdaMaskingScheme,
     rng: OsRng,
+    device_draws: bool,
 }
 
 impl GpuMasker {
@@ -241,12 +271,36 @@ impl GpuMasker {
             scheme: scheme.clone(),
             c: masking_c(scheme),
             rng: OsRng::new().expect("Unable to get randomness source"),
+            device_draws: false,
         }
+    }
+
+    /// Opt in to device-side draws for Full masking: `mask` then reads 8 words from OsRng per call and the
+    /// engine draws the mask (sda_secret_mask_keyed).  None and ChaCha draw nothing per element and are
+    /// unaffected; the default (off) keeps the per-draw host path.
+    pub fn device_draws(mut self, on: bool) -> GpuMasker {
+        self.device_draws = on;
+        self
     }
 }
 
 impl SecretMasker for GpuMasker {
     fn mask(&mut self, secrets: &[Secret]) -> (Vec<Mask>, Vec<MaskedSecret>) {
+        if let (true, &LinearMaskingScheme::Full { .. }) = (self.device_draws, &self.scheme) {
+            let key = fresh_key(&mut self.rng);
+            let mut mask = vec![0_i64; secrets.len()];
+            let mut masked = vec![0_i64; secrets.len()];
+            let mut mask_len = 0_u64;
+            let c = self.c;
+            self.dev
+                .call(|h| unsafe {
+                    sda_secret_mask_keyed(h, &c, secrets.as_ptr(), secrets.len() as u64, key.as_ptr(), 0,
+                                          mask.as_mut_ptr(), mask.len() as u64, &mut mask_len, masked.as_mut_ptr())
+                })
+                .expect("mask");
+            mask.truncate(mask_len as usize);
+            return (mask, masked);
+        }
         // the draws the reference makes: Full, one gen_range(0, m) per element (full.rs:25-27); ChaCha, the
         // ceil(bits / 32) seed words (chacha.rs:29-33)
         let (seed, full): (Vec<u32>, Vec<i64>) = match self.scheme {

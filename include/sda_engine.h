@@ -26,7 +26,8 @@
  *     masking, and the varint encode (row sizes), wait for their stream at the
  *     end of the call instead, so no GPU idle gap opens inside them.
  *   - Randomness is explicit.  Where the reference draws from OsRng the caller
- *     passes the drawn values (or, for ChaCha masking, the seed words).
+ *     passes the drawn values (or, for ChaCha masking, the seed words) -- or, through the `_keyed` entry
+ *     points and sda_draws_dev, one 256-bit OS-RNG key that the device expands into the draws.
  *   - Every function returns an sda_status; 0 = OK.  The codes 1..6 map 1:1 to
  *     the reference's error strings; sda_last_error_message() gives details.
  *   - A handle may be used from one thread at a time (the Rust trait objects
@@ -134,6 +135,18 @@ sda_status sda_share_generate(sda_engine* h, const sda_sharing_scheme* s,
                               const int64_t* draws, uint64_t n_draws,
                               int64_t* out, uint64_t out_cap);
 
+/* sda_share_generate with its draws made on the device (sda_draws_dev's rule, below) instead of passed in:
+ *   Additive:     draw [d][j] is element d*(n-1)+j, bound = modulus
+ *   PackedShamir: draw [b][j] is element b*t+j,     bound = prime_modulus - 1
+ * of (key, stream_id).  key: HOST, 8 words, fresh from the OS RNG for this call (see sda_draws_dev).  Every scheme
+ * check, status and the output layout are sda_share_generate's, and the result is identical to sda_share_generate
+ * fed with sda_draws of the same key, stream_id and bound.  On a multi-device handle the work splits as
+ * sda_share_generate's does and each device makes its own slice of the draws, so the result does not depend on
+ * the device count. */
+sda_status sda_share_generate_keyed(sda_engine* h, const sda_sharing_scheme* s, const int64_t* secrets,
+                                    uint64_t dimension, const uint32_t* key, uint32_t stream_id,
+                                    int64_t* out, uint64_t out_cap);
+
 /* ShareCombiner::combine  (sharing/mod.rs:23-25; combiner.rs:16-28)
  *   rows[i] has lens[i] elements (a Vec<Vec<i64>>).  out_len = lens[0] (0 if n_rows == 0). */
 sda_status sda_share_combine(sda_engine* h, const sda_sharing_scheme* s,
@@ -158,6 +171,16 @@ sda_status sda_secret_mask(sda_engine* h, const sda_masking_scheme* s,
                            const int64_t* full_masks,
                            int64_t* mask_out, uint64_t mask_cap, uint64_t* mask_len,
                            int64_t* masked_out);
+
+/* sda_secret_mask for Full masking with the mask drawn on the device: mask element d is element d of
+ * (key, stream_id) at bound = modulus (sda_draws_dev's rule); mask_out = those draws, *mask_len = dimension,
+ * masked_out = (secrets + mask) % modulus as full.rs:28-32.  key: HOST, 8 words, fresh from the OS RNG for this
+ * call.  Kinds None and ChaCha return SDA_ERR_INVALID_ARGUMENT (None draws nothing, ChaCha expands its own seed:
+ * use sda_secret_mask); a modulus <= 0 is SDA_ERR_PRECONDITION as in sda_secret_mask. */
+sda_status sda_secret_mask_keyed(sda_engine* h, const sda_masking_scheme* s, const int64_t* secrets,
+                                 uint64_t dimension, const uint32_t* key, uint32_t stream_id,
+                                 int64_t* mask_out, uint64_t mask_cap, uint64_t* mask_len,
+                                 int64_t* masked_out);
 
 /* MaskCombiner::combine  (masking/mod.rs:21-23)
  *   Full: rows are masks (full.rs:38-50); ChaCha: rows are seeds-as-i64 (chacha.rs:57-76);
@@ -387,6 +410,31 @@ sda_status sda_additive_generate_dev(sda_engine* h, int64_t modulus, uint64_t sh
 sda_status sda_chacha_mask_combine_dev(sda_engine* h, int64_t modulus, uint64_t dimension,
                                        const uint32_t* seeds, uint64_t w, uint64_t n_seeds,
                                        int64_t* out, void* stream);
+
+/* ---------------- device-side draws (DESIGN.md "Device draws") ----------------
+ * The reference draws every share-generation and Full-mask value from OsRng, one gen_range at a time.  These entry
+ * points expand one 256-bit key with ChaCha20 on the device instead.  Element i (an absolute 64-bit index), retry
+ * round r = 0, 1, ...:
+ *   state = "expand 32-byte k" | key[0..7] | (i >> 3) low word, high word | stream_id | r
+ *   o = ChaCha20 core(state) (20 rounds + feed-forward);  j = i & 7;  v = (o[2j] << 32) | o[2j+1]
+ *   zone = (2^64 - 1) - (2^64 - 1) % bound          (rand 0.3's gen_range rule, as the ChaCha mask kernels)
+ *   v < zone: the draw is v % bound; otherwise round r + 1 (same block counter and position); at r = 63 the
+ *   draw is v % bound unconditionally (reached with probability below 2^-64).
+ * An element depends only on (key, stream_id, i, bound): any sub-range, device split or launch shape gives the
+ * same values.  KEY CONTRACT: key is 8 words in HOST memory, fresh from the OS RNG; a (key, stream_id) pair must
+ * never serve two different jobs -- within one job, distinct element ranges or distinct stream_ids of one key are
+ * independent streams.  The key travels as a kernel argument and is never stored in device memory.
+ * Checks, in this order: a NULL handle, key or needed buffer -> SDA_ERR_INVALID_ARGUMENT; bound <= 0 ->
+ * SDA_ERR_PRECONDITION ("Rng.gen_range called with low >= high"); first + count wrapping past 2^64 ->
+ * SDA_ERR_INVALID_ARGUMENT; count == 0 -> SDA_OK, nothing launched.
+ *
+ * out[p] = draw(first + p), p < count, uniform on [0, bound).  out: device (8-byte aligned).  Only enqueues. */
+sda_status sda_draws_dev(sda_engine* h, const uint32_t* key, uint32_t stream_id, uint64_t first,
+                         uint64_t count, int64_t bound, int64_t* out, void* stream);
+/* The same into host memory (synchronous; the draws pass through the handle's staging scratch).  out_cap < count
+ * -> SDA_ERR_INVALID_ARGUMENT. */
+sda_status sda_draws(sda_engine* h, const uint32_t* key, uint32_t stream_id, uint64_t first,
+                     uint64_t count, int64_t bound, int64_t* out, uint64_t out_cap);
 
 /* ---------------- share payload codec ----------------
  * Encryptor::encrypt encodes shares with integer-encoding 1.0 VarInt before sealing

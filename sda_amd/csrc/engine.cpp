@@ -360,10 +360,15 @@ sda_status chacha_combine_multi(sda_engine* h, int64_t m, uint64_t D, const std:
 sda_status host_stream_ensure(sda_engine* h, size_t tile_bytes, size_t acc_bytes);
 sda_status host_decode_combine(sda_engine* h, int64_t m, const uint8_t* const* blobs, const uint64_t* lens, uint64_t n,
                                int64_t* out, uint64_t out_cap, uint64_t* out_len);
+// kd != nullptr (sda_share_generate_keyed): `draws` is NULL and every device makes its own slice of them
+struct KeyedDraws {
+    const uint32_t* key;          // host, 8 words
+    uint32_t stream_id;
+};
 sda_status host_additive_generate(sda_engine* h, int64_t m, uint64_t n, const int64_t* secrets, uint64_t D,
-                                  const int64_t* draws, int64_t* out);
+                                  const int64_t* draws, int64_t* out, const KeyedDraws* kd = nullptr);
 sda_status host_packed_generate(sda_engine* h, const sda_sharing_scheme* s, const int64_t* secrets, uint64_t D,
-                                const int64_t* draws, int64_t* out);
+                                const int64_t* draws, int64_t* out, const KeyedDraws* kd = nullptr);
 sda_status host_packed_reconstruct(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
                                    const uint64_t* indices, const int64_t* const* rows, uint64_t n_rows, int64_t* out);
 
@@ -523,6 +528,37 @@ sda_status sda_share_generate(sda_engine* h, const sda_sharing_scheme* s, const 
     return ok();
 }
 
+// sda_share_generate with its draws made on the device (draws.hip): every scheme check, status and output layout
+// of sda_share_generate; each device of a multi-device handle draws its own slice, so the result does not depend
+// on the device count.
+sda_status sda_share_generate_keyed(sda_engine* h, const sda_sharing_scheme* s, const int64_t* secrets, uint64_t D,
+                                    const uint32_t* key, uint32_t stream_id, int64_t* out, uint64_t out_cap) {
+    SDA_ENTRY;
+    if (!h || !s || !key) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle, scheme or key");
+    if (D && !secrets) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL input buffer");
+    HIP_TRY(hipSetDevice(h->device));
+    const KeyedDraws kd{key, stream_id};
+    if (s->kind == SDA_SHARING_ADDITIVE) {
+        const uint64_t n = s->share_count;
+        if (n == 0) return fail(SDA_ERR_PRECONDITION, "share_count - 1 underflows (additive.rs:42)");
+        if (s->modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
+        if (out_cap < n * D || (n * D && !out)) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+        if (D == 0) return ok();
+        (void)pick(h, h->stream);
+        if (sda_status st = host_additive_generate(h, s->modulus, n, secrets, D, nullptr, out, &kd)) return st;
+        return ok();
+    }
+    if (s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown sharing scheme kind");
+    if (sda_status st = check_packed(s)) return st;
+    const uint64_t k = s->secret_count, n = s->share_count;
+    const uint64_t B = (D + k - 1) / k;
+    if (out_cap < n * B || (n * B && !out)) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    if (B == 0) return ok();
+    (void)pick(h, h->stream);
+    if (sda_status st = host_packed_generate(h, s, secrets, D, nullptr, out, &kd)) return st;
+    return ok();
+}
+
 // ---------------- ShareCombiner::combine ----------------
 static sda_status combine_rows(sda_engine* h, int64_t modulus, const int64_t* const* rows, const uint64_t* lens,
                                uint64_t n_rows, int64_t* out, uint64_t out_cap, uint64_t* out_len,
@@ -656,6 +692,36 @@ sda_status sda_secret_mask(sda_engine* h, const sda_masking_scheme* s, const int
     HIP_TRY(hipMemcpyAsync(ds, secrets, D * 8, hipMemcpyHostToDevice, h->stream));
     if (sda_status st = chacha_mask(h, s->modulus, seed, w, ds, D, dmask, dseed, dout, h->stream)) return st;
     HIP_TRY(hipMemcpyAsync(masked_out, dout, D * 8, hipMemcpyDeviceToHost, h->stream));
+    return finish(h);
+}
+
+// Full masking (full.rs:22-35) with the mask drawn on the device: element d of (key, stream_id), bound = modulus
+sda_status sda_secret_mask_keyed(sda_engine* h, const sda_masking_scheme* s, const int64_t* secrets, uint64_t D,
+                                 const uint32_t* key, uint32_t stream_id, int64_t* mask_out, uint64_t mask_cap,
+                                 uint64_t* mask_len, int64_t* masked_out) {
+    SDA_ENTRY;
+    if (!h || !s || !key || !mask_len || (D && (!secrets || !masked_out || !mask_out)))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    *mask_len = 0;
+    if (s->kind != SDA_MASKING_FULL)
+        return fail(SDA_ERR_INVALID_ARGUMENT,
+                    "sda_secret_mask_keyed draws Full masks only: None draws nothing and ChaCha expands its own "
+                    "seed (use sda_secret_mask)");
+    if (s->modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
+    if (mask_cap < D) return fail(SDA_ERR_INVALID_ARGUMENT, "mask buffer too small");
+    if (D == 0) return ok();
+    HIP_TRY(hipSetDevice(h->device));
+    DevArena a;
+    if (sda_status st = stage(h, 3 * rup(D * 8), &a)) return st;
+    int64_t* ds = a.take<int64_t>(D);
+    int64_t* dm = a.take<int64_t>(D);
+    int64_t* dout = a.take<int64_t>(D);
+    HIP_TRY(hipMemcpyAsync(ds, secrets, D * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(sda::launch_draws(key, stream_id, 0, D, s->modulus, dm, h->stream));
+    HIP_TRY(sda::launch_addsub_trem(ds, dm, +1, D, dout, s->modulus, h->stream));
+    HIP_TRY(hipMemcpyAsync(masked_out, dout, D * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(mask_out, dm, D * 8, hipMemcpyDeviceToHost, h->stream));
+    *mask_len = D;
     return finish(h);
 }
 
@@ -1113,6 +1179,49 @@ sda_status sda_chacha_mask_combine_dev(sda_engine* h, int64_t modulus, uint64_t 
     if (sda_status st = chacha_combine(h, modulus, dimension, seeds, (uint32_t)w, n_seeds, out, pick(h, stream)))
         return st;
     return ok();
+}
+
+// The argument checks the two draws entry points share, in the header's order; *out_st is the status to return
+// when the result is true (SDA_OK for count == 0: nothing to launch).
+static bool draws_done(sda_engine* h, const uint32_t* key, uint64_t first, uint64_t count, int64_t bound,
+                       const int64_t* out, sda_status* out_st) {
+    if (!h || !key || (count && !out)) {
+        *out_st = fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle, key or output buffer");
+    } else if (bound <= 0) {
+        *out_st = fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
+    } else if (count && first + (count - 1) < first) {
+        *out_st = fail(SDA_ERR_INVALID_ARGUMENT, "first + count wraps past 2^64");
+    } else if (count == 0) {
+        *out_st = ok();
+    } else {
+        return false;
+    }
+    return true;
+}
+
+sda_status sda_draws_dev(sda_engine* h, const uint32_t* key, uint32_t stream_id, uint64_t first, uint64_t count,
+                         int64_t bound, int64_t* out, void* stream) {
+    SDA_ENTRY;
+    sda_status st;
+    if (draws_done(h, key, first, count, bound, out, &st)) return st;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(sda::launch_draws(key, stream_id, first, count, bound, out, pick(h, stream)));
+    return ok();
+}
+
+sda_status sda_draws(sda_engine* h, const uint32_t* key, uint32_t stream_id, uint64_t first, uint64_t count,
+                     int64_t bound, int64_t* out, uint64_t out_cap) {
+    SDA_ENTRY;
+    sda_status st;
+    if (draws_done(h, key, first, count, bound, out, &st)) return st;
+    if (out_cap < count) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    HIP_TRY(hipSetDevice(h->device));
+    DevArena a;
+    if (sda_status e = stage(h, rup(count * 8), &a)) return e;
+    int64_t* dd = a.take<int64_t>(count);
+    HIP_TRY(sda::launch_draws(key, stream_id, first, count, bound, dd, h->stream));
+    HIP_TRY(hipMemcpyAsync(out, dd, count * 8, hipMemcpyDeviceToHost, h->stream));
+    return finish(h);
 }
 
 sda_status sda_synth_fill_dev(sda_engine* h, int64_t* dst, uint64_t rows, uint64_t cols, uint64_t seed, int64_t lo,
@@ -2633,7 +2742,7 @@ sda_status host_decode_combine(sda_engine* h, int64_t m, const uint8_t* const* b
 // additive.rs:32-51 per column (batched.rs:19-53 with input_size 1): columns split over the devices;
 // out [n][D] clerk-major
 sda_status host_additive_generate(sda_engine* h, int64_t m, uint64_t n, const int64_t* secrets, uint64_t D,
-                                  const int64_t* draws, int64_t* out) {
+                                  const int64_t* draws, int64_t* out, const KeyedDraws* kd) {
     const size_t G = n_devices(h);
     return for_devices(h, [&](size_t g) -> sda_status {
         uint64_t lo, w;
@@ -2647,7 +2756,9 @@ sda_status host_additive_generate(sda_engine* h, int64_t m, uint64_t n, const in
         int64_t* ddr = a.take<int64_t>(w * (n - 1) + 1);
         int64_t* dout = a.take<int64_t>(n * w);
         HIP_TRY(hipMemcpyAsync(dsec, secrets + lo, w * 8, hipMemcpyHostToDevice, d->stream));
-        if (n > 1)
+        if (n > 1 && kd)      // element d * (n - 1) + j of the call's draws: this slice starts at column lo
+            HIP_TRY(sda::launch_draws(kd->key, kd->stream_id, lo * (n - 1), w * (n - 1), m, ddr, d->stream));
+        else if (n > 1)
             HIP_TRY(hipMemcpyAsync(ddr, draws + lo * (n - 1), w * (n - 1) * 8, hipMemcpyHostToDevice, d->stream));
         HIP_TRY(sda::launch_additive_generate(dsec, w, ddr, n, dout, m, d->stream));
         HIP_TRY(hipMemcpy2DAsync(out + lo, D * 8, dout, w * 8, w * 8, n, hipMemcpyDeviceToHost, d->stream));
@@ -2658,7 +2769,7 @@ sda_status host_additive_generate(sda_engine* h, int64_t m, uint64_t n, const in
 
 // packed_shamir.rs:40-43 per batch (batched.rs:19-53): batches split over the devices; out [n][B]
 sda_status host_packed_generate(sda_engine* h, const sda_sharing_scheme* s, const int64_t* secrets, uint64_t D,
-                                const int64_t* draws, int64_t* out) {
+                                const int64_t* draws, int64_t* out, const KeyedDraws* kd) {
     const uint64_t k = s->secret_count, t = s->privacy_threshold, n = s->share_count, B = (D + k - 1) / k;
     const size_t G = n_devices(h);
     return for_devices(h, [&](size_t g) -> sda_status {
@@ -2674,7 +2785,10 @@ sda_status host_packed_generate(sda_engine* h, const sda_sharing_scheme* s, cons
         int64_t* ddr = a.take<int64_t>(nb * t + 1);
         int64_t* dout = a.take<int64_t>(n * nb);
         HIP_TRY(hipMemcpyAsync(dsec, secrets + s0, ds * 8, hipMemcpyHostToDevice, d->stream));
-        if (t) HIP_TRY(hipMemcpyAsync(ddr, draws + b0 * t, nb * t * 8, hipMemcpyHostToDevice, d->stream));
+        if (t && kd)          // element b * t + j of the call's draws: this slice starts at batch b0
+            HIP_TRY(sda::launch_draws(kd->key, kd->stream_id, b0 * t, nb * t, s->modulus - 1, ddr, d->stream));
+        else if (t)
+            HIP_TRY(hipMemcpyAsync(ddr, draws + b0 * t, nb * t * 8, hipMemcpyHostToDevice, d->stream));
         if (sda_status e = ensure(&d->gen_log, &d->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
         sda::PackedGenArgs ga{dsec, ds, 1, ddr, dout};
         HIP_TRY(sda::launch_packed_generate(ga, (uint32_t)k, (uint32_t)t, (uint32_t)n, (uint32_t)s->modulus,

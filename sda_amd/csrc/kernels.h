@@ -307,6 +307,16 @@ hipError_t launch_chacha_streams_combine(int64_t modulus, uint64_t dimension, co
 hipError_t launch_chacha_stream(int64_t modulus, uint64_t dimension, const uint32_t* seed, uint32_t w,
                                 int64_t* mask, void* work, hipStream_t s);
 
+// ---- draws.hip ----
+// Elements one workgroup of the draws kernel produces (256 lanes x one ChaCha block of 8 draws); sda_amd/engine.py
+// restates it as DRAWS_TILE for the tests' shapes.
+constexpr uint32_t kDrawsTile = 2048;
+// out[p] = draw(first + p), p < count (device), uniform on [0, bound): ChaCha20 under key_host[8] (HOST words,
+// passed as a kernel argument) with state words 14 = stream_id, 15 = retry round (draws.hip gives the rule).
+// The caller has checked bound >= 1 and that first + count does not wrap.
+hipError_t launch_draws(const uint32_t* key_host, uint32_t stream_id, uint64_t first, uint64_t count, int64_t bound,
+                        int64_t* out, hipStream_t s);
+
 // ---- snapshot.hip ----
 // One blob of the snapshot transposition: len bytes from src offset to dst offset.
 struct SnapshotCopy {

@@ -77,6 +77,10 @@ COMBINE_PIPE = 8
 CombineLaunch = collections.namedtuple("CombineLaunch",
                                        "kind elem_bytes vec rows variant grid wlo nwide per_cu")
 
+# Elements one workgroup of the draws kernel produces (csrc/kernels.h kDrawsTile): the sizes at which
+# sda_draws_dev's grid gains a workgroup
+DRAWS_TILE = 2048
+
 _i64p = C.POINTER(C.c_int64)
 _u64p = C.POINTER(C.c_uint64)
 _u32p = C.POINTER(C.c_uint32)
@@ -141,6 +145,12 @@ SIGNATURES = [
                                            C.c_uint64, _vp, _vp, C.c_int32, _vp]),
     ("sda_additive_generate_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp]),
     ("sda_chacha_mask_combine_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
+    ("sda_draws_dev", _st, [_vp, _u32p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp]),
+    ("sda_draws", _st, [_vp, _u32p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int64, _i64p, C.c_uint64]),
+    ("sda_share_generate_keyed", _st, [_vp, C.POINTER(S.SharingSchemeC), _i64p, C.c_uint64, _u32p, C.c_uint32,
+                                       _i64p, C.c_uint64]),
+    ("sda_secret_mask_keyed", _st, [_vp, C.POINTER(S.MaskingSchemeC), _i64p, C.c_uint64, _u32p, C.c_uint32, _i64p,
+                                    C.c_uint64, _u64p, _i64p]),
     ("sda_synth_fill_dev", _st, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, _vp]),
     ("sda_hbm_alloc", _st, [C.c_int, C.c_uint64, C.POINTER(_vp)]),
     ("sda_hbm_free", _st, [_vp]),
@@ -327,6 +337,52 @@ class Engine:
         _check(self.lib.sda_secret_mask(self.h, C.byref(s), _ptr(sec), sec.size, _ptr(sd, _u32p), sd.size,
                                         _ptr(fm) if fm is not None else None, _ptr(mask), mask.size,
                                         C.byref(mlen), _ptr(masked)))
+        return mask[: mlen.value], masked[: sec.size]
+
+    # ---------------- device-side draws (one OS-RNG key per call, expanded on the device) ----------------
+    @staticmethod
+    def _key(key):
+        k = _arr(key, np.uint32)
+        if k.size != 8:
+            raise ValueError("a draws key is 8 uint32 words")
+        return k
+
+    def draws_dev(self, key, stream_id, first, count, bound, out_ptr, stream=None):
+        """out[p] = draw(first + p), p < count, uniform on [0, bound), into device memory (sda_draws_dev).  A
+        (key, stream_id) pair must never serve two different jobs."""
+        k = self._key(key)
+        _check(self.lib.sda_draws_dev(self.h, _ptr(k, _u32p), stream_id, first, count, bound, out_ptr, stream))
+
+    def draws(self, key, stream_id, first, count, bound) -> np.ndarray:
+        """The same draws into host memory (sda_draws)."""
+        k = self._key(key)
+        out = np.zeros(max(count, 1), np.int64)
+        _check(self.lib.sda_draws(self.h, _ptr(k, _u32p), stream_id, first, count, bound, _ptr(out), out.size))
+        return out[:count]
+
+    def share_generate_keyed(self, scheme, secrets, key, stream_id=0) -> np.ndarray:
+        """share_generate with its draws made on the device from (key, stream_id) (sda_share_generate_keyed)."""
+        s = scheme.c()
+        sec = _arr(secrets)
+        k = self._key(key)
+        B = self.lib.sda_share_length(C.byref(s), sec.size)
+        n = scheme.output_size()
+        out = np.zeros(max(n * B, 1), np.int64)
+        _check(self.lib.sda_share_generate_keyed(self.h, C.byref(s), _ptr(sec), sec.size, _ptr(k, _u32p), stream_id,
+                                                 _ptr(out), out.size))
+        return out[: n * B].reshape(n, B)
+
+    def secret_mask_keyed(self, scheme, secrets, key, stream_id=0):
+        """Full secret_mask with the mask drawn on the device from (key, stream_id) (sda_secret_mask_keyed);
+        returns (mask, masked)."""
+        s = scheme.c()
+        sec = _arr(secrets)
+        k = self._key(key)
+        mask = np.zeros(max(sec.size, 1), np.int64)
+        masked = np.zeros(max(sec.size, 1), np.int64)
+        mlen = C.c_uint64(0)
+        _check(self.lib.sda_secret_mask_keyed(self.h, C.byref(s), _ptr(sec), sec.size, _ptr(k, _u32p), stream_id,
+                                              _ptr(mask), mask.size, C.byref(mlen), _ptr(masked)))
         return mask[: mlen.value], masked[: sec.size]
 
     def mask_combine(self, scheme, rows: Sequence) -> np.ndarray:
