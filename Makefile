@@ -14,7 +14,8 @@ LIB     ?= sda_amd/libsda_engine.so
 GEN_PARTS    := 3_2 9_2 9_4 9_8 27_2 27_4 27_8 27_16 81_2 81_4 81_8 81_16 81_32 81_64
 REVEAL_PARTS := 8 16 32 64 96
 PLAIN   := combine elementwise chacha codec snapshot packed_wide draws
-OBJS    := $(patsubst %,$(OBJDIR)/%.o,$(PLAIN)) $(OBJDIR)/engine.o \
+HOST    := engine engine_dev hbm engine_codec engine_pipelines engine_host
+OBJS    := $(patsubst %,$(OBJDIR)/%.o,$(PLAIN)) $(patsubst %,$(OBJDIR)/%.o,$(HOST)) \
            $(OBJDIR)/packed_gen.o $(patsubst %,$(OBJDIR)/packed_gen_%.o,$(GEN_PARTS)) \
            $(OBJDIR)/packed_reveal.o $(patsubst %,$(OBJDIR)/packed_reveal_%.o,$(REVEAL_PARTS))
 HDRS    := $(CSRC)/packed_common.h $(CSRC)/kernels.h $(CSRC)/modarith.h $(CSRC)/xcd.h include/sda_engine.h
@@ -33,7 +34,8 @@ $(OBJDIR)/packed_reveal_%.o: $(CSRC)/packed_reveal.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -DSDA_REVEAL_PART=$* -c $< -o $@
 
-$(OBJDIR)/engine.o: $(CSRC)/engine.cpp $(CSRC)/host_pack.h $(HDRS)
+# the host translation units of the C ABI: one object each
+$(OBJDIR)/%.o: $(CSRC)/%.cpp $(CSRC)/engine_internal.h $(CSRC)/host_pack.h $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -x hip -c $< -o $@
 

@@ -1,0 +1,356 @@
+// engine_pipelines.cpp -- the fused recipient and participant pipelines of the C ABI (include/sda_engine.h).
+#include "engine_internal.h"
+
+using namespace sda_host;
+
+// ---------------- fused role pipelines ----------------
+namespace {
+
+// receive.rs:80-157 + :14-20 on device-resident inputs (see sda_recipient_reveal_dev).
+sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const void* mask_in, uint64_t n_masks,
+                              uint64_t mask_width, const sda_sharing_scheme* ss, uint64_t dimension,
+                              const uint64_t* indices, const int64_t* shares, uint64_t n_idx, uint64_t share_len,
+                              int64_t output_modulus, int32_t mode, int64_t* out, uint64_t out_cap,
+                              uint64_t* out_len, hipStream_t st) {
+    *out_len = 0;
+    // Checks in the reference's order: mask combine (receive.rs:101-117), reconstruct (:120-146),
+    // unmask (:149-152).
+    // ---- 1. mask combine: its length and panics ----
+    uint64_t mask_len = 0;
+    if (ms->kind == SDA_MASKING_NONE) {
+        if (n_masks && mask_width) return fail(SDA_ERR_PRECONDITION, "assertion failed: masks.iter().all(|mask| mask.len() == 0)");
+    } else if (ms->kind == SDA_MASKING_FULL) {
+        mask_len = n_masks ? mask_width : 0;                // full.rs:38-40
+        if (mask_len) {                                     // full.rs:45 `%= modulus`
+            int64_t q0;
+            if (sda_status e = modulus_abs(ms->modulus, &q0)) return e;
+        }
+    } else if (ms->kind == SDA_MASKING_CHACHA) {
+        mask_len = ms->dimension;                           // chacha.rs:58
+        if (mask_width == 0 || mask_width > 8) return fail(SDA_ERR_UNSUPPORTED, "device seeds must be 1..8 words");
+        if (mask_len && n_masks && ms->modulus <= 0)        // chacha.rs:69 gen_range(0, m)
+            return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
+    } else {
+        return fail(SDA_ERR_INVALID_ARGUMENT, "unknown masking scheme kind");
+    }
+    // ---- 2. reconstruct: masked output length and errors ----
+    uint64_t D;
+    if (ss->kind == SDA_SHARING_ADDITIVE) {
+        D = n_idx ? share_len : 0;                           // additive.rs:56-60
+        if (D) {                                             // additive.rs:67 `%= modulus`
+            int64_t m0;
+            if (sda_status e = modulus_abs(ss->modulus, &m0)) return e;
+        }
+    } else if (ss->kind == SDA_SHARING_PACKED_SHAMIR) {
+        if (sda_status e = check_packed(ss)) return e;
+        if (mode != SDA_REVEAL_EXACT && mode != SDA_REVEAL_CANONICAL) return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
+        const uint64_t B = (dimension + ss->secret_count - 1) / ss->secret_count;
+        if (B) {                                             // batched.rs:77-81: no batch => no check
+            const bool enough = n_idx >= ss->privacy_threshold + ss->secret_count;
+            if (n_idx && share_len < (enough ? B : 1))      // batched.rs:84 indexes [batch_index]
+                return fail(SDA_ERR_PRECONDITION, "index out of bounds: clerk vector shorter than the batch count");
+            if (!enough) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");  // packed_shamir.rs:75
+            if (n_idx > sda::kRevealMaxShares)
+                return fail(SDA_ERR_UNSUPPORTED, "more than %u clerk shares per batch", sda::kRevealMaxShares);
+        }
+        D = dimension;
+    } else {
+        return fail(SDA_ERR_INVALID_ARGUMENT, "unknown sharing scheme kind");
+    }
+    // ---- 3. unmask ----
+    if (ms->kind != SDA_MASKING_NONE && mask_len != D)     // chacha.rs:83 / full.rs:58 assert_eq!
+        return fail(SDA_ERR_PRECONDITION, "assertion failed: mask.len() == masked_secrets.len() (%llu vs %llu)",
+                    (unsigned long long)mask_len, (unsigned long long)D);
+    if (out_cap < D) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    if (D == 0) return ok();
+    int64_t q = 1;
+    if (ms->kind != SDA_MASKING_NONE)
+        if (sda_status e = modulus_abs(ms->modulus, &q)) return e;
+    const bool packed = ss->kind == SDA_SHARING_PACKED_SHAMIR;
+    const uint64_t B = packed ? (dimension + ss->secret_count - 1) / ss->secret_count : 0;
+    const bool compact = packed && share_len != B;
+    if (sda_status e = ensure(&h->pipe, &h->pipe_bytes, 2 * rup(D * 8) + (compact ? rup(n_idx * B * 8) : 0) + 256))
+        return e;
+    int64_t* dmask = static_cast<int64_t*>(h->pipe);
+    int64_t* dmasked = dmask + rup(D * 8) / 8;
+    // 1. masks (receive.rs:101-117)
+    if (ms->kind == SDA_MASKING_FULL) {
+        if (sda_status e = modulus_abs(ms->modulus, &q)) return e;
+        HIP_TRY(sda::launch_combine_exact(static_cast<const int64_t*>(mask_in), n_masks, D, mask_width, dmask, q, st,
+                                          false, &h->combine_last));
+    }
+    PendingChacha pc;                                       // ChaCha: its rejection count is checked at the end
+    if (ms->kind == SDA_MASKING_CHACHA) {
+        if (sda_status e = chacha_combine_begin(h, ms->modulus, D, static_cast<const uint32_t*>(mask_in),
+                                                (uint32_t)mask_width, n_masks, dmask, st, &pc))
+            return e;
+    }
+    // 2. reconstruct (receive.rs:120-146)
+    if (!packed) {
+        int64_t m;
+        if (sda_status e = modulus_abs(ss->modulus, &m)) return e;
+        HIP_TRY(sda::launch_combine_exact(shares, n_idx, D, share_len, dmasked, m, st, false, &h->combine_last));
+    } else {
+        const int64_t* src = shares;
+        if (compact) {                                      // batched.rs:83-85 reads [clerk][0..B)
+            int64_t* c = dmasked + rup(D * 8) / 8;
+            HIP_TRY(hipMemcpy2DAsync(c, B * 8, shares, share_len * 8, B * 8, n_idx, hipMemcpyDeviceToDevice, st));
+            src = c;
+        }
+        if (sda_status e = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
+        sda::PackedRevealArgs ra{src, dimension, 1, dmasked};
+        // The output is positive(unmask(reveal)).  When the masking modulus (or no mask) and output_modulus are
+        // both the sharing prime, that is the canonical residue of (reveal - mask) mod p, which depends only on
+        // the reveal's residue: tss' signed representatives (EXACT, 2.1x the canonical reveal's time) cannot
+        // change a byte of it, so the canonical reveal runs.  Duplicate clerk points (no Lagrange form) fall
+        // back to EXACT.  SDA_RECIPIENT_EXACT=1 keeps EXACT (A/B and test knob).
+        const int64_t p = ss->modulus;
+        const char* keep = getenv("SDA_RECIPIENT_EXACT");
+        const bool residue_only = output_modulus == p && (ms->kind == SDA_MASKING_NONE || q == p) &&
+                                  !(keep && atoi(keep) == 1);
+        const int32_t run_mode = (mode == SDA_REVEAL_EXACT && residue_only) ? SDA_REVEAL_CANONICAL : mode;
+        hipError_t e = packed_reveal(h, ss, ra, indices, n_idx, run_mode, st);
+        if (e == hipErrorInvalidValue && run_mode != mode) e = packed_reveal(h, ss, ra, indices, n_idx, mode, st);
+        if (sda_status r = reveal_status(e, mode)) return r;
+    }
+    // 3. unmask (receive.rs:149-152) + RecipientOutput::positive (:14-20), one pass
+    HIP_TRY(sda::launch_unmask_positive(dmasked, ms->kind == SDA_MASKING_NONE ? nullptr : dmask, D, q,
+                                        output_modulus, out, st));
+    if (pc.pending) {            // the mask's rejection count: fix the mask and unmask again if it had any
+        HIP_TRY(hipStreamSynchronize(st));
+        bool changed = false;
+        if (sda_status e = chacha_combine_end(h, pc, st, &changed)) return e;
+        if (changed)
+            HIP_TRY(sda::launch_unmask_positive(dmasked, dmask, D, q, output_modulus, out, st));
+    }
+    *out_len = D;
+    return SDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+sda_status sda_recipient_reveal_dev(sda_engine* h, const sda_masking_scheme* ms, const void* mask_in, uint64_t n_masks,
+                                    uint64_t mask_width, const sda_sharing_scheme* ss, uint64_t dimension,
+                                    const uint64_t* indices, const int64_t* shares, uint64_t n_idx,
+                                    uint64_t share_len, int64_t output_modulus, int32_t mode, int64_t* out,
+                                    uint64_t out_cap, uint64_t* out_len, void* stream) {
+    SDA_ENTRY;
+    if (!h || !ms || !ss || !out_len || (n_idx && (!shares || !indices)) || (n_masks && mask_width && !mask_in))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (sda_status e = recipient_pipeline(h, ms, mask_in, n_masks, mask_width, ss, dimension, indices, shares, n_idx,
+                                          share_len, output_modulus, mode, out, out_cap, out_len, pick(h, stream)))
+        return e;
+    return ok();
+}
+
+sda_status sda_recipient_reveal(sda_engine* h, const sda_masking_scheme* ms, const int64_t* const* mask_rows,
+                                const uint64_t* mask_lens, uint64_t n_masks, const sda_sharing_scheme* ss,
+                                uint64_t dimension, const uint64_t* indices, const int64_t* const* share_rows,
+                                const uint64_t* share_lens, uint64_t n_idx, int64_t output_modulus, int32_t mode,
+                                int64_t* out, uint64_t out_cap, uint64_t* out_len) {
+    SDA_ENTRY;
+    if (!h || !ms || !ss || !out_len || (n_masks && (!mask_rows || !mask_lens)) ||
+        (n_idx && (!share_rows || !share_lens || !indices)))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out_len = 0;
+    HIP_TRY(hipSetDevice(h->device));
+    // host-side shape checks in the reference's order, then one upload
+    uint64_t share_len = n_idx ? share_lens[0] : 0;
+    for (uint64_t i = 0; i < n_idx; ++i) {
+        if (share_lens[i] == share_len) continue;
+        if (ss->kind == SDA_SHARING_ADDITIVE) return fail(SDA_ERR_MISMATCHING_DIMENSION, "Mismatching dimension");
+        share_len = share_lens[i] < share_len ? share_lens[i] : share_len;   // packed: reads [0, B) of each
+    }
+    uint64_t width = 0;
+    std::vector<uint32_t> seeds;
+    if (ms->kind == SDA_MASKING_FULL) {
+        width = n_masks ? mask_lens[0] : 0;
+        for (uint64_t i = 0; i < n_masks; ++i)
+            if (mask_lens[i] != width) return fail(SDA_ERR_PRECONDITION, "assertion failed: mask.len() == dimension");
+    } else if (ms->kind == SDA_MASKING_CHACHA) {
+        uint32_t w;
+        seeds = pack_seeds(mask_rows, mask_lens, n_masks, &w);        // key = first 8 words, zero padded
+        width = w;
+    } else {
+        for (uint64_t i = 0; i < n_masks; ++i)
+            if (mask_lens[i]) return fail(SDA_ERR_PRECONDITION, "assertion failed: masks.iter().all(|mask| mask.len() == 0)");
+    }
+    const uint64_t outn = ss->kind == SDA_SHARING_ADDITIVE ? share_len : dimension;
+    // A multi-device handle spreads the mask combine (receive.rs:113-116, the dominant cost at configs[4]) over its
+    // devices -- seeds split, one RCCL reduce onto device 0 (engine_host.cpp) -- and runs the rest of the
+    // pipeline on device 0 with the combined mask as one Full mask row: (0 + c) % m = c for the canonical c, so
+    // the unmask sees the same mask.  Only where the reference would not panic in the mask combine (m > 0).
+    const sda_masking_scheme full_row = {SDA_MASKING_FULL, ms->modulus, 0, 0};
+    const bool multi_mask = ms->kind == SDA_MASKING_CHACHA && is_multi(h) && n_masks && ms->dimension &&
+                            ms->modulus > 0;
+    if (multi_mask) {
+        if (sda_status e = host_stream_ensure(h, 0, ms->dimension * 8)) return e;
+        if (sda_status e = chacha_combine_multi(h, ms->modulus, ms->dimension, seeds, (uint32_t)width, n_masks,
+                                                static_cast<int64_t*>(h->hs_dev)))
+            return e;
+    }
+    DevArena a;
+    if (sda_status e = stage(h, rup(n_idx * share_len * 8 + 8) + rup(n_masks * width * 8 + 8) + rup(outn * 8 + 8), &a))
+        return e;
+    int64_t* dsh = a.take<int64_t>(n_idx * share_len + 1);
+    void* dmask = a.take<int64_t>(n_masks * width + 1);
+    int64_t* dout = a.take<int64_t>(outn + 1);
+    for (uint64_t i = 0; i < n_idx; ++i)
+        if (share_len) HIP_TRY(hipMemcpyAsync(dsh + i * share_len, share_rows[i], share_len * 8, hipMemcpyHostToDevice, h->stream));
+    if (ms->kind == SDA_MASKING_FULL)
+        for (uint64_t i = 0; i < n_masks; ++i)
+            if (width) HIP_TRY(hipMemcpyAsync(static_cast<int64_t*>(dmask) + i * width, mask_rows[i], width * 8,
+                                              hipMemcpyHostToDevice, h->stream));
+    if (ms->kind == SDA_MASKING_CHACHA && !seeds.empty() && !multi_mask)
+        HIP_TRY(hipMemcpyAsync(dmask, seeds.data(), seeds.size() * 4, hipMemcpyHostToDevice, h->stream));
+    uint64_t len = 0;
+    if (sda_status e = multi_mask
+                           ? recipient_pipeline(h, &full_row, h->hs_dev, 1, ms->dimension, ss, dimension, indices, dsh,
+                                                n_idx, share_len, output_modulus, mode, dout, (uint64_t)-1, &len, h->stream)
+                           : recipient_pipeline(h, ms, dmask, n_masks, ms->kind == SDA_MASKING_NONE ? 0 : width, ss,
+                                                dimension, indices, dsh, n_idx, share_len, output_modulus, mode, dout,
+                                                (uint64_t)-1, &len, h->stream))
+        return e;
+    if (out_cap < len) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    if (len) HIP_TRY(hipMemcpyAsync(out, dout, len * 8, hipMemcpyDeviceToHost, h->stream));
+    *out_len = len;
+    return finish(h);
+}
+
+// The participant pipeline behind sda_participant_share_dev and sda_participant_share32_dev.  One of shares64 /
+// shares32 is the [n][B] output (shares32: int32 rows, PackedShamir only, encoded by the int32 encoder).
+static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                    uint64_t seed_words, const int64_t* full_masks, const sda_sharing_scheme* ss,
+                                    const int64_t* secrets, uint64_t dimension, const int64_t* draws, int32_t mode,
+                                    int64_t* shares64, int32_t* shares32, uint8_t* payload, uint64_t payload_cap,
+                                    uint64_t* payload_row_bytes, void* stream) {
+    if (!h || !ms || !ss || (dimension && (!secrets || (!shares64 && !shares32))) || (payload && !payload_row_bytes))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = pick(h, stream);
+    const uint64_t D = dimension;
+    const bool packed = ss->kind == SDA_SHARING_PACKED_SHAMIR;
+    if (!packed && ss->kind != SDA_SHARING_ADDITIVE) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown sharing scheme kind");
+    if (!packed && shares32)
+        return fail(SDA_ERR_UNSUPPORTED, "int32 shares need a PackedShamir scheme: an additive scheme's first n - 1 "
+                                         "shares are the caller's draws, copied unchecked");
+    if (mode != SDA_REVEAL_EXACT && mode != SDA_REVEAL_CANONICAL) return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
+    if (packed) {
+        if (sda_status e = check_packed(ss)) return e;
+    } else {
+        if (ss->share_count == 0) return fail(SDA_ERR_PRECONDITION, "share_count - 1 underflows (additive.rs:42)");
+        if (ss->modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
+    }
+    // 1. SecretMasker::mask (participate.rs:53-54)
+    const int64_t* masked = secrets;
+    // ChaCha on the fast path: the masked secrets come straight out of the ChaCha kernel and its rejection
+    // count is checked at the end of the call (a nonzero count -- probability < 2^-28 per draw -- redoes
+    // the mask exactly, then every later step)
+    bool mask_pending = false;
+    int64_t* cmask = nullptr;
+    uint32_t* cseed = nullptr;
+    uint32_t cw = 0;
+    if (ms->kind != SDA_MASKING_NONE && D) {
+        if (ms->modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
+        if (sda_status e = ensure(&h->pipe, &h->pipe_bytes, 2 * rup(D * 8) + 256)) return e;
+        int64_t* dm = static_cast<int64_t*>(h->pipe);
+        if (ms->kind == SDA_MASKING_FULL) {
+            if (!full_masks) return fail(SDA_ERR_INVALID_ARGUMENT, "Full masking needs the drawn masks");
+            HIP_TRY(sda::launch_addsub_trem(secrets, full_masks, +1, D, dm, ms->modulus, st));      // full.rs:28-31
+        } else if (ms->kind == SDA_MASKING_CHACHA) {
+            if (ms->dimension != D) return fail(SDA_ERR_PRECONDITION, "assertion failed: dimension == secrets.len()");
+            const uint64_t want = (ms->seed_bitsize + 31) / 32;
+            if (seed_words != want || (seed_words && !seed))
+                return fail(SDA_ERR_PRECONDITION, "expected %llu seed words", (unsigned long long)want);
+            int64_t* dmask = dm + rup(D * 8) / 8;
+            uint32_t* dseed = reinterpret_cast<uint32_t*>(dmask + rup(D * 8) / 8);
+            const uint32_t w = (uint32_t)(seed_words < 8 ? seed_words : 8);
+            if (w) HIP_TRY(hipMemcpyAsync(dseed, seed, w * 4, hipMemcpyHostToDevice, st));
+            // chacha.rs:36-45: masked = (secrets + draw) % m over one stream
+            if (chacha_fast_path(ms->modulus)) {
+                if (sda_status e = ensure(&h->work, &h->work_bytes, sda::chacha_work_bytes(D, 0))) return e;
+                sda::ChachaLaunchInfo info;
+                HIP_TRY(sda::launch_chacha_mask_add_async(ms->modulus, D, dseed, w, secrets, dm, h->work, st,
+                                                          h->rej_host, &info));
+                record_chacha(h, info);
+                mask_pending = true;
+            } else {
+                if (sda_status e = chacha_combine(h, ms->modulus, D, dseed, w, 1, dmask, st)) return e;
+                HIP_TRY(sda::launch_addsub_trem(secrets, dmask, +1, D, dm, ms->modulus, st));
+            }
+            cmask = dmask;
+            cseed = dseed;
+            cw = w;
+        } else {
+            return fail(SDA_ERR_INVALID_ARGUMENT, "unknown masking scheme kind");
+        }
+        masked = dm;
+    }
+    // 2. ShareGenerator::generate (participate.rs:75-76): shares [n][B]
+    const uint64_t n = ss->share_count;
+    const uint64_t B = packed ? (D + ss->secret_count - 1) / ss->secret_count : D;
+    if (B && !draws) return fail(SDA_ERR_INVALID_ARGUMENT, "need the randomness draws");
+    if (payload && n > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 clerks");
+    auto share_and_encode = [&]() -> sda_status {
+        if (B) {
+            if (packed) {
+                sda::PackedGenArgs ga{masked, D, 1, draws, shares64, mode == SDA_REVEAL_CANONICAL};
+                ga.out32 = shares32;             // as sda_packed_generate32_dev: scratch + narrowing at n + 1 = 81
+                if (sda_status e = packed_generate(h, ss, ga, st)) return e;
+            } else {
+                HIP_TRY(sda::launch_additive_generate(masked, D, draws, n, shares64, ss->modulus, st));
+            }
+        }
+        // 3. per-clerk payload encoding (participate.rs:79-98 -> sodium.rs:36-41); sealing stays on the host
+        if (payload) {
+            if (sda_status e = shares32 ? encode_rows(h, shares32, n, B, B, payload, payload_cap, payload_row_bytes, st,
+                                                      "payload_cap")
+                                        : encode_rows(h, shares64, n, B, B, payload, payload_cap, payload_row_bytes, st,
+                                                      "payload_cap"))
+                return e;
+        }
+        return SDA_OK;
+    };
+    if (sda_status e = share_and_encode()) return e;
+    if (mask_pending) {          // the mask's rejection count: redo the mask exactly, and every later step
+        HIP_TRY(hipStreamSynchronize(st));
+        if (*h->rej_host) {
+            if (sda_status e = chacha_combine(h, ms->modulus, D, cseed, cw, 1, cmask, st)) return e;
+            // the record stays the mask add's, with the redo's fix-up count (or its log overflow)
+            if (h->chacha_last.path != sda::kChachaOverflow) {
+                h->chacha_last.path = sda::kChachaMaskAdd;
+                h->chacha_last.grid_y = 1;
+            }
+            HIP_TRY(sda::launch_addsub_trem(secrets, cmask, +1, D, const_cast<int64_t*>(masked), ms->modulus, st));
+            if (sda_status e = share_and_encode()) return e;
+        }
+    }
+    return ok();
+}
+
+// participate.rs:53-76 (+ the encoding step of Encryptor::encrypt, sodium.rs:36-41) on device.
+sda_status sda_participant_share_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                     uint64_t seed_words, const int64_t* full_masks, const sda_sharing_scheme* ss,
+                                     const int64_t* secrets, uint64_t dimension, const int64_t* draws,
+                                     int32_t mode, int64_t* shares_out, uint8_t* payload, uint64_t payload_cap,
+                                     uint64_t* payload_row_bytes, void* stream) {
+    SDA_ENTRY;
+    return participant_share(h, ms, seed, seed_words, full_masks, ss, secrets, dimension, draws, mode, shares_out,
+                             nullptr, payload, payload_cap, payload_row_bytes, stream);
+}
+
+// The same with the shares as int32 rows, from sda_packed_generate32_dev's kernels into the int32 encoder.
+sda_status sda_participant_share32_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                       uint64_t seed_words, const int64_t* full_masks, const sda_sharing_scheme* ss,
+                                       const int64_t* secrets, uint64_t dimension, const int64_t* draws, int32_t mode,
+                                       int32_t* shares_out, uint8_t* payload, uint64_t payload_cap,
+                                       uint64_t* payload_row_bytes, void* stream) {
+    SDA_ENTRY;
+    return participant_share(h, ms, seed, seed_words, full_masks, ss, secrets, dimension, draws, mode, nullptr,
+                             shares_out, payload, payload_cap, payload_row_bytes, stream);
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// host_pack.h -- packing host share rows into a dense staging tile (the streaming host path of engine.cpp).
+// host_pack.h -- packing host share rows into a dense staging tile (the streaming host path of engine_host.cpp).
 // Header-only and HIP-free, so a plain C++ program can test it under a host sanitizer (tests/host_c).
 #pragma once
 #include <limits.h>

@@ -1,7 +1,7 @@
 """The share payload codec's dispatch, restated once for the tests (CPU only, numpy; no product import).
 
 Everything here is computed from a job's payload bytes and blob offsets alone -- the same inputs
-`decode_combine()` (sda_amd/csrc/engine.cpp) and the launchers of sda_amd/csrc/codec.hip decide from:
+`decode_combine()` (sda_amd/csrc/engine_codec.cpp) and the launchers of sda_amd/csrc/codec.hip decide from:
 
   regions        16 KiB regions aligned to the byte buffer (kRegionBytes; varint_plan);
   terminators    bytes without 0x80 inside a blob, and a blob's last byte when it continues (a truncated tail

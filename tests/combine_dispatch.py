@@ -35,7 +35,7 @@ def small_m(m):
 
 
 def launched_stride(n, dim, row_stride):
-    """engine.cpp: every entry point hands the launcher `n > 1 ? row_stride : dim`."""
+    """engine_dev.cpp: every entry point hands the launcher `n > 1 ? row_stride : dim`."""
     return row_stride if n > 1 else dim
 
 

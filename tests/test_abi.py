@@ -71,12 +71,23 @@ def test_engine_fails_loudly_without_device():
 
 
 def test_every_entry_point_opens_a_call_scope():
-    """engine.cpp: every sda_status entry point starts with SDA_ENTRY (the RAII CallScope that ends the
-    call's stream-ordering scope on every return path), so no entry point can leave a stale
-    stream behind for the next call's early fail()."""
-    import re
-    src = open(os.path.join(ROOT, "sda_amd", "csrc", "engine.cpp")).read()
+    """The host translation units (sda_amd/csrc/*.cpp): every sda_status entry point the header declares is
+    defined in one of them and starts with SDA_ENTRY (the RAII CallScope that ends the call's stream-ordering
+    scope on every return path), so no entry point can leave a stale stream behind for the next
+    call's early fail()."""
+    import glob
+    src = "\n".join(open(p).read() for p in sorted(glob.glob(os.path.join(ROOT, "sda_amd", "csrc", "*.cpp"))))
     defs = list(re.finditer(r"^sda_status (sda_\w+)\([^)]*\)\s*\{\n(.*)\n", src, flags=re.M))
-    assert len(defs) >= 30
+    declared = re.findall(r"^sda_status (sda_\w+)\(", open(HEADER).read(), flags=re.M)
+    assert len(declared) == len(set(declared)) >= 30
+    assert sorted(m.group(1) for m in defs) == sorted(declared)
     missing = [m.group(1) for m in defs if m.group(2).strip() != "SDA_ENTRY;"]
     assert not missing, missing
+
+
+def test_every_declared_function_is_a_defined_dynamic_symbol():
+    """`nm -D --defined-only` of the built library lists every function include/sda_engine.h declares."""
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", E.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if line.split()[-2:-1] == ["T"]}
+    assert not [name for name in declared_symbols() if name not in exported]

@@ -1,6 +1,6 @@
 """GPU: int32 share rows as an input type of the combine (include/sda_engine.h: sda_combine32_dev,
 sda_combine32_accumulate_dev, sda_narrow32_dev, sda_host_stream_stats) and the half-width host stream
-(engine.cpp "host path" section, SDA_HOST_NARROW).
+(engine_host.cpp, SDA_HOST_NARROW).
 
 The oracle is combiner.rs:16-28 over the rows widened to i64 (oracle.combine): the int32 kernels sign-extend and
 run the same recurrence, so every comparison is bit for bit, for every modulus."""

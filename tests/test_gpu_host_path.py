@@ -1,4 +1,4 @@
-"""The streaming, multi-device host path of the C ABI (include/sda_engine.h, engine.cpp "host path" section)
+"""The streaming, multi-device host path of the C ABI (include/sda_engine.h, engine_host.cpp)
 against the oracle, through the host trait entry points the Rust shim calls:
 
   sda_share_combine     ShareCombiner::combine   (clerk.rs:85-86 -> combiner.rs:16-28)
