@@ -126,6 +126,8 @@ extern "C" {
     pub fn sda_combine_last_launch(h: *mut SdaEngine, kind: *mut u32, elem_bytes: *mut u32, vec: *mut u32,
                                    rows: *mut u32, variant: *mut u32, grid: *mut u64, wlo: *mut u32,
                                    nwide: *mut u32, per_cu: *mut u32) -> SdaStatus;
+    pub fn sda_snapshot_last_launch(h: *mut SdaEngine, blobs: *mut u64, chunks: *mut u64, grid: *mut u64,
+                                    chunk_bytes: *mut u64, shifts: *mut u32) -> SdaStatus;
     pub fn sda_combine_finalize_dev(h: *mut SdaEngine, modulus: i64, sums: *const i64, dim: u64, out: *mut i64,
                                     stream: *mut c_void) -> SdaStatus;
     pub fn sda_combine_split_dev(h: *mut SdaEngine, modulus: i64, shares: *const i64, n: u64, dim: u64,

@@ -319,6 +319,20 @@ sda_status sda_combine_last_launch(sda_engine* h, uint32_t* kind, uint32_t* elem
                                    uint32_t* variant, uint64_t* grid, uint32_t* wlo, uint32_t* nwide,
                                    uint32_t* per_cu);
 
+/* Diagnostic (read-only): what the handle's most recent sda_snapshot_transpose_dev planned and launched.  Every
+ * successful call with a dst writes the record; a sizing query (dst == NULL) and a failed call leave it as it was.
+ * Before any such call every field is 0.
+ *   blobs        the non-empty blobs of the copy plan (empty blobs are dropped on the host)
+ *   chunks       the chunks those blobs were cut into: the sum of ceil(len / chunk_bytes)
+ *   grid         workgroups launched; 0 when every blob was empty (nothing is launched)
+ *   chunk_bytes  the bytes of one chunk of the copy kernel as built
+ *   shifts       bit s is set when some planned blob has (source offset - destination offset) mod 16 == s: the
+ *                kernel's 16 load variants this call reached
+ * A snapshot of empty blobs alone reports (0, 0, 0, chunk_bytes, 0).  A host-side record: nothing is waited for or
+ * copied.  No pointer may be NULL. */
+sda_status sda_snapshot_last_launch(sda_engine* h, uint64_t* blobs, uint64_t* chunks, uint64_t* grid,
+                                    uint64_t* chunk_bytes, uint32_t* shifts);
+
 /* Multi-GPU finalize: `sums` are the int64 sums (RCCL-reduced; |sum| <= 2^63 - 1, signed allowed)
  * of per-GPU combine results; out = their canonical residue in [0, m).  Exact w.r.t. the reference
  * when all combined inputs were non-negative. */

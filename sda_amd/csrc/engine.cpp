@@ -770,4 +770,19 @@ sda_status sda_combine_last_launch(sda_engine* h, uint32_t* kind, uint32_t* elem
     return ok();
 }
 
+sda_status sda_snapshot_last_launch(sda_engine* h, uint64_t* blobs, uint64_t* chunks, uint64_t* grid,
+                                    uint64_t* chunk_bytes, uint32_t* shifts) {
+    SDA_ENTRY;
+    if (!h || !blobs || !chunks || !grid || !chunk_bytes || !shifts)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    // a host-side record, final when the call that made it returned: nothing to wait for
+    const sda::SnapshotLaunchInfo& s = h->snap_last;
+    *blobs = s.blobs;
+    *chunks = s.chunks;
+    *grid = s.grid;
+    *chunk_bytes = s.chunk_bytes;
+    *shifts = s.shifts;
+    return ok();
+}
+
 }  // extern "C"

@@ -337,14 +337,23 @@ sda_status sda_snapshot_transpose_dev(sda_engine* h, const uint8_t* src, const u
     std::vector<uint64_t> cstart(1, 0);
     blobs.reserve(nb);
     cstart.reserve(nb + 1);
+    // sda_snapshot_last_launch: collected here, the handle's record only once this call returns SDA_OK
+    sda::SnapshotLaunchInfo info;
+    info.chunk_bytes = chunk;
     for (uint64_t c = 0; c < n; ++c)
         for (uint64_t p = 0; p < P; ++p) {
             const uint64_t len = part_off[p * n + c + 1] - part_off[p * n + c];
             if (!len) continue;
             blobs.push_back({part_off[p * n + c], clerk_base[c] + clerk_off[c * (P + 1) + p], len});
             cstart.push_back(cstart.back() + (len + chunk - 1) / chunk);
+            info.shifts |= 1u << ((blobs.back().src - blobs.back().dst) & 15);
         }
-    if (blobs.empty()) return ok();
+    info.blobs = blobs.size();
+    info.chunks = cstart.back();
+    if (blobs.empty()) {
+        h->snap_last = info;
+        return ok();
+    }
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = pick(h, stream);
     const size_t b0 = rup(blobs.size() * sizeof(sda::SnapshotCopy));
@@ -354,8 +363,9 @@ sda_status sda_snapshot_transpose_dev(sda_engine* h, const uint8_t* src, const u
     HIP_TRY(hipMemcpyAsync(plan + b0, cstart.data(), cstart.size() * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(sda::launch_snapshot_transpose(src, dst, reinterpret_cast<const sda::SnapshotCopy*>(plan),
                                            reinterpret_cast<const uint64_t*>(plan + b0), blobs.size(),
-                                           cstart.back(), st));
+                                           cstart.back(), st, &info.grid));
     HIP_TRY(hipStreamSynchronize(st));                             // the host plan vectors go out of scope
+    h->snap_last = info;
     return ok();
 }
 

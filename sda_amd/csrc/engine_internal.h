@@ -66,6 +66,8 @@ struct sda_engine {
     // sda_combine_last_launch: which combine kernel this handle (of a multi-device handle: this device) launched
     // last and on what grid, filled by the launcher where it decides; a call that launches nothing leaves it
     sda::CombineLaunchInfo combine_last;
+    // sda_snapshot_last_launch: what the last successful, non-sizing sda_snapshot_transpose_dev planned and launched
+    sda::SnapshotLaunchInfo snap_last;
     // streaming host path (host rows -> HBM in row tiles, engine_host.cpp): pinned staging and device
     // tiles, double buffered, and a copy stream so a tile's upload overlaps the previous tile's combine
     hipStream_t copy_stream = nullptr;

@@ -323,10 +323,20 @@ struct SnapshotCopy {
     uint64_t src, dst, len;
 };
 uint64_t snapshot_chunk_bytes();
+// What the last snapshot transposition on a handle planned and launched (sda_snapshot_last_launch).  The host
+// plan (sda_snapshot_transpose_dev) fills blobs, chunks, chunk_bytes and shifts; the launcher reports its grid.
+struct SnapshotLaunchInfo {
+    uint64_t blobs = 0;        // non-empty blobs planned
+    uint64_t chunks = 0;       // their chunks (total_chunks)
+    uint64_t grid = 0;         // workgroups launched
+    uint64_t chunk_bytes = 0;  // snapshot_chunk_bytes()
+    uint32_t shifts = 0;       // bit s: some planned blob has (src - dst) & 15 == s
+};
 // blobs[n_blobs] (each len >= 1), chunk_start[n_blobs + 1] = exclusive prefix of ceil(len / chunk);
-// src/dst 16-byte aligned, src readable 32 bytes past the last blob's end.
+// src/dst 16-byte aligned, src readable 32 bytes past the last blob's end.  *grid (when given): the workgroups
+// of the launch the runtime accepted, 0 when there was nothing to launch; a refused launch leaves it.
 hipError_t launch_snapshot_transpose(const uint8_t* src, uint8_t* dst, const SnapshotCopy* blobs,
                                      const uint64_t* chunk_start, uint64_t n_blobs, uint64_t total_chunks,
-                                     hipStream_t s);
+                                     hipStream_t s, uint64_t* grid = nullptr);
 
 }  // namespace sda

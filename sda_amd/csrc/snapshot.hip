@@ -143,16 +143,24 @@ uint64_t snapshot_chunk_bytes() { return kChunk; }
 
 hipError_t launch_snapshot_transpose(const uint8_t* src, uint8_t* dst, const SnapshotCopy* blobs,
                                      const uint64_t* chunk_start, uint64_t n_blobs, uint64_t total_chunks,
-                                     hipStream_t s) {
-    if (!n_blobs || !total_chunks) return hipSuccess;
+                                     hipStream_t s, uint64_t* grid) {
+    if (!n_blobs || !total_chunks) {
+        if (grid) *grid = 0;
+        return hipSuccess;
+    }
     // short-lived workgroups of SDA_SNAP_CHUNKS_PER_WG chunks each: the dispatcher balances the
     // ragged tail better than long walks (A/B in profiles/r01h/ab_snapshot.txt)
     const uint64_t cpw = total_chunks / SDA_SNAP_CHUNKS_PER_WG < 0x7fffffffull
                              ? SDA_SNAP_CHUNKS_PER_WG : total_chunks / 0x7fffffffull + 1;
-    const uint64_t g = (total_chunks + cpw - 1) / cpw;
+    uint64_t g = (total_chunks + cpw - 1) / cpw;
+    // the kernel forms total_chunks * (w + 1), w < g, in 64 bits: from about 6 * 2^31 chunks on the capped grid
+    // would wrap it, so the grid shrinks further there (below 2^32 chunks g * total_chunks < 2^64 as it is)
+    if (g > UINT64_MAX / total_chunks) g = UINT64_MAX / total_chunks;
     snapshot_transpose_kernel<<<dim3((uint32_t)g), dim3(kThreads), 0, s>>>(src, dst, blobs, chunk_start, n_blobs,
                                                                           total_chunks);
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (grid && e == hipSuccess) *grid = g;      // as decided here (sda_snapshot_last_launch)
+    return e;
 }
 
 }  // namespace sda

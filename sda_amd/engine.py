@@ -127,6 +127,7 @@ SIGNATURES = [
     ("sda_chacha_last_launch", _st, [_vp, _u32p, _u64p, _u64p]),
     ("sda_codec_last_launch", _st, [_vp, _u32p, _u32p, _u32p, _u64p]),
     ("sda_combine_last_launch", _st, [_vp, _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, _u32p, _u32p, _u32p]),
+    ("sda_snapshot_last_launch", _st, [_vp, _u64p, _u64p, _u64p, _u64p, _u32p]),
     ("sda_combine_split_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     ("sda_combine_split_prefix_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp,
                                            _vp]),
@@ -555,6 +556,14 @@ class Engine:
         v = [C.c_uint32() for _ in range(5)] + [C.c_uint64()] + [C.c_uint32() for _ in range(3)]
         _check(self.lib.sda_combine_last_launch(self.h, *[C.byref(x) for x in v]))
         return CombineLaunch(*[int(x.value) for x in v])
+
+    def snapshot_last_launch(self):
+        """(blobs, chunks, grid, chunk_bytes, shifts) of the handle's last snapshot_transpose_dev with a dst: the
+        non-empty blobs planned, their chunks, the workgroups launched, the kernel's chunk size and the set of
+        (src - dst) mod 16 the blobs had, bit s for shift s (sda_snapshot_last_launch)."""
+        v = [C.c_uint64() for _ in range(4)] + [C.c_uint32()]
+        _check(self.lib.sda_snapshot_last_launch(self.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
 
     def combine_finalize_dev(self, modulus, sums_ptr, dim, out_ptr, stream=None):
         _check(self.lib.sda_combine_finalize_dev(self.h, modulus, sums_ptr, dim, out_ptr, stream))

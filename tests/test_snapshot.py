@@ -69,7 +69,9 @@ def _run_device(engine, blobs, pad_front=0):
                                        (3, 4, 16_000, 40_000), (200, 26, 0, 64)])
 @pytest.mark.parametrize("pad_front", [0, 5])
 def test_gpu_transpose_matches_oracle(engine, oracle, P, n, lo, hi, pad_front):
-    """every source/destination misalignment, blobs shorter than a quad, blobs across 16 KiB chunks"""
+    """random ragged snapshots: blobs shorter than a quad, empty blobs, one shape with blobs across the 32 KiB
+    chunks.  The source/destination misalignments these happen to produce are not the coverage: every shift, start
+    and chunk boundary is covered by construction in the matrix file (tests/test_gpu_snapshot_matrix.py)."""
     blobs = _ragged(np.random.default_rng(P * 7 + n + pad_front), P, n, lo, hi)
     got, base, coff = _run_device(engine, blobs, pad_front)
     assert got == oracle.snapshot_transpose(blobs)
