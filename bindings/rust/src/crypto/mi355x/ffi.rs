@@ -167,6 +167,13 @@ extern "C" {
                          out: *mut i64, stream: *mut c_void) -> SdaStatus;
     pub fn sda_draws(h: *mut SdaEngine, key: *const u32, stream_id: u32, first: u64, count: u64, bound: i64,
                      out: *mut i64, out_cap: u64) -> SdaStatus;
+    // Additive share generation with the draws made inside the kernel; the 32 form writes int32 rows (m <= 2^31)
+    pub fn sda_additive_generate_keyed_dev(h: *mut SdaEngine, modulus: i64, share_count: u64, secrets: *const i64,
+                                           dimension: u64, key: *const u32, stream_id: u32, first_column: u64,
+                                           out: *mut i64, out_stride: u64, stream: *mut c_void) -> SdaStatus;
+    pub fn sda_additive_generate_keyed32_dev(h: *mut SdaEngine, modulus: i64, share_count: u64, secrets: *const i64,
+                                             dimension: u64, key: *const u32, stream_id: u32, first_column: u64,
+                                             out: *mut i32, out_stride: u64, stream: *mut c_void) -> SdaStatus;
 
     // ---- share payload codec (sodium.rs:36-41, :82-88) ----
     pub fn sda_varint_encode(h: *mut SdaEngine, vals: *const i64, n: u64, out: *mut u8, out_cap: u64,
@@ -214,6 +221,18 @@ extern "C" {
                                        secrets: *const i64, dimension: u64, draws: *const i64, mode: i32,
                                        shares_out: *mut i32, payload: *mut u8, payload_cap: u64,
                                        payload_row_bytes: *mut u64, stream: *mut c_void) -> SdaStatus;
+    // the two calls above with the share-generation draws made on the device from (key, stream_id); the 32 form
+    // takes an Additive scheme with modulus <= 2^31
+    pub fn sda_participant_share_keyed_dev(h: *mut SdaEngine, ms: *const SdaMaskingScheme, seed: *const u32,
+                                           seed_words: u64, full_masks: *const i64, ss: *const SdaSharingScheme,
+                                           secrets: *const i64, dimension: u64, key: *const u32, stream_id: u32,
+                                           mode: i32, shares_out: *mut i64, payload: *mut u8, payload_cap: u64,
+                                           payload_row_bytes: *mut u64, stream: *mut c_void) -> SdaStatus;
+    pub fn sda_participant_share32_keyed_dev(h: *mut SdaEngine, ms: *const SdaMaskingScheme, seed: *const u32,
+                                             seed_words: u64, full_masks: *const i64, ss: *const SdaSharingScheme,
+                                             secrets: *const i64, dimension: u64, key: *const u32, stream_id: u32,
+                                             mode: i32, shares_out: *mut i32, payload: *mut u8, payload_cap: u64,
+                                             payload_row_bytes: *mut u64, stream: *mut c_void) -> SdaStatus;
 
     // ---- synthetic benchmark input ----
     pub fn sda_synth_fill_dev(h: *mut SdaEngine, dst: *mut i64, rows: u64, cols: u64, seed: u64, lo: i64, hi: i64,

@@ -27,7 +27,9 @@
  *     end of the call instead, so no GPU idle gap opens inside them.
  *   - Randomness is explicit.  Where the reference draws from OsRng the caller
  *     passes the drawn values (or, for ChaCha masking, the seed words) -- or, through the `_keyed` entry
- *     points and sda_draws_dev, one 256-bit OS-RNG key that the device expands into the draws.
+ *     points and sda_draws_dev, one 256-bit OS-RNG key that the device expands into the draws.  Keyed
+ *     Additive generation (sda_additive_generate_keyed_dev, sda_participant_share_keyed_dev and their 32 forms)
+ *     makes the draws inside the share kernel: they never exist as a buffer.
  *   - Every function returns an sda_status; 0 = OK.  The codes 1..6 map 1:1 to
  *     the reference's error strings; sda_last_error_message() gives details.
  *   - A handle may be used from one thread at a time (the Rust trait objects
@@ -450,6 +452,33 @@ sda_status sda_draws_dev(sda_engine* h, const uint32_t* key, uint32_t stream_id,
 sda_status sda_draws(sda_engine* h, const uint32_t* key, uint32_t stream_id, uint64_t first,
                      uint64_t count, int64_t bound, int64_t* out, uint64_t out_cap);
 
+/* Additive share generation with the draws made inside the kernel: column d < dimension of
+ * `secrets` (device) is absolute column c = first_column + d of the job and takes draws c (n - 1) + j, j < n - 1,
+ * of (key, stream_id) at bound = modulus (n = share_count), so
+ *   out[j * out_stride + d] = draw(c (n - 1) + j)                      for j < n - 1, and
+ *   out[(n - 1) * out_stride + d] = the fold of additive.rs:47 over them in order from the raw secret,
+ * which is bit-identical to sda_draws_dev(key, stream_id, first_column (n - 1), dimension (n - 1), modulus) fed to
+ * sda_additive_generate_dev, without the draws ever being a buffer.  n = 1 draws nothing and writes the secrets
+ * unreduced.  first_column lets a caller split one job's columns over calls, devices or streams: any split gives
+ * the same shares.  out: device, rows out_stride elements apart (columns past `dimension` of a row are not
+ * written).  Only enqueues; runs on ordinals[0] of a multi-device handle.  sda_draws_dev's KEY CONTRACT applies
+ * verbatim.
+ * The 32 form writes int32 rows (4-byte alignment is enough, any dimension), equal to (int32_t) of the i64 form's:
+ * with modulus <= 2^31 every draw lies in [0, m) and the last share in (-m, m), so each share fits by construction.
+ * Checks, in this order: a NULL handle, key or needed buffer -> SDA_ERR_INVALID_ARGUMENT; share_count == 0 ->
+ * SDA_ERR_PRECONDITION (share_count - 1 underflows); modulus <= 0 -> SDA_ERR_PRECONDITION ("Rng.gen_range called
+ * with low >= high"); out_stride < dimension -> SDA_ERR_INVALID_ARGUMENT; (first_column + dimension) *
+ * (share_count - 1) wrapping past 2^64 -> SDA_ERR_INVALID_ARGUMENT; the 32 form with modulus > 2^31 ->
+ * SDA_ERR_UNSUPPORTED; dimension == 0 -> SDA_OK, nothing launched.  A refused call writes nothing. */
+sda_status sda_additive_generate_keyed_dev(sda_engine* h, int64_t modulus, uint64_t share_count,
+                                           const int64_t* secrets, uint64_t dimension, const uint32_t* key,
+                                           uint32_t stream_id, uint64_t first_column, int64_t* out,
+                                           uint64_t out_stride, void* stream);
+sda_status sda_additive_generate_keyed32_dev(sda_engine* h, int64_t modulus, uint64_t share_count,
+                                             const int64_t* secrets, uint64_t dimension, const uint32_t* key,
+                                             uint32_t stream_id, uint64_t first_column, int32_t* out,
+                                             uint64_t out_stride, void* stream);
+
 /* ---------------- share payload codec ----------------
  * Encryptor::encrypt encodes shares with integer-encoding 1.0 VarInt before sealing
  * (client/src/crypto/encryption/sodium.rs:36-41); Decryptor::decrypt decodes after opening
@@ -560,7 +589,8 @@ sda_status sda_participant_share_dev(sda_engine* h, const sda_masking_scheme* ms
  * rejection check and its redo of every later step included), sda_chacha_last_launch, sda_packed_fixup_count,
  * payload == NULL and the waits are those of sda_participant_share_dev.
  * PackedShamir only: an Additive scheme returns SDA_ERR_UNSUPPORTED, because its first n - 1 shares are the
- * caller's draws copied verbatim and the engine does not range-check them, so they need not fit int32.
+ * caller's draws copied verbatim and the engine does not range-check them, so they need not fit int32
+ * (sda_participant_share32_keyed_dev, whose draws are the engine's own, takes Additive).
  * At n + 1 = 81 the SDA_ERR_OUT_OF_MEMORY contract of sda_packed_generate32_dev applies (n * B * 8 bytes of
  * handle-owned scratch; shares_out and payload are untouched when it cannot be allocated). */
 sda_status sda_participant_share32_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
@@ -568,6 +598,34 @@ sda_status sda_participant_share32_dev(sda_engine* h, const sda_masking_scheme* 
                                        const sda_sharing_scheme* ss, const int64_t* secrets, uint64_t dimension,
                                        const int64_t* draws, int32_t mode, int32_t* shares_out, uint8_t* payload,
                                        uint64_t payload_cap, uint64_t* payload_row_bytes, void* stream);
+
+/* sda_participant_share_dev with the share-generation draws made on the device from (key, stream_id) instead of
+ * passed in (key: HOST, 8 words; sda_draws_dev's KEY CONTRACT applies verbatim).  shares_out, payload and
+ * payload_row_bytes are bit-identical to sda_participant_share_dev fed with sda_draws_dev(key, stream_id, 0, count,
+ * bound) -- Additive: count = D (n - 1), bound = modulus, made inside the share kernel
+ * (sda_additive_generate_keyed_dev with first_column 0); PackedShamir: count = B t, bound = p - 1, into
+ * handle-owned scratch ahead of the unchanged share generation.  Everything else is sda_participant_share_dev's:
+ * the masking (full_masks is still passed in, because the mask must also reach the recipient: make it with
+ * sda_draws_dev under another stream_id), the ChaCha rejection redo (share generation runs again and, under the
+ * same key, makes the same shares), the payload encode, the waits, sda_chacha_last_launch and
+ * sda_packed_fixup_count.  A NULL key -> SDA_ERR_INVALID_ARGUMENT. */
+sda_status sda_participant_share_keyed_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                           uint64_t seed_words, const int64_t* full_masks,
+                                           const sda_sharing_scheme* ss, const int64_t* secrets,
+                                           uint64_t dimension, const uint32_t* key, uint32_t stream_id,
+                                           int32_t mode, int64_t* shares_out, uint8_t* payload,
+                                           uint64_t payload_cap, uint64_t* payload_row_bytes, void* stream);
+
+/* sda_participant_share32_dev likewise.  Unlike the unkeyed form it takes an Additive scheme with modulus <= 2^31:
+ * the engine makes the first n - 1 shares itself, in [0, m), and the last is a `% m` result, so every share fits
+ * int32 by construction and flows on to sda_combine32_dev, sda_varint_encode32_dev and the clerk's int32 decode.
+ * An Additive modulus above 2^31 -> SDA_ERR_UNSUPPORTED (a draw need not fit int32). */
+sda_status sda_participant_share32_keyed_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                             uint64_t seed_words, const int64_t* full_masks,
+                                             const sda_sharing_scheme* ss, const int64_t* secrets,
+                                             uint64_t dimension, const uint32_t* key, uint32_t stream_id,
+                                             int32_t mode, int32_t* shares_out, uint8_t* payload,
+                                             uint64_t payload_cap, uint64_t* payload_row_bytes, void* stream);
 
 /* Synthetic benchmark input: dst[r*cols + c] = lo + splitmix64(seed, r, c) % (hi - lo). */
 sda_status sda_synth_fill_dev(sda_engine* h, int64_t* dst, uint64_t rows, uint64_t cols,

@@ -10,56 +10,19 @@
 //   otherwise round r + 1, same block counter and position; round 63 is taken unconditionally.
 // An element depends only on (key, stream_id, i, bound): any sub-range, device split or launch shape gives
 // the same values.  chacha.hip's block function keeps state words 14 and 15 at zero (rand 0.3's stream), so
-// this file carries its own with the two extra words.
+// draws_common.h carries its own with the two extra words, shared with additive_keyed.hip.
 //
 // One lane expands one block (8 draws).  The grid is laid out in absolute block indices from first >> 3, so
 // `first` need not be a multiple of 8: the first and last block's elements outside [first, first + count)
 // are computed and never stored.  A workgroup's 2048 results go through LDS so that lane t stores element
 // t + 256 j: each store instruction writes 512 contiguous bytes, once, nontemporal.
-#include "kernels.h"
+#include "draws_common.h"
 
 namespace sda {
 
 namespace {
 
-constexpr uint32_t C0 = 0x61707865u, C1 = 0x3320646Eu, C2 = 0x79622D32u, C3 = 0x6B206574u;
-constexpr uint32_t kLastRound = 63;            // the retry round whose value is taken unconditionally
-constexpr int kPad = 9;                        // LDS row stride (u64) of a lane's 8 results
 static_assert(kDrawsTile == 256 * 8, "one lane per block of 8 draws, 256 lanes per workgroup");
-
-struct DrawKey { uint32_t k[8]; };
-
-__device__ __forceinline__ uint32_t rotl(uint32_t x, int r) { return __builtin_amdgcn_alignbit(x, x, 32 - r); }
-
-#define SDA_DQR(a, b, c, d)                   \
-    a += b; d ^= a; d = rotl(d, 16);          \
-    c += d; b ^= c; b = rotl(b, 12);          \
-    a += b; d ^= a; d = rotl(d, 8);           \
-    c += d; b ^= c; b = rotl(b, 7);
-
-// core(state) with state words 14 = stream_id, 15 = round
-__device__ __forceinline__ void draw_block(const DrawKey& K, uint64_t counter, uint32_t stream_id, uint32_t round,
-                                           uint32_t (&o)[16]) {
-    const uint32_t* key = K.k;
-    uint32_t x0 = C0, x1 = C1, x2 = C2, x3 = C3;
-    uint32_t x4 = key[0], x5 = key[1], x6 = key[2], x7 = key[3];
-    uint32_t x8 = key[4], x9 = key[5], x10 = key[6], x11 = key[7];
-    uint32_t x12 = (uint32_t)counter, x13 = (uint32_t)(counter >> 32), x14 = stream_id, x15 = round;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        SDA_DQR(x0, x4, x8, x12); SDA_DQR(x1, x5, x9, x13); SDA_DQR(x2, x6, x10, x14); SDA_DQR(x3, x7, x11, x15);
-        SDA_DQR(x0, x5, x10, x15); SDA_DQR(x1, x6, x11, x12); SDA_DQR(x2, x7, x8, x13); SDA_DQR(x3, x4, x9, x14);
-    }
-    o[0] = x0 + C0; o[1] = x1 + C1; o[2] = x2 + C2; o[3] = x3 + C3;
-    o[4] = x4 + key[0]; o[5] = x5 + key[1]; o[6] = x6 + key[2]; o[7] = x7 + key[3];
-    o[8] = x8 + key[4]; o[9] = x9 + key[5]; o[10] = x10 + key[6]; o[11] = x11 + key[7];
-    o[12] = x12 + (uint32_t)counter; o[13] = x13 + (uint32_t)(counter >> 32);
-    o[14] = x14 + stream_id; o[15] = x15 + round;
-}
-#undef SDA_DQR
-
-// v % bound: the 64-bit Barrett `%` of modarith.h, for every bound in [1, 2^63)
-__device__ __forceinline__ uint64_t draw_mod(uint64_t v, const Mod64& M) { return umod64(v, M); }
 
 // out[p] = draw(first + p), p < count.  Workgroup x owns blocks blk0 + 256 x + lane (blk0 = first >> 3); wg0 is
 // the grid slice's first workgroup (launch_draws slices grids past 2^30 workgroups).
@@ -71,32 +34,7 @@ __global__ __launch_bounds__(256) void draws_kernel(DrawKey key, uint32_t stream
     const uint64_t wg = wg0 + blockIdx.x;
     const uint64_t blk = (first >> 3) + wg * 256 + tid;      // cannot wrap: the host checked first + count
     uint64_t res[8];
-    uint32_t rej = 0;                                        // bit q: element q still waits for an accepted value
-    {
-        uint32_t o[16];
-        draw_block(key, blk, stream_id, 0u, o);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const uint64_t v = ((uint64_t)o[2 * q] << 32) | o[2 * q + 1];   // high word first
-            rej |= v < zone ? 0u : (1u << q);                // the one accept/retry decision, for every bound
-            res[q] = draw_mod(v, M);
-        }
-    }
-    // Retries, per element: round r of block `blk` serves every element of the lane still waiting at r, each
-    // at its own position.  Rare for the shipped moduli (< 2^-32 per draw below 2^32), about one element in
-    // three for bounds near 2^64 / 3; elements outside [first, first + count) retry too and are never stored.
-    for (uint32_t r = 1; rej != 0 && r <= kLastRound; ++r) {
-        uint32_t o[16];
-        draw_block(key, blk, stream_id, r, o);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const uint64_t v = ((uint64_t)o[2 * q] << 32) | o[2 * q + 1];
-            if ((rej >> q) & 1u) {
-                res[q] = draw_mod(v, M);
-                if (v < zone) rej &= ~(1u << q);             // at r == kLastRound the value stands either way
-            }
-        }
-    }
+    draw_eight(key, blk, stream_id, M, zone, res);
 #pragma unroll
     for (int q = 0; q < 8; ++q) st[tid * kPad + q] = res[q];
     __syncthreads();

@@ -327,6 +327,7 @@ void sda_engine_destroy(sda_engine* h) {
     dev_free(h->work);
     dev_free(h->gen_log);
     dev_free(h->gen32_tmp);
+    dev_free(h->keyed_draws);
     dev_free(h->codec_work);
     dev_free(h->codec_mat);
     dev_free(h->pipe);

@@ -265,6 +265,53 @@ sda_status sda_additive_generate_dev(sda_engine* h, int64_t modulus, uint64_t sh
     return ok();
 }
 
+}  // extern "C"
+
+// Both keyed Additive entry points: the header's checks in its order, then the fused kernel (additive_keyed.hip).
+template <typename Out>
+static sda_status additive_generate_keyed(sda_engine* h, int64_t modulus, uint64_t share_count, const int64_t* secrets,
+                                          uint64_t dimension, const uint32_t* key, uint32_t stream_id,
+                                          uint64_t first_column, Out* out, uint64_t out_stride, void* stream) {
+    if (!h || !key || (dimension && (!secrets || !out)))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle, key or needed buffer");
+    if (share_count == 0) return fail(SDA_ERR_PRECONDITION, "share_count - 1 underflows (additive.rs:42)");
+    if (modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
+    if (out_stride < dimension) return fail(SDA_ERR_INVALID_ARGUMENT, "out_stride is smaller than the dimension");
+    uint64_t end, elems;
+    if (share_count > 1 && (__builtin_add_overflow(first_column, dimension, &end) ||
+                            __builtin_mul_overflow(end, share_count - 1, &elems)))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "(first_column + dimension) * (share_count - 1) wraps past 2^64");
+    if (sizeof(Out) == 4 && modulus > (int64_t)1 << 31)
+        return fail(SDA_ERR_UNSUPPORTED, "int32 shares need modulus <= 2^31: a draw in [0, modulus) need not fit int32");
+    if (dimension == 0) return ok();
+    HIP_TRY(hipSetDevice(h->device));
+    int64_t* o64 = nullptr;
+    int32_t* o32 = nullptr;
+    if constexpr (sizeof(Out) == 4) o32 = out; else o64 = out;
+    HIP_TRY(sda::launch_additive_generate_keyed(key, stream_id, first_column, secrets, dimension, share_count, modulus,
+                                                o64, o32, out_stride, pick(h, stream)));
+    return ok();
+}
+
+extern "C" {
+
+sda_status sda_additive_generate_keyed_dev(sda_engine* h, int64_t modulus, uint64_t share_count, const int64_t* secrets,
+                                           uint64_t dimension, const uint32_t* key, uint32_t stream_id,
+                                           uint64_t first_column, int64_t* out, uint64_t out_stride, void* stream) {
+    SDA_ENTRY;
+    return additive_generate_keyed(h, modulus, share_count, secrets, dimension, key, stream_id, first_column, out,
+                                   out_stride, stream);
+}
+
+sda_status sda_additive_generate_keyed32_dev(sda_engine* h, int64_t modulus, uint64_t share_count,
+                                             const int64_t* secrets, uint64_t dimension, const uint32_t* key,
+                                             uint32_t stream_id, uint64_t first_column, int32_t* out,
+                                             uint64_t out_stride, void* stream) {
+    SDA_ENTRY;
+    return additive_generate_keyed(h, modulus, share_count, secrets, dimension, key, stream_id, first_column, out,
+                                   out_stride, stream);
+}
+
 sda_status sda_chacha_mask_combine_dev(sda_engine* h, int64_t modulus, uint64_t dimension, const uint32_t* seeds,
                                        uint64_t w, uint64_t n_seeds, int64_t* out, void* stream) {
     SDA_ENTRY;

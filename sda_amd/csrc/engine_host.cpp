@@ -428,16 +428,20 @@ sda_status host_additive_generate(sda_engine* h, int64_t m, uint64_t n, const in
         sda_engine* d = dev_of(h, g);
         HIP_TRY(hipSetDevice(d->device));
         DevArena a;
-        if (sda_status e = stage(d, rup(w * 8) + rup(w * (n - 1) * 8 + 8) + rup(n * w * 8), &a)) return e;
+        // keyed: the fused kernel draws in registers (additive_keyed.hip), so no draws are staged
+        if (sda_status e = stage(d, rup(w * 8) + (kd ? 0 : rup(w * (n - 1) * 8 + 8)) + rup(n * w * 8), &a)) return e;
         int64_t* dsec = a.take<int64_t>(w);
-        int64_t* ddr = a.take<int64_t>(w * (n - 1) + 1);
+        int64_t* ddr = kd ? nullptr : a.take<int64_t>(w * (n - 1) + 1);
         int64_t* dout = a.take<int64_t>(n * w);
         HIP_TRY(hipMemcpyAsync(dsec, secrets + lo, w * 8, hipMemcpyHostToDevice, d->stream));
-        if (n > 1 && kd)      // element d * (n - 1) + j of the call's draws: this slice starts at column lo
-            HIP_TRY(sda::launch_draws(kd->key, kd->stream_id, lo * (n - 1), w * (n - 1), m, ddr, d->stream));
-        else if (n > 1)
-            HIP_TRY(hipMemcpyAsync(ddr, draws + lo * (n - 1), w * (n - 1) * 8, hipMemcpyHostToDevice, d->stream));
-        HIP_TRY(sda::launch_additive_generate(dsec, w, ddr, n, dout, m, d->stream));
+        if (kd) {             // column lo + c of the call takes draws (lo + c) * (n - 1) + j: first_column = lo
+            HIP_TRY(sda::launch_additive_generate_keyed(kd->key, kd->stream_id, lo, dsec, w, n, m, dout, nullptr, w,
+                                                        d->stream));
+        } else {
+            if (n > 1)
+                HIP_TRY(hipMemcpyAsync(ddr, draws + lo * (n - 1), w * (n - 1) * 8, hipMemcpyHostToDevice, d->stream));
+            HIP_TRY(sda::launch_additive_generate(dsec, w, ddr, n, dout, m, d->stream));
+        }
         HIP_TRY(hipMemcpy2DAsync(out + lo, D * 8, dout, w * 8, w * 8, n, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(hipStreamSynchronize(d->stream));
         return SDA_OK;

@@ -42,6 +42,8 @@ struct sda_engine {
     bool gen_log_used = false;    // the last packed launch zeroed gen_log's count and logs into it
     void* gen32_tmp = nullptr;    // sda_packed_generate32_dev at n + 1 = 81: i64 shares before the narrowing pass
     size_t gen32_tmp_bytes = 0;
+    void* keyed_draws = nullptr;  // sda_participant_share*_keyed_dev, PackedShamir: the B * t draws made on the device
+    size_t keyed_draws_bytes = 0;
     void* codec_work = nullptr;   // varint codec plan / scan workspace
     size_t codec_work_bytes = 0;
     void* codec_mat = nullptr;    // decoded [N][len] matrix of the clerk decode+combine path

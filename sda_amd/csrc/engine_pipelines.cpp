@@ -220,21 +220,24 @@ sda_status sda_recipient_reveal(sda_engine* h, const sda_masking_scheme* ms, con
     return finish(h);
 }
 
-// The participant pipeline behind sda_participant_share_dev and sda_participant_share32_dev.  One of shares64 /
-// shares32 is the [n][B] output (shares32: int32 rows, PackedShamir only, encoded by the int32 encoder).
+// The participant pipeline behind sda_participant_share_dev, sda_participant_share32_dev and their keyed forms.
+// One of shares64 / shares32 is the [n][B] output (shares32: int32 rows, encoded by the int32 encoder; PackedShamir,
+// and keyed Additive up to modulus 2^31).  kd (the keyed forms): `draws` is NULL and the share-generation draws
+// come from (kd->key, kd->stream_id) -- Additive in the fused kernel, PackedShamir into h->keyed_draws.
 static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
                                     uint64_t seed_words, const int64_t* full_masks, const sda_sharing_scheme* ss,
                                     const int64_t* secrets, uint64_t dimension, const int64_t* draws, int32_t mode,
                                     int64_t* shares64, int32_t* shares32, uint8_t* payload, uint64_t payload_cap,
-                                    uint64_t* payload_row_bytes, void* stream) {
-    if (!h || !ms || !ss || (dimension && (!secrets || (!shares64 && !shares32))) || (payload && !payload_row_bytes))
+                                    uint64_t* payload_row_bytes, void* stream, const KeyedDraws* kd = nullptr) {
+    if (!h || !ms || !ss || (dimension && (!secrets || (!shares64 && !shares32))) || (payload && !payload_row_bytes) ||
+        (kd && !kd->key))
         return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = pick(h, stream);
     const uint64_t D = dimension;
     const bool packed = ss->kind == SDA_SHARING_PACKED_SHAMIR;
     if (!packed && ss->kind != SDA_SHARING_ADDITIVE) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown sharing scheme kind");
-    if (!packed && shares32)
+    if (!packed && shares32 && !kd)
         return fail(SDA_ERR_UNSUPPORTED, "int32 shares need a PackedShamir scheme: an additive scheme's first n - 1 "
                                          "shares are the caller's draws, copied unchecked");
     if (mode != SDA_REVEAL_EXACT && mode != SDA_REVEAL_CANONICAL) return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
@@ -243,6 +246,9 @@ static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms,
     } else {
         if (ss->share_count == 0) return fail(SDA_ERR_PRECONDITION, "share_count - 1 underflows (additive.rs:42)");
         if (ss->modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
+        if (shares32 && ss->modulus > (int64_t)1 << 31)
+            return fail(SDA_ERR_UNSUPPORTED, "int32 shares of an additive scheme need modulus <= 2^31: its first n - 1 "
+                                             "shares are draws in [0, modulus), which need not fit int32");
     }
     // 1. SecretMasker::mask (participate.rs:53-54)
     const int64_t* masked = secrets;
@@ -292,14 +298,25 @@ static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms,
     // 2. ShareGenerator::generate (participate.rs:75-76): shares [n][B]
     const uint64_t n = ss->share_count;
     const uint64_t B = packed ? (D + ss->secret_count - 1) / ss->secret_count : D;
-    if (B && !draws) return fail(SDA_ERR_INVALID_ARGUMENT, "need the randomness draws");
+    if (B && !draws && !kd) return fail(SDA_ERR_INVALID_ARGUMENT, "need the randomness draws");
     if (payload && n > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 clerks");
+    if (kd && packed && B) {     // the B * t draws of (key, stream_id) at bound p - 1, where the caller's would be
+        const uint64_t count = B * ss->privacy_threshold;
+        if (sda_status e = ensure(&h->keyed_draws, &h->keyed_draws_bytes, rup(count * 8 + 8))) return e;
+        draws = static_cast<const int64_t*>(h->keyed_draws);
+    }
     auto share_and_encode = [&]() -> sda_status {
         if (B) {
             if (packed) {
+                if (kd)
+                    HIP_TRY(sda::launch_draws(kd->key, kd->stream_id, 0, B * ss->privacy_threshold, ss->modulus - 1,
+                                              static_cast<int64_t*>(h->keyed_draws), st));
                 sda::PackedGenArgs ga{masked, D, 1, draws, shares64, mode == SDA_REVEAL_CANONICAL};
                 ga.out32 = shares32;             // as sda_packed_generate32_dev: scratch + narrowing at n + 1 = 81
                 if (sda_status e = packed_generate(h, ss, ga, st)) return e;
+            } else if (kd) {
+                HIP_TRY(sda::launch_additive_generate_keyed(kd->key, kd->stream_id, 0, masked, D, n, ss->modulus,
+                                                            shares64, shares32, B, st));
             } else {
                 HIP_TRY(sda::launch_additive_generate(masked, D, draws, n, shares64, ss->modulus, st));
             }
@@ -351,6 +368,31 @@ sda_status sda_participant_share32_dev(sda_engine* h, const sda_masking_scheme* 
     SDA_ENTRY;
     return participant_share(h, ms, seed, seed_words, full_masks, ss, secrets, dimension, draws, mode, nullptr,
                              shares_out, payload, payload_cap, payload_row_bytes, stream);
+}
+
+// The two calls above with the share-generation draws made on the device from (key, stream_id).
+sda_status sda_participant_share_keyed_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                           uint64_t seed_words, const int64_t* full_masks,
+                                           const sda_sharing_scheme* ss, const int64_t* secrets, uint64_t dimension,
+                                           const uint32_t* key, uint32_t stream_id, int32_t mode, int64_t* shares_out,
+                                           uint8_t* payload, uint64_t payload_cap, uint64_t* payload_row_bytes,
+                                           void* stream) {
+    SDA_ENTRY;
+    const KeyedDraws kd{key, stream_id};
+    return participant_share(h, ms, seed, seed_words, full_masks, ss, secrets, dimension, nullptr, mode, shares_out,
+                             nullptr, payload, payload_cap, payload_row_bytes, stream, &kd);
+}
+
+sda_status sda_participant_share32_keyed_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                             uint64_t seed_words, const int64_t* full_masks,
+                                             const sda_sharing_scheme* ss, const int64_t* secrets, uint64_t dimension,
+                                             const uint32_t* key, uint32_t stream_id, int32_t mode,
+                                             int32_t* shares_out, uint8_t* payload, uint64_t payload_cap,
+                                             uint64_t* payload_row_bytes, void* stream) {
+    SDA_ENTRY;
+    const KeyedDraws kd{key, stream_id};
+    return participant_share(h, ms, seed, seed_words, full_masks, ss, secrets, dimension, nullptr, mode, nullptr,
+                             shares_out, payload, payload_cap, payload_row_bytes, stream, &kd);
 }
 
 }  // extern "C"

@@ -317,6 +317,17 @@ constexpr uint32_t kDrawsTile = 2048;
 hipError_t launch_draws(const uint32_t* key_host, uint32_t stream_id, uint64_t first, uint64_t count, int64_t bound,
                         int64_t* out, hipStream_t s);
 
+// ---- additive_keyed.hip ----
+// Columns one workgroup of the fused Additive kernel owns; sda_amd/engine.py restates it as ADDITIVE_KEYED_TILE.
+constexpr uint32_t kAdditiveKeyedTile = 512;
+// Additive share generation with the draws made in the kernel: column d < D of `secrets` (device) takes draws
+// (first_column + d)(n - 1) + j, j < n - 1, of launch_draws' rule at bound = modulus, and share j of it goes to
+// out[j * out_stride + d] -- out64, or out32 (int32 rows) when that is given.  The caller has checked n >= 1,
+// modulus >= 1 (out32: modulus <= 2^31), out_stride >= D and that (first_column + D)(n - 1) does not wrap.
+hipError_t launch_additive_generate_keyed(const uint32_t* key_host, uint32_t stream_id, uint64_t first_column,
+                                          const int64_t* secrets, uint64_t D, uint64_t n, int64_t modulus,
+                                          int64_t* out64, int32_t* out32, uint64_t out_stride, hipStream_t s);
+
 // ---- snapshot.hip ----
 // One blob of the snapshot transposition: len bytes from src offset to dst offset.
 struct SnapshotCopy {

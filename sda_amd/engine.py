@@ -81,6 +81,10 @@ CombineLaunch = collections.namedtuple("CombineLaunch",
 # sda_draws_dev's grid gains a workgroup
 DRAWS_TILE = 2048
 
+# Columns one workgroup of the fused Additive kernel owns (csrc/kernels.h kAdditiveKeyedTile): the dimensions at
+# which sda_additive_generate_keyed_dev's grid gains a workgroup
+ADDITIVE_KEYED_TILE = 512
+
 _i64p = C.POINTER(C.c_int64)
 _u64p = C.POINTER(C.c_uint64)
 _u32p = C.POINTER(C.c_uint32)
@@ -179,6 +183,16 @@ SIGNATURES = [
     ("sda_participant_share32_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _u32p, C.c_uint64, _vp,
                                           C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, _vp, C.c_int32, _vp, _vp,
                                           C.c_uint64, _u64p, _vp]),
+    ("sda_additive_generate_keyed_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, _u32p, C.c_uint32,
+                                              C.c_uint64, _vp, C.c_uint64, _vp]),
+    ("sda_additive_generate_keyed32_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, _u32p, C.c_uint32,
+                                                C.c_uint64, _vp, C.c_uint64, _vp]),
+    ("sda_participant_share_keyed_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _u32p, C.c_uint64, _vp,
+                                              C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, _u32p, C.c_uint32,
+                                              C.c_int32, _vp, _vp, C.c_uint64, _u64p, _vp]),
+    ("sda_participant_share32_keyed_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _u32p, C.c_uint64, _vp,
+                                                C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, _u32p, C.c_uint32,
+                                                C.c_int32, _vp, _vp, C.c_uint64, _u64p, _vp]),
 ]
 
 _libs = {}
@@ -622,6 +636,24 @@ class Engine:
         _check(self.lib.sda_additive_generate_dev(self.h, modulus, share_count, secrets_ptr, dimension, draws_ptr,
                                                   out_ptr, stream))
 
+    def additive_generate_keyed_dev(self, modulus, share_count, secrets_ptr, dimension, key, stream_id, out_ptr,
+                                    out_stride, first_column=0, stream=None):
+        """Additive shares with the draws made inside the kernel (sda_additive_generate_keyed_dev): column d takes
+        draws (first_column + d) * (share_count - 1) + j of (key, stream_id); out is device i64, rows out_stride
+        apart.  key=None passes a NULL key (the status tests)."""
+        k = self._key(key) if key is not None else None
+        _check(self.lib.sda_additive_generate_keyed_dev(self.h, modulus, share_count, secrets_ptr, dimension,
+                                                        _ptr(k, _u32p) if k is not None else None, stream_id,
+                                                        first_column, out_ptr, out_stride, stream))
+
+    def additive_generate_keyed32_dev(self, modulus, share_count, secrets_ptr, dimension, key, stream_id, out_ptr,
+                                      out_stride, first_column=0, stream=None):
+        """additive_generate_keyed_dev with out as device int32 rows (modulus <= 2^31)."""
+        k = self._key(key) if key is not None else None
+        _check(self.lib.sda_additive_generate_keyed32_dev(self.h, modulus, share_count, secrets_ptr, dimension,
+                                                          _ptr(k, _u32p) if k is not None else None, stream_id,
+                                                          first_column, out_ptr, out_stride, stream))
+
     def chacha_mask_combine_dev(self, modulus, dimension, seeds_ptr, w, n_seeds, out_ptr, stream=None):
         _check(self.lib.sda_chacha_mask_combine_dev(self.h, modulus, dimension, seeds_ptr, w, n_seeds, out_ptr,
                                                     stream))
@@ -708,4 +740,36 @@ class Engine:
         _check(self.lib.sda_participant_share32_dev(self.h, C.byref(ms), _ptr(sd, _u32p), sd.size, full_masks_ptr,
                                                     C.byref(ss), secrets_ptr, dimension, draws_ptr, mode,
                                                     shares_ptr, payload_ptr, payload_cap, _ptr(rb, _u64p), stream))
+        return rb[:n]
+
+    def participant_share_keyed_dev(self, masking, sharing, secrets_ptr, dimension, key, stream_id, shares_ptr,
+                                    seed=None, full_masks_ptr=None, payload_ptr=None, payload_cap=0,
+                                    mode=REVEAL_EXACT, stream=None):
+        """participant_share_dev with the share-generation draws made on the device from (key, stream_id)
+        (sda_participant_share_keyed_dev); returns per-clerk payload byte counts."""
+        ms, ss = masking.c(), sharing.c()
+        sd = _arr(seed if seed is not None else [], np.uint32)
+        k = self._key(key)
+        n = sharing.output_size()
+        rb = np.zeros(max(n, 1), np.uint64)
+        _check(self.lib.sda_participant_share_keyed_dev(self.h, C.byref(ms), _ptr(sd, _u32p), sd.size, full_masks_ptr,
+                                                        C.byref(ss), secrets_ptr, dimension, _ptr(k, _u32p), stream_id,
+                                                        mode, shares_ptr, payload_ptr, payload_cap, _ptr(rb, _u64p),
+                                                        stream))
+        return rb[:n]
+
+    def participant_share32_keyed_dev(self, masking, sharing, secrets_ptr, dimension, key, stream_id, shares_ptr,
+                                      seed=None, full_masks_ptr=None, payload_ptr=None, payload_cap=0,
+                                      mode=REVEAL_EXACT, stream=None):
+        """participant_share_keyed_dev with shares_ptr as device int32 [n][B] (PackedShamir, and Additive up to
+        modulus 2^31) and the payload from the int32 encoder."""
+        ms, ss = masking.c(), sharing.c()
+        sd = _arr(seed if seed is not None else [], np.uint32)
+        k = self._key(key)
+        n = sharing.output_size()
+        rb = np.zeros(max(n, 1), np.uint64)
+        _check(self.lib.sda_participant_share32_keyed_dev(self.h, C.byref(ms), _ptr(sd, _u32p), sd.size,
+                                                          full_masks_ptr, C.byref(ss), secrets_ptr, dimension,
+                                                          _ptr(k, _u32p), stream_id, mode, shares_ptr, payload_ptr,
+                                                          payload_cap, _ptr(rb, _u64p), stream))
         return rb[:n]

@@ -1,0 +1,49 @@
+"""CPU: the fused Additive kernel's register, scratch and LDS budget (no GPU needed), read from the library the GPU
+tests load (scripts/code_objects.py, as tests/test_kernel_resources_draws.py does).  The figures are those DESIGN.md
+§4.9 states."""
+import importlib.util
+import os
+
+import pytest
+
+from sda_amd import engine as E
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_spec = importlib.util.spec_from_file_location("code_objects", os.path.join(ROOT, "scripts", "code_objects.py"))
+CO = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(CO)
+
+WANT = "additive_generate_keyed_kernel"
+INSTANCES = ("long", "int")                 # Out = int64_t, int32_t
+VGPR_BUDGET = 72                            # 512 / 72 = 7 waves per SIMD
+LDS_BYTES = (64 * 9 + 2) * 8                # one wave's chunk (64 lanes x 9 u64) + the two carry words
+CU_LDS, SIMDS, WAVES_PER_SIMD = 160 * 1024, 4, 7
+
+
+@pytest.fixture(scope="module")
+def kernels():
+    if not os.path.exists(E.LIB_PATH):
+        pytest.fail(f"{E.LIB_PATH} is not built (run __graft_entry__.build())")
+    rows = [k for k in CO.kernels(E.LIB_PATH) if k["pretty"].startswith(WANT + "<")]
+    return {k["pretty"][len(WANT) + 1:].split(">")[0]: k for k in rows}, rows
+
+
+def test_both_instantiations_exist_exactly_once(kernels):
+    by_type, rows = kernels
+    assert len(rows) == 2 and sorted(by_type) == sorted(INSTANCES), [k["pretty"] for k in rows]
+
+
+@pytest.mark.parametrize("out", INSTANCES)
+def test_no_agprs_scratch_or_spills(kernels, out):
+    k = kernels[0][out]
+    assert not k["agpr"] and not k["scratch"] and not k["vgpr_spill"] and not k["sgpr_spill"], k
+
+
+@pytest.mark.parametrize("out", INSTANCES)
+def test_seven_waves_per_simd(kernels, out):
+    """At most 72 VGPRs keeps 7 waves on a SIMD; a workgroup is one wave, and its LDS (a chunk of 512 results, the
+    same for every share_count) lets those 28 workgroups share a CU's 160 KiB."""
+    k = kernels[0][out]
+    assert k["vgpr"] <= VGPR_BUDGET and 512 // VGPR_BUDGET == WAVES_PER_SIMD, k["vgpr"]
+    assert k["lds"] == LDS_BYTES, k["lds"]
+    assert SIMDS * WAVES_PER_SIMD * k["lds"] <= CU_LDS
