@@ -174,6 +174,17 @@ extern "C" {
     pub fn sda_additive_generate_keyed32_dev(h: *mut SdaEngine, modulus: i64, share_count: u64, secrets: *const i64,
                                              dimension: u64, key: *const u32, stream_id: u32, first_column: u64,
                                              out: *mut i32, out_stride: u64, stream: *mut c_void) -> SdaStatus;
+    // Packed-Shamir share generation with the draws made in the share kernels (staged in handle-owned scratch for
+    // the schemes those kernels do not serve); the record tells which: path 1 in-kernel, 2 staged
+    pub fn sda_packed_generate_keyed_dev(h: *mut SdaEngine, s: *const SdaSharingScheme, secrets: *const i64,
+                                         dimension: u64, n_vectors: u64, key: *const u32, stream_id: u32,
+                                         first_batch: u64, out: *mut i64, mode: i32, stream: *mut c_void)
+                                         -> SdaStatus;
+    pub fn sda_packed_generate_keyed32_dev(h: *mut SdaEngine, s: *const SdaSharingScheme, secrets: *const i64,
+                                           dimension: u64, n_vectors: u64, key: *const u32, stream_id: u32,
+                                           first_batch: u64, out: *mut i32, mode: i32, stream: *mut c_void)
+                                           -> SdaStatus;
+    pub fn sda_packed_keyed_last_launch(h: *mut SdaEngine, path: *mut u32, staged_bytes: *mut u64) -> SdaStatus;
 
     // ---- share payload codec (sodium.rs:36-41, :82-88) ----
     pub fn sda_varint_encode(h: *mut SdaEngine, vals: *const i64, n: u64, out: *mut u8, out_cap: u64,

@@ -479,6 +479,36 @@ sda_status sda_additive_generate_keyed32_dev(sda_engine* h, int64_t modulus, uin
                                              uint32_t stream_id, uint64_t first_column, int32_t* out,
                                              uint64_t out_stride, void* stream);
 
+/* Packed-Shamir share generation with the draws made inside the share kernels: the keyed form of
+ * sda_packed_generate_mode_dev.  With B = ceil(dimension / k) batches per vector, batch b of vector v is absolute
+ * batch first_batch + v B + b of the job and takes draws (first_batch + v B + b) t + j, j < t, of (key, stream_id)
+ * at bound p - 1 as its randomness, so out [n_vectors][n][B] is bit-identical to
+ * sda_draws_dev(key, stream_id, first_batch t, n_vectors B t, p - 1) fed to sda_packed_generate_mode_dev (the 32
+ * form: to sda_packed_generate32_dev), in both modes, and sda_packed_fixup_count afterwards reports the same count
+ * as after that unkeyed call.  first_batch lets a caller split one job's batches over calls, devices or streams: any
+ * split gives the same shares.  Schemes the register kernels serve with n + 1 <= 27 make the draws in the share
+ * kernel's tile and never write them to device memory; every other scheme (n + 1 >= 81, k + t + 1 > 64, the
+ * workspace kernels) gets them from the draws kernel in scratch owned by the handle (n_vectors * B * t * 8 bytes,
+ * kept and reused until the handle is destroyed) ahead of the unkeyed kernels.  Only enqueues; runs on ordinals[0]
+ * of a multi-device handle.  sda_draws_dev's KEY CONTRACT applies verbatim.
+ * Checks, in this order: those of sda_packed_generate_mode_dev / sda_packed_generate32_dev (scheme kind, mode,
+ * the scheme's domain, the 65,535-vector limit, a NULL needed buffer); a NULL key -> SDA_ERR_INVALID_ARGUMENT;
+ * (first_batch + n_vectors * B) * t wrapping past 2^64 -> SDA_ERR_INVALID_ARGUMENT; on the staged path, scratch
+ * that cannot be allocated -> SDA_ERR_OUT_OF_MEMORY with out untouched.  A refused call writes nothing. */
+sda_status sda_packed_generate_keyed_dev(sda_engine* h, const sda_sharing_scheme* s, const int64_t* secrets,
+                                         uint64_t dimension, uint64_t n_vectors, const uint32_t* key,
+                                         uint32_t stream_id, uint64_t first_batch, int64_t* out, int32_t mode,
+                                         void* stream);
+sda_status sda_packed_generate_keyed32_dev(sda_engine* h, const sda_sharing_scheme* s, const int64_t* secrets,
+                                           uint64_t dimension, uint64_t n_vectors, const uint32_t* key,
+                                           uint32_t stream_id, uint64_t first_batch, int32_t* out, int32_t mode,
+                                           void* stream);
+/* How the last keyed packed-Shamir launch on the handle got its draws (the two entry points above, the keyed
+ * participant calls, sda_share_generate_keyed on its first device): *path = 0 none yet, 1 made in the share
+ * kernels, 2 staged; *staged_bytes = the draw bytes that crossed HBM (0 on path 1).  A host-side record: calls
+ * that launch nothing (dimension or n_vectors 0) and refused calls leave it as it was. */
+sda_status sda_packed_keyed_last_launch(sda_engine* h, uint32_t* path, uint64_t* staged_bytes);
+
 /* ---------------- share payload codec ----------------
  * Encryptor::encrypt encodes shares with integer-encoding 1.0 VarInt before sealing
  * (client/src/crypto/encryption/sodium.rs:36-41); Decryptor::decrypt decodes after opening
@@ -603,8 +633,9 @@ sda_status sda_participant_share32_dev(sda_engine* h, const sda_masking_scheme* 
  * passed in (key: HOST, 8 words; sda_draws_dev's KEY CONTRACT applies verbatim).  shares_out, payload and
  * payload_row_bytes are bit-identical to sda_participant_share_dev fed with sda_draws_dev(key, stream_id, 0, count,
  * bound) -- Additive: count = D (n - 1), bound = modulus, made inside the share kernel
- * (sda_additive_generate_keyed_dev with first_column 0); PackedShamir: count = B t, bound = p - 1, into
- * handle-owned scratch ahead of the unchanged share generation.  Everything else is sda_participant_share_dev's:
+ * (sda_additive_generate_keyed_dev with first_column 0); PackedShamir: count = B t, bound = p - 1, made as
+ * sda_packed_generate_keyed_dev with first_batch 0 makes them (sda_packed_keyed_last_launch tells where).
+ * Everything else is sda_participant_share_dev's:
  * the masking (full_masks is still passed in, because the mask must also reach the recipient: make it with
  * sda_draws_dev under another stream_id), the ChaCha rejection redo (share generation runs again and, under the
  * same key, makes the same shares), the payload encode, the waits, sda_chacha_last_launch and

@@ -15,8 +15,22 @@ sda_status packed_generate(sda_engine* h, const sda_sharing_scheme* s, sda::Pack
             ga.flag = ga.scratch + tmp / sizeof(int64_t);      // launch_narrow32's overflow word: never set here
         }
     }
+    uint32_t keyed_path = 0;
+    size_t staged = 0;
+    if (ga.key) {             // keyed: draws made in the share kernels (path 1), or staged in handle-owned scratch (2)
+        keyed_path = sda::packed_gen_keyed_in_kernel(ga, k, t, n, (uint32_t)s->modulus) ? 1 : 2;
+        staged = sda::packed_gen_keyed_scratch_bytes(ga, k, t, n, (uint32_t)s->modulus);
+        if (staged) {
+            if (sda_status e = ensure(&h->keyed_draws, &h->keyed_draws_bytes, rup(staged + 8))) return e;
+            ga.draw_scratch = static_cast<int64_t*>(h->keyed_draws);
+        }
+    }
     HIP_TRY(sda::launch_packed_generate(ga, k, t, n, (uint32_t)s->modulus, (uint32_t)s->omega_secrets,
                                         (uint32_t)s->omega_shares, h->gen_tab, h->gen_log, st, &h->gen_log_used));
+    if (keyed_path && ga.dimension && ga.n_vectors) {           // sda_packed_keyed_last_launch
+        h->keyed_path = keyed_path;
+        h->keyed_staged_bytes = staged;
+    }
     return SDA_OK;
 }
 
@@ -293,7 +307,58 @@ static sda_status additive_generate_keyed(sda_engine* h, int64_t modulus, uint64
     return ok();
 }
 
+// Both keyed packed entry points: the unkeyed entry points' checks in their order, then the key and the wrap.
+template <typename Out>
+static sda_status packed_generate_keyed(sda_engine* h, const sda_sharing_scheme* s, const int64_t* secrets,
+                                        uint64_t dimension, uint64_t n_vectors, const uint32_t* key,
+                                        uint32_t stream_id, uint64_t first_batch, Out* out, int32_t mode,
+                                        void* stream) {
+    if (!h || !s || s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "need a PackedShamir scheme");
+    if (mode != SDA_REVEAL_EXACT && mode != SDA_REVEAL_CANONICAL) return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
+    if (sda_status st = check_packed(s)) return st;
+    if (n_vectors > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 vectors per launch");
+    if (dimension && n_vectors && (!out || !secrets)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!key) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL key");
+    const uint64_t k = s->secret_count, t = s->privacy_threshold, B = dimension / k + (dimension % k ? 1 : 0);
+    uint64_t end, elems;                                       // n_vectors B <= 65535 * 2^64 / k may itself wrap
+    if (t && (__builtin_mul_overflow(n_vectors, B, &end) || __builtin_add_overflow(end, first_batch, &end) ||
+              __builtin_mul_overflow(end, t, &elems)))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "(first_batch + n_vectors * B) * t wraps past 2^64");
+    HIP_TRY(hipSetDevice(h->device));
+    sda::PackedGenArgs ga{secrets, dimension, n_vectors, nullptr, nullptr, mode == SDA_REVEAL_CANONICAL};
+    if constexpr (sizeof(Out) == 4) ga.out32 = out; else ga.out = out;
+    ga.key = key;
+    ga.stream_id = stream_id;
+    ga.first_batch = first_batch;
+    if (sda_status st = packed_generate(h, s, ga, pick(h, stream))) return st;
+    return ok();
+}
+
 extern "C" {
+
+sda_status sda_packed_generate_keyed_dev(sda_engine* h, const sda_sharing_scheme* s, const int64_t* secrets,
+                                         uint64_t dimension, uint64_t n_vectors, const uint32_t* key,
+                                         uint32_t stream_id, uint64_t first_batch, int64_t* out, int32_t mode,
+                                         void* stream) {
+    SDA_ENTRY;
+    return packed_generate_keyed(h, s, secrets, dimension, n_vectors, key, stream_id, first_batch, out, mode, stream);
+}
+
+sda_status sda_packed_generate_keyed32_dev(sda_engine* h, const sda_sharing_scheme* s, const int64_t* secrets,
+                                           uint64_t dimension, uint64_t n_vectors, const uint32_t* key,
+                                           uint32_t stream_id, uint64_t first_batch, int32_t* out, int32_t mode,
+                                           void* stream) {
+    SDA_ENTRY;
+    return packed_generate_keyed(h, s, secrets, dimension, n_vectors, key, stream_id, first_batch, out, mode, stream);
+}
+
+sda_status sda_packed_keyed_last_launch(sda_engine* h, uint32_t* path, uint64_t* staged_bytes) {
+    SDA_ENTRY;
+    if (!h || !path || !staged_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    *path = h->keyed_path;
+    *staged_bytes = h->keyed_staged_bytes;
+    return ok();
+}
 
 sda_status sda_additive_generate_keyed_dev(sda_engine* h, int64_t modulus, uint64_t share_count, const int64_t* secrets,
                                            uint64_t dimension, const uint32_t* key, uint32_t stream_id,

@@ -461,16 +461,20 @@ sda_status host_packed_generate(sda_engine* h, const sda_sharing_scheme* s, cons
         HIP_TRY(hipSetDevice(d->device));
         const uint64_t s0 = b0 * k, ds = std::min(D, (b0 + nb) * k) - s0;   // the last batch may be short (padded)
         DevArena a;
-        if (sda_status e = stage(d, rup(ds * 8) + rup(nb * t * 8 + 8) + rup(n * nb * 8), &a)) return e;
+        // keyed: the launch makes the draws itself (packed_generate), so no draws slice is staged in the arena
+        if (sda_status e = stage(d, rup(ds * 8) + (kd ? 0 : rup(nb * t * 8 + 8)) + rup(n * nb * 8), &a)) return e;
         int64_t* dsec = a.take<int64_t>(ds);
-        int64_t* ddr = a.take<int64_t>(nb * t + 1);
+        int64_t* ddr = kd ? nullptr : a.take<int64_t>(nb * t + 1);
         int64_t* dout = a.take<int64_t>(n * nb);
         HIP_TRY(hipMemcpyAsync(dsec, secrets + s0, ds * 8, hipMemcpyHostToDevice, d->stream));
-        if (t && kd)          // element b * t + j of the call's draws: this slice starts at batch b0
-            HIP_TRY(sda::launch_draws(kd->key, kd->stream_id, b0 * t, nb * t, s->modulus - 1, ddr, d->stream));
-        else if (t)
+        if (t && !kd)
             HIP_TRY(hipMemcpyAsync(ddr, draws + b0 * t, nb * t * 8, hipMemcpyHostToDevice, d->stream));
         sda::PackedGenArgs ga{dsec, ds, 1, ddr, dout};
+        if (kd) {             // batch b0 + b of the call takes draws (b0 + b) t + j: first_batch = b0
+            ga.key = kd->key;
+            ga.stream_id = kd->stream_id;
+            ga.first_batch = b0;
+        }
         if (sda_status e = packed_generate(d, s, ga, d->stream)) return e;
         HIP_TRY(hipMemcpy2DAsync(out + b0, B * 8, dout, nb * 8, nb * 8, n, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(hipStreamSynchronize(d->stream));

@@ -42,8 +42,12 @@ struct sda_engine {
     bool gen_log_used = false;    // the last packed launch zeroed gen_log's count and logs into it
     void* gen32_tmp = nullptr;    // sda_packed_generate32_dev at n + 1 = 81: i64 shares before the narrowing pass
     size_t gen32_tmp_bytes = 0;
-    void* keyed_draws = nullptr;  // sda_participant_share*_keyed_dev, PackedShamir: the B * t draws made on the device
+    void* keyed_draws = nullptr;  // keyed PackedShamir calls on the staged path: the n_vectors * B * t draws made on the device
     size_t keyed_draws_bytes = 0;
+    // sda_packed_keyed_last_launch: how the last keyed packed launch on this handle got its draws -- 0 none yet,
+    // 1 made in the share kernels, 2 staged through keyed_draws -- and the draw bytes that crossed HBM
+    uint32_t keyed_path = 0;
+    uint64_t keyed_staged_bytes = 0;
     void* codec_work = nullptr;   // varint codec plan / scan workspace
     size_t codec_work_bytes = 0;
     void* codec_mat = nullptr;    // decoded [N][len] matrix of the clerk decode+combine path
@@ -191,7 +195,8 @@ std::vector<uint32_t> pack_seeds(const int64_t* const* rows, const uint64_t* len
 
 // ---------------- packed-Shamir launches (engine_dev.cpp) ----------------
 // Share generation of `ga` under scheme s on stream st with h's tables and fix-up log; int32 shares (ga.out32)
-// at n + 1 = 81 get the handle-owned scratch their narrowing pass needs.
+// at n + 1 = 81 get the handle-owned scratch their narrowing pass needs, and a keyed call (ga.key) off the in-kernel
+// path the handle-owned draw scratch; a keyed call that launches records its path (sda_packed_keyed_last_launch).
 sda_status packed_generate(sda_engine* h, const sda_sharing_scheme* s, sda::PackedGenArgs ga, hipStream_t st);
 // Reveal of `ra` from n_idx clerk shares (h->gen_log is allocated); hipErrorInvalidValue: a CANONICAL reveal of
 // repeated clerk indices, which reveal_status turns into the call's failure.

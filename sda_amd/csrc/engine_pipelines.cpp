@@ -223,7 +223,8 @@ sda_status sda_recipient_reveal(sda_engine* h, const sda_masking_scheme* ms, con
 // The participant pipeline behind sda_participant_share_dev, sda_participant_share32_dev and their keyed forms.
 // One of shares64 / shares32 is the [n][B] output (shares32: int32 rows, encoded by the int32 encoder; PackedShamir,
 // and keyed Additive up to modulus 2^31).  kd (the keyed forms): `draws` is NULL and the share-generation draws
-// come from (kd->key, kd->stream_id) -- Additive in the fused kernel, PackedShamir into h->keyed_draws.
+// come from (kd->key, kd->stream_id) -- Additive in the fused kernel, PackedShamir through the keyed launch
+// (packed_generate: in the share kernels, or staged in h->keyed_draws where those do not serve the scheme).
 static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
                                     uint64_t seed_words, const int64_t* full_masks, const sda_sharing_scheme* ss,
                                     const int64_t* secrets, uint64_t dimension, const int64_t* draws, int32_t mode,
@@ -300,19 +301,15 @@ static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms,
     const uint64_t B = packed ? (D + ss->secret_count - 1) / ss->secret_count : D;
     if (B && !draws && !kd) return fail(SDA_ERR_INVALID_ARGUMENT, "need the randomness draws");
     if (payload && n > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 clerks");
-    if (kd && packed && B) {     // the B * t draws of (key, stream_id) at bound p - 1, where the caller's would be
-        const uint64_t count = B * ss->privacy_threshold;
-        if (sda_status e = ensure(&h->keyed_draws, &h->keyed_draws_bytes, rup(count * 8 + 8))) return e;
-        draws = static_cast<const int64_t*>(h->keyed_draws);
-    }
     auto share_and_encode = [&]() -> sda_status {
         if (B) {
             if (packed) {
-                if (kd)
-                    HIP_TRY(sda::launch_draws(kd->key, kd->stream_id, 0, B * ss->privacy_threshold, ss->modulus - 1,
-                                              static_cast<int64_t*>(h->keyed_draws), st));
                 sda::PackedGenArgs ga{masked, D, 1, draws, shares64, mode == SDA_REVEAL_CANONICAL};
                 ga.out32 = shares32;             // as sda_packed_generate32_dev: scratch + narrowing at n + 1 = 81
+                if (kd) {                        // batch b takes draws b t + j of (key, stream_id) at bound p - 1
+                    ga.key = kd->key;
+                    ga.stream_id = kd->stream_id;
+                }
                 if (sda_status e = packed_generate(h, ss, ga, st)) return e;
             } else if (kd) {
                 HIP_TRY(sda::launch_additive_generate_keyed(kd->key, kd->stream_id, 0, masked, D, n, ss->modulus,

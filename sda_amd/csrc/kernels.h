@@ -118,9 +118,23 @@ struct PackedGenArgs {
     int64_t* flag = nullptr;
     const void* align_as = nullptr;   // set by launch_packed_generate: the buffer whose alignment picks the kernel
     int store32 = 0;              // set by launch_packed_generate: 2 = the 16-byte quad store (A/B, SDA_GEN32_QUAD builds)
+    // keyed (sda_packed_generate_keyed_dev): key != nullptr replaces `draws`.  Batch b of vector v takes draws
+    // (first_batch + v B + b) t + j, j < t, of launch_draws' rule under (key, stream_id) at bound p - 1 (key: HOST,
+    // 8 words; the caller has checked that (first_batch + n_vectors B) t does not wrap).  Schemes on the register
+    // path with n + 1 <= 27 make them in the share kernels; the others get launch_draws into draw_scratch
+    // (packed_gen_keyed_scratch_bytes() bytes) ahead of the unkeyed kernels.  keyed_fuse = false stages every scheme.
+    const uint32_t* key = nullptr;
+    uint32_t stream_id = 0;
+    uint64_t first_batch = 0;
+    int64_t* draw_scratch = nullptr;
+    bool keyed_fuse = true;
 };
 // Scratch the int32 call needs (0: native int32 kernels serve it).
 size_t packed_gen32_scratch_bytes(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p);
+// Whether a keyed call's draws are made in the share kernels (else staged through draw_scratch).
+bool packed_gen_keyed_in_kernel(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p);
+// Draw scratch a keyed call needs: 0 when the share kernels make the draws (or t == 0), else n_vectors B t 8 bytes.
+size_t packed_gen_keyed_scratch_bytes(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p);
 // A/B knob: SDA_XCD_ORDER=0 runs the streaming kernels in natural workgroup order (xcd.h).
 bool xcd_order_enabled();
 // Exact share-gen uses lazy truncation (packed_gen.hip: Trunc<true>) for primes at least this big.

@@ -2,10 +2,38 @@
 #include <stdlib.h>
 
 #include "packed_common.h"
+#include "draws_common.h"
 #include "xcd.h"
 
 namespace sda {
 using namespace packed;
+
+namespace {
+
+// The keyed kernels' draws (sda_packed_generate_keyed_dev): batch b of vector v takes elements
+// (first_batch + v B + b) t + j, j < t, of the draw rule (draws.hip) under (key, stream_id) at bound p - 1.
+// A kernel argument, as in additive_keyed.hip: the key is never stored in device memory.
+struct GenKeyed {
+    DrawKey key;
+    uint32_t stream_id;
+    uint64_t first_batch;
+    Mod64 M;               // bound p - 1
+    uint64_t zone;
+};
+
+inline GenKeyed make_gen_keyed(const PackedGenArgs& a) {
+    GenKeyed kg{};
+    if (!a.key) return kg;
+    for (int q = 0; q < 8; ++q) kg.key.k[q] = a.key[q];
+    const int64_t bound = (int64_t)a.prime - 1;
+    kg.stream_id = a.stream_id;
+    kg.first_batch = a.first_batch;
+    kg.M = make_mod64(bound);
+    kg.zone = UINT64_MAX - UINT64_MAX % (uint64_t)bound;
+    return kg;
+}
+
+}  // namespace
 
 // One launcher per (L = k+t+1, N3 = n+1); each is compiled in its own object (Makefile:
 // -DSDA_GEN_PART=N3 -DSDA_GEN_L=L) so the instantiations build in parallel.
@@ -261,11 +289,20 @@ __device__ __forceinline__ void transform_canon(const int64_t (&raw)[L], const G
 //      the tail is not store-issue-bound, and the trade costs 12 DPP moves and 24 selects per lane; DESIGN.md
 //      §4.2, profiles/packed32), so it is compiled only with -DSDA_GEN32_QUAD=1 (A/B knob; SDA_GEN32_STORE=16
 //      then selects it at run time).
-template <class OT, int L, int N3, int STORE, bool CANON, bool LAZY, bool SIGNBIT>
+//
+// KEYED (packed_gen_keyed_kernel, n + 1 <= 27): `draws` is not read.  The tile's draws are the contiguous element
+// range [E0, E0 + nb t) of the draw stream, E0 = (first_batch + vec B + b0) t, nb the tile's live batches, and they
+// lie in the LDS image exactly as in that stream: after issuing its share of the secrets' loads each lane makes
+// ChaCha blocks (E0 >> 3) + tid, + BS, ... (draw_eight, 8 draws each) and stores the elements that fall into the
+// range at lds[BS k + (e - E0)]; those outside (the first and last block's, when the range starts or ends inside
+// a block) are computed and dropped.  The secrets' LDS DMA stays in flight during that VALU work; its wait and
+// the barrier follow.  The draws never exist in HBM.
+template <class OT, int L, int N3, int STORE, bool CANON, bool LAZY, bool SIGNBIT, bool KEYED = false>
 __device__ __forceinline__ void packed_gen_body(const int64_t* __restrict__ secrets, uint64_t D,
                                                 const int64_t* __restrict__ draws, OT* __restrict__ out, uint32_t k,
                                                 uint32_t t, uint64_t B, const GenTables* __restrict__ Tp,
-                                                unsigned int* __restrict__ log, int xcd) {
+                                                unsigned int* __restrict__ log, int xcd,
+                                                [[maybe_unused]] const GenKeyed& kg = GenKeyed{}) {
     static_assert(STORE <= 1 || sizeof(OT) == 4, "the quad store is an int32 form");
     constexpr int LB = ilog(L, 2);
     constexpr int ND = ilog(N3, 3);
@@ -314,12 +351,12 @@ __device__ __forceinline__ void packed_gen_body(const int64_t* __restrict__ secr
             // 2 (k + t) chunks with a computed source and a wave-uniform chunk index: every DMA of the tile is
             // issued before any wait (round 5's two loops put an s_waitcnt vmcnt(0) between them).
             const int64_t* sblk = sec + b0 * k;
-            const int64_t* dblk = draws + ((uint64_t)vec * B + b0) * t;
+            const int64_t* dblk = KEYED ? sblk : draws + ((uint64_t)vec * B + b0) * t;     // KEYED: the secrets alone
             if (full && (((uintptr_t)sblk | (uintptr_t)dblk) & 15) == 0) {
                 typedef __attribute__((address_space(3))) char lds_char;
                 lds_char* lbase = (lds_char*)lds;
                 const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63;
-                const uint32_t nsc = 2 * k, nc = 2 * (k + t);    // 1 KiB chunks: BS k * 8 / 1024 = 2 k
+                const uint32_t nsc = 2 * k, nc = KEYED ? nsc : 2 * (k + t);    // 1 KiB chunks: BS k * 8 / 1024 = 2 k
                 for (uint32_t c = w; c < nc; c += BS / 64) {
                     const int64_t* src = c < nsc ? sblk + (uint64_t)c * 128 : dblk + (uint64_t)(c - nsc) * 128;
                     __builtin_amdgcn_global_load_lds((const void*)(src + 2 * l), lbase + c * 1024, 16, 0,
@@ -327,7 +364,8 @@ __device__ __forceinline__ void packed_gen_body(const int64_t* __restrict__ secr
                 }
                 // the LDS writes of a DMA count in vmcnt, and s_barrier does not wait for them: every wave drains
                 // its own DMAs before the barrier, so the other waves' reads see every chunk
-                __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0) (gfx9 encoding; lgkm/exp counters untouched)
+                // (KEYED: after the draw loop below)
+                if constexpr (!KEYED) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) (gfx9 encoding; lgkm/exp counters untouched)
                 staged = true;
             }
         }
@@ -337,12 +375,17 @@ __device__ __forceinline__ void packed_gen_body(const int64_t* __restrict__ secr
             // [b0 k + u BS, +BS), row u >= k draws [(vec B + b0) t + (u - k) BS, +BS) -- each row one
             // coalesced load from a uniform base, landing at lds[u BS + tid] (the layout below)
             const int64_t* ssrc = sec + b0 * k + tid;
-            const int64_t* dsrc = draws + ((uint64_t)vec * B + b0) * t + tid;
             int64_t v[L - 1];
+            if constexpr (KEYED) {                 // the secrets' rows alone
+                static_for<0, L - 1>([&](auto u) { if ((uint32_t)u < k) v[u] = gen_load(ssrc + (uint64_t)u * BS); });
+                static_for<0, L - 1>([&](auto u) { if ((uint32_t)u < k) lds[lpos((uint32_t)u * BS + tid)] = v[u]; });
+            } else {
+            const int64_t* dsrc = draws + ((uint64_t)vec * B + b0) * t + tid;
             static_for<0, L - 1>([&](auto u) {
                 v[u] = gen_load((uint32_t)u < k ? ssrc + (uint64_t)u * BS : dsrc + (uint64_t)(u - k) * BS);
             });
             static_for<0, L - 1>([&](auto u) { lds[lpos((uint32_t)u * BS + tid)] = v[u]; });
+            }
         } else {
             constexpr int U = 8;
             const uint64_t nb = B - b0 < (uint64_t)BS ? B - b0 : (uint64_t)BS;
@@ -361,6 +404,7 @@ __device__ __forceinline__ void packed_gen_body(const int64_t* __restrict__ secr
                     if (e < ns) lds[lpos(e)] = e < valid ? v[u] : 0;
                 });
             }
+            if constexpr (!KEYED) {
             const uint32_t nd = (uint32_t)nb * t;
             const int64_t* dsrc = draws + ((uint64_t)vec * B + b0) * t;
             const uint32_t dbase = (uint32_t)BS * k;
@@ -375,6 +419,29 @@ __device__ __forceinline__ void packed_gen_body(const int64_t* __restrict__ secr
                     if (e < nd) lds[lpos(dbase + e)] = v[u];
                 });
             }
+            }
+        }
+        if constexpr (KEYED) {
+            // ---- the tile's draws, made in place (see the head comment) ----
+            if constexpr (!CANON) set_prio<0>();             // VALU work: the loads above are issued
+            const uint32_t nb = B - b0 < (uint64_t)BS ? (uint32_t)(B - b0) : (uint32_t)BS;
+            const uint32_t nd = nb * t;                      // 0 with t = 0: no iteration
+            if (nd) {
+                // the host checked that (first_batch + n_vectors B) t does not wrap
+                const uint64_t E0 = (kg.first_batch + (uint64_t)vec * B + b0) * t;
+                const uint64_t blk0 = E0 >> 3, blk1 = (E0 + (nd - 1)) >> 3;
+                const uint32_t lead = (uint32_t)E0 & 7;      // elements of block blk0 before the range
+                const uint32_t dbase = (uint32_t)BS * k;
+                for (uint64_t blk = blk0 + tid; blk <= blk1; blk += BS) {
+                    uint64_t res[8];
+                    draw_eight(kg.key, blk, kg.stream_id, kg.M, kg.zone, res);
+                    const uint32_t e = (uint32_t)(blk - blk0) * 8 - lead;      // offset of the block's element 0
+#pragma unroll
+                    for (uint32_t q = 0; q < 8; ++q)
+                        if (e + q < nd) lds[lpos(dbase + e + q)] = (int64_t)res[q];   // (wraps below the range)
+                }
+            }
+            if (staged) __builtin_amdgcn_s_waitcnt(0x0F70);  // the secrets' DMAs (vmcnt(0), as above)
         }
         __syncthreads();
         if constexpr (!CANON) set_prio<0>();
@@ -629,6 +696,17 @@ void packed_gen_kernel(const int64_t* __restrict__ secrets, uint64_t D, const in
     packed_gen_body<int64_t, L, N3, WIDE ? 1 : 0, CANON, LAZY, SIGNBIT>(secrets, D, draws, out, k, t, B, Tp, log, xcd);
 }
 
+// The same kernel with the draws made in the tile (KEYED above), in the objects with n + 1 <= 27.
+template <int L, int N3, bool WIDE, bool CANON, bool LAZY, bool SIGNBIT = false>
+__global__ __launch_bounds__(gen_block<L>())
+__attribute__((amdgpu_waves_per_eu(gen_waves<L, N3, CANON, LAZY>(), gen_waves<L, N3, CANON, LAZY>())))
+void packed_gen_keyed_kernel(const int64_t* __restrict__ secrets, uint64_t D, GenKeyed kg, int64_t* __restrict__ out,
+                             uint32_t k, uint32_t t, uint64_t B, const GenTables* __restrict__ Tp,
+                             unsigned int* __restrict__ log, int xcd) {
+    packed_gen_body<int64_t, L, N3, WIDE ? 1 : 0, CANON, LAZY, SIGNBIT, true>(secrets, D, nullptr, out, k, t, B, Tp,
+                                                                              log, xcd, kg);
+}
+
 // int32 shares (STORE as above), for n + 1 <= 27; the n + 1 = 81 objects dominate the build, and int32 output
 // there goes through the i64 kernels and launch_narrow32 (launch_packed_generate).
 template <int L, int N3, int STORE, bool CANON, bool LAZY, bool SIGNBIT = false>
@@ -638,6 +716,16 @@ void packed_gen32_kernel(const int64_t* __restrict__ secrets, uint64_t D, const 
                          int32_t* __restrict__ out, uint32_t k, uint32_t t, uint64_t B,
                          const GenTables* __restrict__ Tp, unsigned int* __restrict__ log, int xcd) {
     packed_gen_body<int32_t, L, N3, STORE, CANON, LAZY, SIGNBIT>(secrets, D, draws, out, k, t, B, Tp, log, xcd);
+}
+
+template <int L, int N3, int STORE, bool CANON, bool LAZY, bool SIGNBIT = false>
+__global__ __launch_bounds__(gen_block<L>())
+__attribute__((amdgpu_waves_per_eu(gen_waves<L, N3, CANON, LAZY>(), gen_waves<L, N3, CANON, LAZY>())))
+void packed_gen32_keyed_kernel(const int64_t* __restrict__ secrets, uint64_t D, GenKeyed kg,
+                               int32_t* __restrict__ out, uint32_t k, uint32_t t, uint64_t B,
+                               const GenTables* __restrict__ Tp, unsigned int* __restrict__ log, int xcd) {
+    packed_gen_body<int32_t, L, N3, STORE, CANON, LAZY, SIGNBIT, true>(secrets, D, nullptr, out, k, t, B, Tp, log,
+                                                                        xcd, kg);
 }
 
 }  // namespace
@@ -652,20 +740,32 @@ static hipError_t gen_launch_mode(const PackedGenArgs& a, uint32_t k, uint32_t t
     const bool wide = B % 2 == 0 && ((uintptr_t)a.out % 16) == 0 && ((uintptr_t)a.align_as % 16) == 0;
     const int xcd = a.xcd_order && (uint64_t)grid.x * grid.y < (1ull << 32) ? 1 : 0;
     constexpr bool NONLAZY = CANON || gen_register_path(L, N3, true);
+    // a.key (n + 1 <= 27: launch_packed_generate stages the draws of the other schemes): the keyed twin
+    [[maybe_unused]] const GenKeyed kg = make_gen_keyed(a);
+#define SDA_GEN64(WD, CN, LZ, SB)                                                                                 \
+    do {                                                                                                          \
+        if constexpr (N3 <= 27) {                                                                                 \
+            if (a.key) {                                                                                          \
+                hipLaunchKernelGGL((packed_gen_keyed_kernel<L, N3, WD, CN, LZ, SB>), grid, dim3(BS), 0, s,        \
+                                   a.secrets, a.dimension, kg, a.out, k, t, B, T, log.count, xcd);                \
+                break;                                                                                            \
+            }                                                                                                     \
+        }                                                                                                         \
+        hipLaunchKernelGGL((packed_gen_kernel<L, N3, WD, CN, LZ, SB>), grid, dim3(BS), 0, s, a.secrets,           \
+                           a.dimension, a.draws, a.out, k, t, B, T, log.count, xcd);                              \
+    } while (0)
+    if (a.key && N3 > 27) return hipErrorInvalidValue;
     if (wide && !CANON && p >= kLazyTruncMinP && a.signbit)   // exact shares, sign-bit radix-2 half
-        hipLaunchKernelGGL((packed_gen_kernel<L, N3, true, false, true, true>), grid, dim3(BS), 0, s, a.secrets,
-                           a.dimension, a.draws, a.out, k, t, B, T, log.count, xcd);
+        SDA_GEN64(true, false, true, true);
     else if (wide && !CANON && p >= kLazyTruncMinP)          // exact shares, lazy zero handling
-        hipLaunchKernelGGL((packed_gen_kernel<L, N3, true, false, true>), grid, dim3(BS), 0, s, a.secrets,
-                           a.dimension, a.draws, a.out, k, t, B, T, log.count, xcd);
+        SDA_GEN64(true, false, true, false);
     else if constexpr (!NONLAZY)
         return hipErrorInvalidValue;                          // the dispatcher sends these to packed_wide.hip
     else if (wide)
-        hipLaunchKernelGGL((packed_gen_kernel<L, N3, true, CANON, false>), grid, dim3(BS), 0, s, a.secrets,
-                           a.dimension, a.draws, a.out, k, t, B, T, log.count, xcd);
+        SDA_GEN64(true, CANON, false, false);
     else
-        hipLaunchKernelGGL((packed_gen_kernel<L, N3, false, CANON, false>), grid, dim3(BS), 0, s, a.secrets,
-                           a.dimension, a.draws, a.out, k, t, B, T, log.count, xcd);
+        SDA_GEN64(false, CANON, false, false);
+#undef SDA_GEN64
     return hipSuccess;
 }
 
@@ -683,9 +783,16 @@ static hipError_t gen_launch_mode32(const PackedGenArgs& a, uint32_t k, uint32_t
         constexpr bool QUAD = SDA_GEN32_QUAD;
         const bool quad = QUAD && wide && B % 4 == 0 && a.store32 == 2;
         const int xcd = a.xcd_order && (uint64_t)grid.x * grid.y < (1ull << 32) ? 1 : 0;
+        const GenKeyed kg = make_gen_keyed(a);                // a.key: the keyed twin
 #define SDA_GEN32(STORE, CN, LZ, SB)                                                                               \
-    hipLaunchKernelGGL((packed_gen32_kernel<L, N3, STORE, CN, LZ, SB>), grid, dim3(BS), 0, s, a.secrets, a.dimension, \
-                       a.draws, a.out32, k, t, B, T, log.count, xcd)
+    do {                                                                                                           \
+        if (a.key)                                                                                                 \
+            hipLaunchKernelGGL((packed_gen32_keyed_kernel<L, N3, STORE, CN, LZ, SB>), grid, dim3(BS), 0, s,        \
+                               a.secrets, a.dimension, kg, a.out32, k, t, B, T, log.count, xcd);                   \
+        else                                                                                                       \
+            hipLaunchKernelGGL((packed_gen32_kernel<L, N3, STORE, CN, LZ, SB>), grid, dim3(BS), 0, s, a.secrets,   \
+                               a.dimension, a.draws, a.out32, k, t, B, T, log.count, xcd);                         \
+    } while (0)
 #define SDA_GEN32_WIDE(CN, LZ, SB)                                 \
     do {                                                           \
         if constexpr (QUAD) {                                      \
@@ -736,11 +843,14 @@ namespace {
 // radix-2 level and outputs j, j + 64 of a radix-3 level, the state in LDS (radix-3 levels double
 // buffered, as their outputs overwrite other lanes' inputs).  If the log overflowed, every batch of the
 // launch is recomputed (correct, slow, and only reachable with raw i64 secrets far outside the field).
-template <class OT>
+// KEYED (after a keyed kernel): `draws` is not read; lane i in (k, k + t] takes element
+// (first_batch + gb) t + i - 1 - k of the draw rule from its block's draw_eight, as the keyed tile did.
+template <class OT, bool KEYED = false>
 __device__ __forceinline__ void gen_fixup_body(const int64_t* __restrict__ secrets, uint64_t D,
                                                const int64_t* __restrict__ draws, OT* __restrict__ out, uint32_t k,
                                                uint32_t t, uint64_t B, uint64_t n_vec, int L, int N3,
-                                               const GenTables* __restrict__ T, GenFixupLog log, int canonical) {
+                                               const GenTables* __restrict__ T, GenFixupLog log, int canonical,
+                                               [[maybe_unused]] const GenKeyed& kg = GenKeyed{}) {
     const uint32_t n = *log.count;
     if (n == 0) return;
     const bool all = n > log.cap;
@@ -761,7 +871,16 @@ __device__ __forceinline__ void gen_fixup_body(const int64_t* __restrict__ secre
                 const uint64_t idx = b * k + (lane - 1);
                 val = idx < D ? secrets[vec * D + idx] : 0;
             } else if (lane > 0) {
-                val = draws[gb * t + (lane - 1 - k)];
+                if constexpr (KEYED) {
+                    const uint64_t e = (kg.first_batch + gb) * t + (uint32_t)(lane - 1 - k);
+                    uint64_t res[8];
+                    draw_eight(kg.key, e >> 3, kg.stream_id, kg.M, kg.zone, res);
+                    uint64_t r = res[0];
+                    static_for<1, 8>([&](auto q) { r = (e & 7) == (uint32_t)q ? res[q] : r; });
+                    val = (int64_t)r;
+                } else {
+                    val = draws[gb * t + (lane - 1 - k)];
+                }
             }
             xa[rev_digits(lane, 2, lb)] = val;
         }
@@ -826,6 +945,24 @@ __global__ __launch_bounds__(64) void packed_gen32_fixup_kernel(const int64_t* _
     gen_fixup_body(secrets, D, draws, out, k, t, B, n_vec, L, N3, T, log, canonical);
 }
 
+// the two fix-up kernels after a keyed launch
+__global__ __launch_bounds__(64) void packed_gen_keyed_fixup_kernel(const int64_t* __restrict__ secrets, uint64_t D,
+                                                                    GenKeyed kg, int64_t* __restrict__ out,
+                                                                    uint32_t k, uint32_t t, uint64_t B, uint64_t n_vec,
+                                                                    int L, int N3, const GenTables* __restrict__ T,
+                                                                    GenFixupLog log, int canonical) {
+    gen_fixup_body<int64_t, true>(secrets, D, nullptr, out, k, t, B, n_vec, L, N3, T, log, canonical, kg);
+}
+
+__global__ __launch_bounds__(64) void packed_gen32_keyed_fixup_kernel(const int64_t* __restrict__ secrets, uint64_t D,
+                                                                      GenKeyed kg, int32_t* __restrict__ out,
+                                                                      uint32_t k, uint32_t t, uint64_t B,
+                                                                      uint64_t n_vec, int L, int N3,
+                                                                      const GenTables* __restrict__ T, GenFixupLog log,
+                                                                      int canonical) {
+    gen_fixup_body<int32_t, true>(secrets, D, nullptr, out, k, t, B, n_vec, L, N3, T, log, canonical, kg);
+}
+
 }  // namespace
 
 bool xcd_order_enabled() {
@@ -847,6 +984,17 @@ static bool gen_takes_register_path(const PackedGenArgs& a, uint32_t k, uint32_t
     return gen_register_path(k + t + 1, n + 1, exact_nonlazy);
 }
 
+// a keyed call whose draws are made in the share kernels: the register path up to n + 1 = 27
+bool packed_gen_keyed_in_kernel(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p) {
+    return a.key && a.keyed_fuse && n + 1 <= 27 && gen_takes_register_path(a, k, t, n, p);
+}
+
+size_t packed_gen_keyed_scratch_bytes(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p) {
+    if (!a.key || packed_gen_keyed_in_kernel(a, k, t, n, p)) return 0;
+    const uint64_t B = (a.dimension + k - 1) / k;
+    return (size_t)(a.n_vectors * B * t) * sizeof(int64_t);
+}
+
 size_t packed_gen32_scratch_bytes(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p) {
     if (n + 1 <= 27 || !gen_takes_register_path(a, k, t, n, p)) return 0;
     const uint64_t B = (a.dimension + k - 1) / k;
@@ -861,6 +1009,19 @@ hipError_t launch_packed_generate(const PackedGenArgs& args, uint32_t k, uint32_
     a.prime = p;
     const uint32_t L = k + t + 1, N3 = n + 1;
     const uint64_t B = (a.dimension + k - 1) / k;
+    if (a.key && !packed_gen_keyed_in_kernel(a, k, t, n, p)) {
+        // keyed, staged: the call's draws into the caller's scratch (packed_gen_keyed_scratch_bytes), then the
+        // unkeyed path below reads them back
+        const uint64_t count = a.n_vectors * B * t;
+        if (count) {
+            if (!a.draw_scratch) return hipErrorInvalidValue;
+            const hipError_t e = launch_draws(a.key, a.stream_id, a.first_batch * t, count, (int64_t)p - 1,
+                                              a.draw_scratch, s);
+            if (e != hipSuccess) return e;
+        }
+        a.draws = a.draw_scratch;
+        a.key = nullptr;
+    }
     if (!gen_takes_register_path(a, k, t, n, p))             // past the register kernels: packed_wide.hip
         return launch_packed_generate_wide(a, k, t, n, p, omega_secrets, omega_shares, tab, s);
     if (B == 0 || a.n_vectors == 0) return hipSuccess;
@@ -912,7 +1073,15 @@ hipError_t launch_packed_generate(const PackedGenArgs& args, uint32_t k, uint32_
         default: e = hipErrorInvalidValue;
     }
     if (e != hipSuccess) return e;
-    if (a.out32)
+    if (a.key && a.out32)
+        hipLaunchKernelGGL(packed_gen32_keyed_fixup_kernel, dim3(512), dim3(64), 0, s, a.secrets, a.dimension,
+                           make_gen_keyed(a), a.out32, k, t, B, a.n_vectors, (int)L, (int)N3, T, log,
+                           a.canonical ? 1 : 0);
+    else if (a.key)
+        hipLaunchKernelGGL(packed_gen_keyed_fixup_kernel, dim3(512), dim3(64), 0, s, a.secrets, a.dimension,
+                           make_gen_keyed(a), a.out, k, t, B, a.n_vectors, (int)L, (int)N3, T, log,
+                           a.canonical ? 1 : 0);
+    else if (a.out32)
         hipLaunchKernelGGL(packed_gen32_fixup_kernel, dim3(512), dim3(64), 0, s, a.secrets, a.dimension, a.draws,
                            a.out32, k, t, B, a.n_vectors, (int)L, (int)N3, T, log, a.canonical ? 1 : 0);
     else

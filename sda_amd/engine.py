@@ -187,6 +187,11 @@ SIGNATURES = [
                                               C.c_uint64, _vp, C.c_uint64, _vp]),
     ("sda_additive_generate_keyed32_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, _u32p, C.c_uint32,
                                                 C.c_uint64, _vp, C.c_uint64, _vp]),
+    ("sda_packed_generate_keyed_dev", _st, [_vp, C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, C.c_uint64, _u32p,
+                                            C.c_uint32, C.c_uint64, _vp, C.c_int32, _vp]),
+    ("sda_packed_generate_keyed32_dev", _st, [_vp, C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, C.c_uint64, _u32p,
+                                              C.c_uint32, C.c_uint64, _vp, C.c_int32, _vp]),
+    ("sda_packed_keyed_last_launch", _st, [_vp, _u32p, _u64p]),
     ("sda_participant_share_keyed_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _u32p, C.c_uint64, _vp,
                                               C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, _u32p, C.c_uint32,
                                               C.c_int32, _vp, _vp, C.c_uint64, _u64p, _vp]),
@@ -579,6 +584,14 @@ class Engine:
         _check(self.lib.sda_snapshot_last_launch(self.h, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
+    def packed_keyed_last_launch(self):
+        """(path, staged_bytes) of the handle's last keyed packed-Shamir launch: path 0 none yet, 1 the draws were
+        made in the share kernels, 2 staged in device scratch; staged_bytes the draw bytes that crossed HBM
+        (sda_packed_keyed_last_launch)."""
+        path, staged = C.c_uint32(), C.c_uint64()
+        _check(self.lib.sda_packed_keyed_last_launch(self.h, C.byref(path), C.byref(staged)))
+        return int(path.value), int(staged.value)
+
     def combine_finalize_dev(self, modulus, sums_ptr, dim, out_ptr, stream=None):
         _check(self.lib.sda_combine_finalize_dev(self.h, modulus, sums_ptr, dim, out_ptr, stream))
 
@@ -631,6 +644,26 @@ class Engine:
         idx = _arr(indices, np.uint64)
         _check(self.lib.sda_packed_reconstruct32_dev(self.h, C.byref(s), dimension, _ptr(idx, _u64p), idx.size,
                                                      n_vectors, shares_ptr, out_ptr, mode, stream))
+
+    def packed_generate_keyed_dev(self, scheme, secrets_ptr, dimension, n_vectors, key, stream_id, out_ptr, mode,
+                                  first_batch=0, stream=None):
+        """packed_generate_mode_dev with the draws made on the device (sda_packed_generate_keyed_dev): batch b of
+        vector v takes draws (first_batch + v B + b) t + j of (key, stream_id) at bound p - 1.  key=None passes a
+        NULL key (the status tests)."""
+        s = scheme.c()
+        k = self._key(key) if key is not None else None
+        _check(self.lib.sda_packed_generate_keyed_dev(self.h, C.byref(s), secrets_ptr, dimension, n_vectors,
+                                                      _ptr(k, _u32p) if k is not None else None, stream_id,
+                                                      first_batch, out_ptr, mode, stream))
+
+    def packed_generate_keyed32_dev(self, scheme, secrets_ptr, dimension, n_vectors, key, stream_id, out_ptr, mode,
+                                    first_batch=0, stream=None):
+        """packed_generate_keyed_dev with out as device int32 [n_vectors][n][B]."""
+        s = scheme.c()
+        k = self._key(key) if key is not None else None
+        _check(self.lib.sda_packed_generate_keyed32_dev(self.h, C.byref(s), secrets_ptr, dimension, n_vectors,
+                                                        _ptr(k, _u32p) if k is not None else None, stream_id,
+                                                        first_batch, out_ptr, mode, stream))
 
     def additive_generate_dev(self, modulus, share_count, secrets_ptr, dimension, draws_ptr, out_ptr, stream=None):
         _check(self.lib.sda_additive_generate_dev(self.h, modulus, share_count, secrets_ptr, dimension, draws_ptr,
