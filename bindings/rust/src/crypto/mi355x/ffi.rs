@@ -128,6 +128,10 @@ extern "C" {
                                    nwide: *mut u32, per_cu: *mut u32) -> SdaStatus;
     pub fn sda_snapshot_last_launch(h: *mut SdaEngine, blobs: *mut u64, chunks: *mut u64, grid: *mut u64,
                                     chunk_bytes: *mut u64, shifts: *mut u32) -> SdaStatus;
+    pub fn sda_recipient_last_launch(h: *mut SdaEngine, mask_kind: *mut u32, reveal_mode: *mut u32,
+                                     fell_back: *mut u32, compact: *mut u32, unmask_launches: *mut u32) -> SdaStatus;
+    pub fn sda_participant_last_launch(h: *mut SdaEngine, mask_route: *mut u32, share_route: *mut u32,
+                                       passes: *mut u32) -> SdaStatus;
     pub fn sda_combine_finalize_dev(h: *mut SdaEngine, modulus: i64, sums: *const i64, dim: u64, out: *mut i64,
                                     stream: *mut c_void) -> SdaStatus;
     pub fn sda_combine_split_dev(h: *mut SdaEngine, modulus: i64, shares: *const i64, n: u64, dim: u64,

@@ -185,7 +185,8 @@ sda_status sda_secret_mask_keyed(sda_engine* h, const sda_masking_scheme* s, con
                                  int64_t* masked_out);
 
 /* MaskCombiner::combine  (masking/mod.rs:21-23)
- *   Full: rows are masks (full.rs:38-50); ChaCha: rows are seeds-as-i64 (chacha.rs:57-76);
+ *   Full: rows are masks (full.rs:38-50); ChaCha: rows are seeds-as-i64 (chacha.rs:57-76) -- no row gives
+ *   `dimension` zeros for any modulus (nothing is drawn), a modulus <= 0 with a row is SDA_ERR_PRECONDITION;
  *   None: every row must be empty, out_len = 0 (none.rs:22-25). */
 sda_status sda_mask_combine(sda_engine* h, const sda_masking_scheme* s,
                             const int64_t* const* rows, const uint64_t* lens, uint64_t n_rows,
@@ -335,6 +336,44 @@ sda_status sda_combine_last_launch(sda_engine* h, uint32_t* kind, uint32_t* elem
 sda_status sda_snapshot_last_launch(sda_engine* h, uint64_t* blobs, uint64_t* chunks, uint64_t* grid,
                                     uint64_t* chunk_bytes, uint32_t* shifts);
 
+/* Diagnostic (read-only): the decisions the handle's most recent sda_recipient_reveal / sda_recipient_reveal_dev
+ * took.  A call writes the record when it returns SDA_OK with an output of at least one element; a failed call and
+ * a call whose output is empty leave it as it was.  Before any such call every field is 0.
+ *   mask_kind        1  no masking
+ *                    2  Full: the mask rows were combined by the pipeline
+ *                    3  ChaCha: the seeds were expanded and combined by the pipeline
+ *                    4  ChaCha on a multi-device handle: the mask combine was split over the devices and the
+ *                       pipeline ran with the combined row
+ *   reveal_mode      0  Additive: the clerk rows were combined
+ *                    1  PackedShamir, the exact reveal (tss' signed representatives)
+ *                    2  PackedShamir, the canonical reveal -- asked for, or substituted for an EXACT request
+ *                       whose output cannot depend on the representative (masking and output modulus both the
+ *                       sharing prime; SDA_RECIPIENT_EXACT=1 keeps EXACT)
+ *   fell_back        1 when that substituted canonical reveal was refused (repeated clerk indices) and the
+ *                    exact reveal ran instead
+ *   compact          1 when the clerk vectors were longer than the batch count and their first B values were
+ *                    copied into a dense matrix first
+ *   unmask_launches  1, or 2 when the ChaCha mask had rejected draws: it was fixed and the unmask redone
+ * A host-side record: nothing is waited for or copied.  No pointer may be NULL. */
+sda_status sda_recipient_last_launch(sda_engine* h, uint32_t* mask_kind, uint32_t* reveal_mode, uint32_t* fell_back,
+                                     uint32_t* compact, uint32_t* unmask_launches);
+
+/* Diagnostic (read-only): the routes the handle's most recent sda_participant_share_dev, _share32_dev or keyed form
+ * took.  A call of dimension > 0 writes the record when it returns SDA_OK; a failed call and a call of dimension 0
+ * leave it as it was.  Before any such call every field is 0.
+ *   mask_route   1  no masking
+ *                2  Full: one add of the caller's masks
+ *                3  ChaCha, the fused single-stream mask add (sda_chacha_last_launch path 4)
+ *                4  ChaCha, the mask expanded by the combine's dispatch (a modulus off the fast path, or
+ *                   SDA_CHACHA_PATH=stream), then one add
+ *   share_route  1  Additive from the caller's draws
+ *                2  Additive, draws made in the kernel (keyed)
+ *                3  PackedShamir from the caller's draws
+ *                4  PackedShamir keyed (sda_packed_keyed_last_launch tells in-kernel from staged draws)
+ *   passes       1, or 2 when route 3's mask had a rejected draw: the mask and every later step were redone
+ * A host-side record: nothing is waited for or copied.  No pointer may be NULL. */
+sda_status sda_participant_last_launch(sda_engine* h, uint32_t* mask_route, uint32_t* share_route, uint32_t* passes);
+
 /* Multi-GPU finalize: `sums` are the int64 sums (RCCL-reduced; |sum| <= 2^63 - 1, signed allowed)
  * of per-GPU combine results; out = their canonical residue in [0, m).  Exact w.r.t. the reference
  * when all combined inputs were non-negative. */
@@ -422,7 +461,8 @@ sda_status sda_additive_generate_dev(sda_engine* h, int64_t modulus, uint64_t sh
  * (seeds [n_seeds][w] u32, device), out [dimension].  Exact including gen_range rejections
  * (fix-up pass; moduli with a high rejection rate expand each stream exactly instead) and the
  * reference's wrapping i64 sum for moduli above 2^62 (the result is then signed and
- * order-dependent, as in the reference).  Waits for its rejection log before returning. */
+ * order-dependent, as in the reference).  Waits for its rejection log before returning.  n_seeds == 0 gives
+ * `dimension` zeros for any modulus; a modulus <= 0 with a seed is SDA_ERR_PRECONDITION. */
 sda_status sda_chacha_mask_combine_dev(sda_engine* h, int64_t modulus, uint64_t dimension,
                                        const uint32_t* seeds, uint64_t w, uint64_t n_seeds,
                                        int64_t* out, void* stream);

@@ -200,8 +200,12 @@ def chacha_mask(m: int, seed_words, secrets) -> np.ndarray:
 
 
 def chacha_mask_combine(m: int, dimension: int, seeds_as_i64) -> np.ndarray:
+    """chacha.rs:57-76.  No seed row: `dimension` zeros for any modulus (nothing is drawn or reduced); a modulus
+    <= 0 with a seed row is the reference's gen_range panic."""
     s, sp = _i64(seeds_as_i64)
     N, w = s.shape if s.ndim == 2 else (0, 0)
+    if N and dimension and m <= 0:
+        raise ValueError("Rng.gen_range called with low >= high")
     out, op = _i64(np.zeros(max(dimension, 1), np.int64))
     lib().or_chacha_mask_combine(m, dimension, sp, w, N, op)
     return out[:dimension]

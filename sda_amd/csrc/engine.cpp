@@ -629,11 +629,17 @@ sda_status sda_mask_combine(sda_engine* h, const sda_masking_scheme* s, const in
     HIP_TRY(hipSetDevice(h->device));
     const uint64_t D = s->dimension;                        // chacha.rs:58 vec![0; self.dimension]
     if (out_cap < D) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
-    if (D && s->modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
-    uint32_t w;
-    const std::vector<uint32_t> seeds = pack_seeds(rows, lens, n_rows, &w);
+    if (D && !out) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    // chacha.rs:69 gen_range(0, m) runs once per seed row and element: no row, no draw, whatever the modulus
+    if (D && n_rows && s->modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
     *out_len = D;
     if (D == 0) return ok();
+    if (n_rows == 0) {                                      // chacha.rs:58 vec![0; self.dimension], returned as it is
+        memset(out, 0, D * 8);
+        return ok();
+    }
+    uint32_t w;
+    const std::vector<uint32_t> seeds = pack_seeds(rows, lens, n_rows, &w);
     // seeds split over the handle's devices, one RCCL reduce (engine_host.cpp); one device: all seeds
     if (sda_status st = host_chacha_combine(h, s->modulus, D, seeds, w, n_rows, out)) return st;
     return ok();
@@ -783,6 +789,32 @@ sda_status sda_snapshot_last_launch(sda_engine* h, uint64_t* blobs, uint64_t* ch
     *grid = s.grid;
     *chunk_bytes = s.chunk_bytes;
     *shifts = s.shifts;
+    return ok();
+}
+
+sda_status sda_recipient_last_launch(sda_engine* h, uint32_t* mask_kind, uint32_t* reveal_mode, uint32_t* fell_back,
+                                     uint32_t* compact, uint32_t* unmask_launches) {
+    SDA_ENTRY;
+    if (!h || !mask_kind || !reveal_mode || !fell_back || !compact || !unmask_launches)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    // a host-side record, final when the call that made it returned: nothing to wait for
+    const sda_engine::RecipientLaunchInfo& r = h->recipient_last;
+    *mask_kind = r.mask_kind;
+    *reveal_mode = r.reveal_mode;
+    *fell_back = r.fell_back;
+    *compact = r.compact;
+    *unmask_launches = r.unmask_launches;
+    return ok();
+}
+
+sda_status sda_participant_last_launch(sda_engine* h, uint32_t* mask_route, uint32_t* share_route, uint32_t* passes) {
+    SDA_ENTRY;
+    if (!h || !mask_route || !share_route || !passes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    // a host-side record, final when the call that made it returned: nothing to wait for
+    const sda_engine::ParticipantLaunchInfo& r = h->participant_last;
+    *mask_route = r.mask_route;
+    *share_route = r.share_route;
+    *passes = r.passes;
     return ok();
 }
 

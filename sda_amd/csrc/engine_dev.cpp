@@ -381,9 +381,14 @@ sda_status sda_chacha_mask_combine_dev(sda_engine* h, int64_t modulus, uint64_t 
                                        uint64_t w, uint64_t n_seeds, int64_t* out, void* stream) {
     SDA_ENTRY;
     if (!h || (dimension && !out) || (n_seeds && w && !seeds)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (dimension && modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
+    // chacha.rs:69 gen_range(0, m) runs once per seed and element: no seed, no draw, whatever the modulus
+    if (dimension && n_seeds && modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
     if (w == 0 || w > 8) return fail(SDA_ERR_INVALID_ARGUMENT, "seed width must be 1..8 words");
     HIP_TRY(hipSetDevice(h->device));
+    if (dimension && n_seeds == 0 && modulus <= 0) {        // chacha.rs:58 vec![0; self.dimension]: no kernel sees m
+        HIP_TRY(hipMemsetAsync(out, 0, dimension * 8, pick(h, stream)));
+        return ok();
+    }
     if (sda_status st = chacha_combine(h, modulus, dimension, seeds, (uint32_t)w, n_seeds, out, pick(h, stream)))
         return st;
     return ok();

@@ -74,6 +74,14 @@ struct sda_engine {
     sda::CombineLaunchInfo combine_last;
     // sda_snapshot_last_launch: what the last successful, non-sizing sda_snapshot_transpose_dev planned and launched
     sda::SnapshotLaunchInfo snap_last;
+    // sda_recipient_last_launch / sda_participant_last_launch: the decisions the last role pipeline call on this
+    // handle took (engine_pipelines.cpp), written when a call of dimension > 0 returns SDA_OK
+    struct RecipientLaunchInfo {
+        uint32_t mask_kind = 0, reveal_mode = 0, fell_back = 0, compact = 0, unmask_launches = 0;
+    } recipient_last;
+    struct ParticipantLaunchInfo {
+        uint32_t mask_route = 0, share_route = 0, passes = 0;
+    } participant_last;
     // streaming host path (host rows -> HBM in row tiles, engine_host.cpp): pinned staging and device
     // tiles, double buffered, and a copy stream so a tile's upload overlaps the previous tile's combine
     hipStream_t copy_stream = nullptr;

@@ -6,6 +6,31 @@ using namespace sda_host;
 // ---------------- fused role pipelines ----------------
 namespace {
 
+// The mask combine of receive.rs:101-117 over n_masks rows of mask_width values: its panics, and *mask_len, the
+// length of the mask it returns.  The host form runs it before its own share-shape checks (the reference combines
+// the masks before it reconstructs), the pipeline as its first step.
+sda_status mask_combine_checks(const sda_masking_scheme* ms, uint64_t n_masks, uint64_t mask_width,
+                               uint64_t* mask_len) {
+    *mask_len = 0;
+    if (ms->kind == SDA_MASKING_NONE) {
+        if (n_masks && mask_width) return fail(SDA_ERR_PRECONDITION, "assertion failed: masks.iter().all(|mask| mask.len() == 0)");
+    } else if (ms->kind == SDA_MASKING_FULL) {
+        *mask_len = n_masks ? mask_width : 0;               // full.rs:38-40
+        if (*mask_len) {                                    // full.rs:45 `%= modulus`
+            int64_t q0;
+            if (sda_status e = modulus_abs(ms->modulus, &q0)) return e;
+        }
+    } else if (ms->kind == SDA_MASKING_CHACHA) {
+        *mask_len = ms->dimension;                          // chacha.rs:58
+        if (mask_width == 0 || mask_width > 8) return fail(SDA_ERR_UNSUPPORTED, "device seeds must be 1..8 words");
+        if (*mask_len && n_masks && ms->modulus <= 0)       // chacha.rs:69 gen_range(0, m)
+            return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
+    } else {
+        return fail(SDA_ERR_INVALID_ARGUMENT, "unknown masking scheme kind");
+    }
+    return SDA_OK;
+}
+
 // receive.rs:80-157 + :14-20 on device-resident inputs (see sda_recipient_reveal_dev).
 sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const void* mask_in, uint64_t n_masks,
                               uint64_t mask_width, const sda_sharing_scheme* ss, uint64_t dimension,
@@ -17,22 +42,7 @@ sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const
     // unmask (:149-152).
     // ---- 1. mask combine: its length and panics ----
     uint64_t mask_len = 0;
-    if (ms->kind == SDA_MASKING_NONE) {
-        if (n_masks && mask_width) return fail(SDA_ERR_PRECONDITION, "assertion failed: masks.iter().all(|mask| mask.len() == 0)");
-    } else if (ms->kind == SDA_MASKING_FULL) {
-        mask_len = n_masks ? mask_width : 0;                // full.rs:38-40
-        if (mask_len) {                                     // full.rs:45 `%= modulus`
-            int64_t q0;
-            if (sda_status e = modulus_abs(ms->modulus, &q0)) return e;
-        }
-    } else if (ms->kind == SDA_MASKING_CHACHA) {
-        mask_len = ms->dimension;                           // chacha.rs:58
-        if (mask_width == 0 || mask_width > 8) return fail(SDA_ERR_UNSUPPORTED, "device seeds must be 1..8 words");
-        if (mask_len && n_masks && ms->modulus <= 0)        // chacha.rs:69 gen_range(0, m)
-            return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
-    } else {
-        return fail(SDA_ERR_INVALID_ARGUMENT, "unknown masking scheme kind");
-    }
+    if (sda_status e = mask_combine_checks(ms, n_masks, mask_width, &mask_len)) return e;
     // ---- 2. reconstruct: masked output length and errors ----
     uint64_t D;
     if (ss->kind == SDA_SHARING_ADDITIVE) {
@@ -73,6 +83,11 @@ sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const
         return e;
     int64_t* dmask = static_cast<int64_t*>(h->pipe);
     int64_t* dmasked = dmask + rup(D * 8) / 8;
+    // sda_recipient_last_launch: collected here, the handle's record only once this call returns SDA_OK
+    sda_engine::RecipientLaunchInfo rec;
+    rec.mask_kind = ms->kind == SDA_MASKING_NONE ? 1 : ms->kind == SDA_MASKING_FULL ? 2 : 3;
+    rec.compact = compact;
+    rec.unmask_launches = 1;
     // 1. masks (receive.rs:101-117)
     if (ms->kind == SDA_MASKING_FULL) {
         if (sda_status e = modulus_abs(ms->modulus, &q)) return e;
@@ -110,7 +125,12 @@ sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const
                                   !(keep && atoi(keep) == 1);
         const int32_t run_mode = (mode == SDA_REVEAL_EXACT && residue_only) ? SDA_REVEAL_CANONICAL : mode;
         hipError_t e = packed_reveal(h, ss, ra, indices, n_idx, run_mode, st);
-        if (e == hipErrorInvalidValue && run_mode != mode) e = packed_reveal(h, ss, ra, indices, n_idx, mode, st);
+        rec.reveal_mode = run_mode == SDA_REVEAL_CANONICAL ? 2 : 1;
+        if (e == hipErrorInvalidValue && run_mode != mode) {
+            e = packed_reveal(h, ss, ra, indices, n_idx, mode, st);
+            rec.reveal_mode = 1;
+            rec.fell_back = 1;
+        }
         if (sda_status r = reveal_status(e, mode)) return r;
     }
     // 3. unmask (receive.rs:149-152) + RecipientOutput::positive (:14-20), one pass
@@ -120,9 +140,12 @@ sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const
         HIP_TRY(hipStreamSynchronize(st));
         bool changed = false;
         if (sda_status e = chacha_combine_end(h, pc, st, &changed)) return e;
-        if (changed)
+        if (changed) {
             HIP_TRY(sda::launch_unmask_positive(dmasked, dmask, D, q, output_modulus, out, st));
+            rec.unmask_launches = 2;
+        }
     }
+    h->recipient_last = rec;
     *out_len = D;
     return SDA_OK;
 }
@@ -157,19 +180,20 @@ sda_status sda_recipient_reveal(sda_engine* h, const sda_masking_scheme* ms, con
         return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     *out_len = 0;
     HIP_TRY(hipSetDevice(h->device));
-    // host-side shape checks in the reference's order, then one upload
-    uint64_t share_len = n_idx ? share_lens[0] : 0;
-    for (uint64_t i = 0; i < n_idx; ++i) {
-        if (share_lens[i] == share_len) continue;
-        if (ss->kind == SDA_SHARING_ADDITIVE) return fail(SDA_ERR_MISMATCHING_DIMENSION, "Mismatching dimension");
-        share_len = share_lens[i] < share_len ? share_lens[i] : share_len;   // packed: reads [0, B) of each
-    }
+    // host-side shape checks in the reference's order -- the mask combine (receive.rs:101-117) before the
+    // reconstruction (:120-146) -- then one upload
     uint64_t width = 0;
     std::vector<uint32_t> seeds;
     if (ms->kind == SDA_MASKING_FULL) {
         width = n_masks ? mask_lens[0] : 0;
-        for (uint64_t i = 0; i < n_masks; ++i)
-            if (mask_lens[i] != width) return fail(SDA_ERR_PRECONDITION, "assertion failed: mask.len() == dimension");
+        for (uint64_t i = 0; i < n_masks; ++i) {
+            if (mask_lens[i] == width) continue;
+            if (width) {                                    // full.rs:45-46 folds row 0 (`%= 0` panics) before :43 reads row i
+                int64_t q0;
+                if (sda_status e = modulus_abs(ms->modulus, &q0)) return e;
+            }
+            return fail(SDA_ERR_PRECONDITION, "assertion failed: mask.len() == dimension");
+        }
     } else if (ms->kind == SDA_MASKING_CHACHA) {
         uint32_t w;
         seeds = pack_seeds(mask_rows, mask_lens, n_masks, &w);        // key = first 8 words, zero padded
@@ -177,6 +201,22 @@ sda_status sda_recipient_reveal(sda_engine* h, const sda_masking_scheme* ms, con
     } else {
         for (uint64_t i = 0; i < n_masks; ++i)
             if (mask_lens[i]) return fail(SDA_ERR_PRECONDITION, "assertion failed: masks.iter().all(|mask| mask.len() == 0)");
+    }
+    if (ms->kind == SDA_MASKING_FULL || ms->kind == SDA_MASKING_CHACHA) {
+        uint64_t mask_len;
+        if (sda_status e = mask_combine_checks(ms, n_masks, width, &mask_len)) return e;
+    }
+    uint64_t share_len = n_idx ? share_lens[0] : 0;
+    for (uint64_t i = 0; i < n_idx; ++i) {
+        if (share_lens[i] == share_len) continue;
+        if (ss->kind == SDA_SHARING_ADDITIVE) {
+            if (share_len) {                                // additive.rs:66-67 folds row 0 (`%= 0` panics) before :64 reads row i
+                int64_t m0;
+                if (sda_status e = modulus_abs(ss->modulus, &m0)) return e;
+            }
+            return fail(SDA_ERR_MISMATCHING_DIMENSION, "Mismatching dimension");
+        }
+        share_len = share_lens[i] < share_len ? share_lens[i] : share_len;   // packed: reads [0, B) of each
     }
     const uint64_t outn = ss->kind == SDA_SHARING_ADDITIVE ? share_len : dimension;
     // A multi-device handle spreads the mask combine (receive.rs:113-116, the dominant cost at configs[4]) over its
@@ -207,6 +247,7 @@ sda_status sda_recipient_reveal(sda_engine* h, const sda_masking_scheme* ms, con
     if (ms->kind == SDA_MASKING_CHACHA && !seeds.empty() && !multi_mask)
         HIP_TRY(hipMemcpyAsync(dmask, seeds.data(), seeds.size() * 4, hipMemcpyHostToDevice, h->stream));
     uint64_t len = 0;
+    const sda_engine::RecipientLaunchInfo before = h->recipient_last;
     if (sda_status e = multi_mask
                            ? recipient_pipeline(h, &full_row, h->hs_dev, 1, ms->dimension, ss, dimension, indices, dsh,
                                                 n_idx, share_len, output_modulus, mode, dout, (uint64_t)-1, &len, h->stream)
@@ -214,7 +255,11 @@ sda_status sda_recipient_reveal(sda_engine* h, const sda_masking_scheme* ms, con
                                                 dimension, indices, dsh, n_idx, share_len, output_modulus, mode, dout,
                                                 (uint64_t)-1, &len, h->stream))
         return e;
-    if (out_cap < len) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    if (out_cap < len) {
+        h->recipient_last = before;              // the call fails: the record stays the previous call's
+        return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    }
+    if (multi_mask && len) h->recipient_last.mask_kind = 4;   // the pipeline saw the combined row as a Full mask
     if (len) HIP_TRY(hipMemcpyAsync(out, dout, len * 8, hipMemcpyDeviceToHost, h->stream));
     *out_len = len;
     return finish(h);
@@ -257,9 +302,17 @@ static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms,
     // count is checked at the end of the call (a nonzero count -- probability < 2^-28 per draw -- redoes
     // the mask exactly, then every later step)
     bool mask_pending = false;
+    // sda_participant_last_launch: collected here, the handle's record only once this call returns SDA_OK
+    sda_engine::ParticipantLaunchInfo rec;
+    rec.mask_route = 1;
+    rec.share_route = packed ? (kd ? 4 : 3) : (kd ? 2 : 1);
+    rec.passes = 1;
     int64_t* cmask = nullptr;
     uint32_t* cseed = nullptr;
     uint32_t cw = 0;
+    // chacha.rs:26 assert_eq!(self.dimension, secrets.len()): before any draw, and for an empty secrets vector too
+    if (ms->kind == SDA_MASKING_CHACHA && ms->dimension != D)
+        return fail(SDA_ERR_PRECONDITION, "assertion failed: dimension == secrets.len()");
     if (ms->kind != SDA_MASKING_NONE && D) {
         if (ms->modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
         if (sda_status e = ensure(&h->pipe, &h->pipe_bytes, 2 * rup(D * 8) + 256)) return e;
@@ -267,8 +320,8 @@ static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms,
         if (ms->kind == SDA_MASKING_FULL) {
             if (!full_masks) return fail(SDA_ERR_INVALID_ARGUMENT, "Full masking needs the drawn masks");
             HIP_TRY(sda::launch_addsub_trem(secrets, full_masks, +1, D, dm, ms->modulus, st));      // full.rs:28-31
+            rec.mask_route = 2;
         } else if (ms->kind == SDA_MASKING_CHACHA) {
-            if (ms->dimension != D) return fail(SDA_ERR_PRECONDITION, "assertion failed: dimension == secrets.len()");
             const uint64_t want = (ms->seed_bitsize + 31) / 32;
             if (seed_words != want || (seed_words && !seed))
                 return fail(SDA_ERR_PRECONDITION, "expected %llu seed words", (unsigned long long)want);
@@ -284,9 +337,11 @@ static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms,
                                                           h->rej_host, &info));
                 record_chacha(h, info);
                 mask_pending = true;
+                rec.mask_route = 3;
             } else {
                 if (sda_status e = chacha_combine(h, ms->modulus, D, dseed, w, 1, dmask, st)) return e;
                 HIP_TRY(sda::launch_addsub_trem(secrets, dmask, +1, D, dm, ms->modulus, st));
+                rec.mask_route = 4;
             }
             cmask = dmask;
             cseed = dseed;
@@ -340,8 +395,10 @@ static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms,
             }
             HIP_TRY(sda::launch_addsub_trem(secrets, cmask, +1, D, const_cast<int64_t*>(masked), ms->modulus, st));
             if (sda_status e = share_and_encode()) return e;
+            rec.passes = 2;
         }
     }
+    if (D) h->participant_last = rec;
     return ok();
 }
 

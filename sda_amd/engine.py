@@ -77,6 +77,28 @@ COMBINE_PIPE = 8
 CombineLaunch = collections.namedtuple("CombineLaunch",
                                        "kind elem_bytes vec rows variant grid wlo nwide per_cu")
 
+# sda_recipient_last_launch's mask_kind and reveal_mode codes
+RECIPIENT_MASK_NONE_YET = 0
+RECIPIENT_MASK_NONE = 1
+RECIPIENT_MASK_FULL = 2
+RECIPIENT_MASK_CHACHA = 3
+RECIPIENT_MASK_COMBINED_ROW = 4
+RECIPIENT_REVEAL_ADDITIVE = 0
+RECIPIENT_REVEAL_EXACT = 1
+RECIPIENT_REVEAL_CANONICAL = 2
+RecipientLaunch = collections.namedtuple("RecipientLaunch", "mask_kind reveal_mode fell_back compact unmask_launches")
+
+# sda_participant_last_launch's route codes
+PARTICIPANT_MASK_NONE = 1
+PARTICIPANT_MASK_FULL_ADD = 2
+PARTICIPANT_MASK_CHACHA_FUSED = 3
+PARTICIPANT_MASK_CHACHA_COMBINE_ADD = 4
+PARTICIPANT_SHARE_ADDITIVE = 1
+PARTICIPANT_SHARE_ADDITIVE_KEYED = 2
+PARTICIPANT_SHARE_PACKED = 3
+PARTICIPANT_SHARE_PACKED_KEYED = 4
+ParticipantLaunch = collections.namedtuple("ParticipantLaunch", "mask_route share_route passes")
+
 # Elements one workgroup of the draws kernel produces (csrc/kernels.h kDrawsTile): the sizes at which
 # sda_draws_dev's grid gains a workgroup
 DRAWS_TILE = 2048
@@ -132,6 +154,8 @@ SIGNATURES = [
     ("sda_codec_last_launch", _st, [_vp, _u32p, _u32p, _u32p, _u64p]),
     ("sda_combine_last_launch", _st, [_vp, _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, _u32p, _u32p, _u32p]),
     ("sda_snapshot_last_launch", _st, [_vp, _u64p, _u64p, _u64p, _u64p, _u32p]),
+    ("sda_recipient_last_launch", _st, [_vp, _u32p, _u32p, _u32p, _u32p, _u32p]),
+    ("sda_participant_last_launch", _st, [_vp, _u32p, _u32p, _u32p]),
     ("sda_combine_split_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     ("sda_combine_split_prefix_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp,
                                            _vp]),
@@ -583,6 +607,23 @@ class Engine:
         v = [C.c_uint64() for _ in range(4)] + [C.c_uint32()]
         _check(self.lib.sda_snapshot_last_launch(self.h, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    def recipient_last_launch(self):
+        """RecipientLaunch(mask_kind, reveal_mode, fell_back, compact, unmask_launches) of the handle's last
+        recipient_reveal / recipient_reveal_dev with a non-empty output: the RECIPIENT_MASK_* and RECIPIENT_REVEAL_*
+        codes, whether a substituted canonical reveal fell back to the exact one, whether the clerk vectors were
+        compacted, and the unmask launches (2 after a late ChaCha resolve) (sda_recipient_last_launch)."""
+        v = [C.c_uint32() for _ in range(5)]
+        _check(self.lib.sda_recipient_last_launch(self.h, *[C.byref(x) for x in v]))
+        return RecipientLaunch(*[int(x.value) for x in v])
+
+    def participant_last_launch(self):
+        """ParticipantLaunch(mask_route, share_route, passes) of the handle's last participant_share*_dev of
+        dimension > 0: the PARTICIPANT_MASK_* and PARTICIPANT_SHARE_* codes, and 2 passes when a rejecting ChaCha
+        mask was redone (sda_participant_last_launch)."""
+        v = [C.c_uint32() for _ in range(3)]
+        _check(self.lib.sda_participant_last_launch(self.h, *[C.byref(x) for x in v]))
+        return ParticipantLaunch(*[int(x.value) for x in v])
 
     def packed_keyed_last_launch(self):
         """(path, staged_bytes) of the handle's last keyed packed-Shamir launch: path 0 none yet, 1 the draws were

@@ -90,6 +90,8 @@ class CpuEngine:
 
     def chacha_mask_combine_dev(self, modulus, dimension, seeds_ptr, w, n_seeds, out_ptr, stream=None):
         self.calls.append("chacha_mask_combine_dev")
+        if n_seeds and dimension and modulus <= 0:                 # chacha.rs:69 gen_range(0, m), once per seed row
+            raise ValueError("Rng.gen_range called with low >= high")
         seeds = _view(seeds_ptr, n_seeds * w, ctypes.c_uint32).reshape(n_seeds, w).astype(np.int64) \
             if n_seeds else np.zeros((0, w), np.int64)
         _view(out_ptr, dimension)[:] = O.chacha_mask_combine(modulus, dimension, seeds)

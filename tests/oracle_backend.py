@@ -70,6 +70,8 @@ class OracleBackend:
             if rc:
                 raise SdaError(ERR_PRECONDITION, "assertion failed: mask.len() == dimension")
             return out
+        if rows and scheme.dimension and scheme.modulus <= 0:      # chacha.rs:69 gen_range(0, m), once per seed row
+            raise SdaError(ERR_PRECONDITION, "Rng.gen_range called with low >= high")
         w = max([len(r) for r in rows] + [1])
         seeds = np.zeros((len(rows), w), np.int64)
         for i, r in enumerate(rows):
