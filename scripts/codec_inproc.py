@@ -3,6 +3,8 @@ field-share payloads encoded once, the variants interleaved call block by call b
     python scripts/codec_inproc.py [rounds] [variants ...]        (SDA_INPROC_KNOB names the variable)
 SDA_INPROC_SHAPE=encode times the encode of the same matrix instead (varint_encode_dev, host wait included);
 SDA_INPROC_SHAPE=decode the decode of the payloads back into a 1000 x 1M i64 matrix (varint_decode_dev).
+SDA_INPROC_KNOB=lib: the variants are builds of libsda_engine.so, each loaded into this process
+(Engine(lib_path=...)) and timed on the same payloads: the A/B of one build against another.
 """
 import os
 import sys
@@ -19,6 +21,7 @@ variants = sys.argv[2:] or ["4", "2"]
 knob = os.environ.get("SDA_INPROC_KNOB", "SDA_SLOT_CPL")
 torch.cuda.init()
 eng = Engine(0)
+engs = {v: Engine(0, lib_path=v) if knob == "lib" else eng for v in variants}
 N, D = 1000, 1_000_000
 st = torch.cuda.current_stream().cuda_stream
 x = torch.empty((N, D), dtype=torch.int64, device="cuda")
@@ -44,13 +47,12 @@ else:
 
 def call(v):
     if dec:
-        eng.varint_decode_dev(buf.data_ptr(), off, mat.data_ptr(), D, st)
+        engs[v].varint_decode_dev(buf.data_ptr(), off, mat.data_ptr(), D, st)
         outs[v].copy_(mat[N - 1])
     elif enc:
-        eng.varint_encode_dev(x.data_ptr(), N, D, D, outs[v].data_ptr(), ecap, st)
+        engs[v].varint_encode_dev(x.data_ptr(), N, D, D, outs[v].data_ptr(), ecap, st)
     else:
-        eng.clerk_decode_combine_dev(M, buf.data_ptr(), off, outs[v].data_ptr(), D, st)
-
+        engs[v].clerk_decode_combine_dev(M, buf.data_ptr(), off, outs[v].data_ptr(), D, st)
 
 
 res = {v: [] for v in variants}

@@ -9,10 +9,12 @@ Prints the median time per launch of each, their ratio next to the byte model's 
 8 + 8 + payload bytes per value: the size pass and the write pass each read every value), and the payload bytes,
 which must be equal.  Then the same for one sda_participant_share_dev against sda_participant_share32_dev
 (ChaCha masking, configs[2]'s scheme, with a payload) at configs[4]'s dimension, 10M.
-SDA_INPROC_ALT_LIB=<libsda_engine.so built with EXTRA=-DSDA_ENC32_CHUNK=4096> adds a third encode leg from that
-library, loaded into the same process (Engine(lib_path=...)): the A/B of the int32 chunk size;
+SDA_INPROC_ALT_LIB=<another build of libsda_engine.so> adds both encode legs from that library, loaded into the same
+process (Engine(lib_path=...)): the A/B of the int32 chunk size (EXTRA=-DSDA_ENC32_CHUNK=4096), or of this tree
+against its parent's library, each encoder with its twin of the other build as the yardstick;
 SDA_INPROC_ALT_NOTE is printed next to its file name to say what that build is.
-SDA_INPROC_ROWS / SDA_INPROC_DIM / SDA_INPROC_PDIM shrink the job (rehearsal).
+SDA_INPROC_ROWS / SDA_INPROC_DIM / SDA_INPROC_PDIM shrink the job (rehearsal); SDA_INPROC_PDIM=0 leaves the
+participant pipeline out.
 """
 import os
 import sys
@@ -55,7 +57,7 @@ def report(tag, res, legs, bytes_of, unit):
                 f"spread {100 * (s[-1] - s[0]) / med[name]:.2f} %  bytes {nb / 1e9:.3f} GB ({nb / unit:.2f} B/value)  "
                 f"{nb / (med[name] * 1e-3) / PEAK:.3f} of 8 TB/s")
         if twin:
-            line += f"  time / i64 {med[name] / med[twin]:.3f}  (byte ratio {nb / bytes_of[twin]:.3f})"
+            line += f"  time / {twin} {med[name] / med[twin]:.3f}  (byte ratio {nb / bytes_of[twin]:.3f})"
         say(line)
         say(f"[{tag}] {name:<22} per-launch ms by round: " + " ".join(f"{x:.4f}" for x in res[name]))
 
@@ -81,17 +83,17 @@ assert int(flag.item()) == 0
 cap = N * D * 5 + 32
 LEGS = [("encode i64", None), ("encode int32", "encode i64")]
 if alt:
-    LEGS.append(("encode int32 alt lib", "encode i64"))
+    LEGS += [("encode i64 alt lib", "encode i64"), ("encode int32 alt lib", "encode int32")]
 bufs = {name: torch.zeros(cap, dtype=torch.uint8, device="cuda") for name, _ in LEGS}
 sizes = {}
 
 
 def enc(name):
     b = bufs[name]
-    if name == "encode i64":
-        sizes[name] = eng.varint_encode_dev(x64.data_ptr(), N, D, D, b.data_ptr(), cap, st)
+    e = alt if name.endswith("alt lib") else eng
+    if name.startswith("encode i64"):
+        sizes[name] = e.varint_encode_dev(x64.data_ptr(), N, D, D, b.data_ptr(), cap, st)
     else:
-        e = alt if name.endswith("alt lib") else eng
         sizes[name] = e.varint_encode32_dev(x32.data_ptr(), N, D, D, b.data_ptr(), cap, st)
 
 
@@ -106,19 +108,33 @@ same = {name: bool(np.array_equal(sizes[name], sizes["encode i64"])) and
         all(torch.equal(bufs[name][a:min(a + (1 << 28), total)], bufs["encode i64"][a:min(a + (1 << 28), total)])
             for a in range(0, total, 1 << 28)) for name, _ in LEGS[1:]}
 say(f"[encode] payload bytes: " + "  ".join(f"{name} {int(sizes[name].sum())}" for name, _ in LEGS) +
-    f"  ({total / N / D:.3f} B/value); int32 payload == i64 payload: {same}")
+    f"  ({total / N / D:.3f} B/value); payload == i64 payload: {same}")
 assert all(same.values())
 res = {name: [] for name, _ in LEGS}
 for r in range(rounds):
     for name, _ in LEGS:
         res[name].append(timed(lambda: enc(name), 5))
 nv = float(N) * D
-bytes_of = {name: (16.0 if name == "encode i64" else 8.0) * nv + total for name, _ in LEGS}
+bytes_of = {name: (16.0 if name.startswith("encode i64") else 8.0) * nv + total for name, _ in LEGS}
 report("encode", res, LEGS, bytes_of, nv)
 del x64, x32, bufs
 
+
+def finish():
+    eng.close()
+    if alt:
+        alt.close()
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 # ---- the participant pipeline ----
 PD = int(os.environ.get("SDA_INPROC_PDIM", 10_000_000))
+if PD == 0:
+    finish()
+    sys.exit(0)
 ms = S.ChaChaMasking(p, PD, 128)
 k, t, n = sch.secret_count, sch.privacy_threshold(), sch.share_count
 B = (PD + k - 1) // k
@@ -163,10 +179,4 @@ for r in range(rounds):
 pin = 24.0 * PD + 8.0 * B * t
 pbytes = {"participant i64": pin + 24.0 * n * B + ptotal, "participant int32": pin + 12.0 * n * B + ptotal}
 report("participant", pres, PLEGS, pbytes, float(n) * B)
-eng.close()
-if alt:
-    alt.close()
-if out_path:
-    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
+finish()

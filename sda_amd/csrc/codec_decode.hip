@@ -1,4 +1,5 @@
-// codec.hip -- share payload codec on gfx950.
+// codec_decode.hip -- share payload codec on gfx950: the decoder, the clerk's
+// decode -> combine and their launchers.  The encoder is codec_encode.hip.
 //
 // Reference: client/src/crypto/encryption/sodium.rs
 //   encrypt (:36-41):  for share in shares { size = share.encode_var(&mut buf); bytes.extend(&buf[..size]) }
@@ -28,18 +29,15 @@
 // the previous tile and how many of its terminators precede the tile; then one workgroup per column
 // tile walks the blobs in order, decodes its tile's slice of each payload (read once, plus at most a
 // sub-chunk per tile edge) and folds it into combiner.rs:16-28's exact recurrence in registers.
-#include <stdlib.h>
-
 #include <type_traits>
 
-#include "kernels.h"
+#include "codec_common.h"
 
 namespace sda {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWPT = 4;                       // 16-byte words per thread: word t + 256 k, k < kWPT
+constexpr int kWPT = 4;                      // 16-byte words per thread: word t + 256 k, k < kWPT
 constexpr uint64_t kSubBytes = kThreads * 16; // one sub-region = one word per thread
 constexpr uint64_t kRegionBytes = kSubBytes * kWPT;
 // Slots per region of the clerk's slot decode: a region of 16 KiB holds at most 4096 elements of >= 4
@@ -47,20 +45,6 @@ constexpr uint64_t kRegionBytes = kSubBytes * kWPT;
 // job takes the matrix path; the slot buffer has kRegionBytes - kSlotCap slots of slack at its end, so the
 // last region's overflowing stores stay inside it.
 constexpr uint64_t kSlotCap = 4096;
-
-
-
-// Inclusive prefix sum over the 64 lanes of a wave with DPP (row shifts, then the row broadcasts of
-// gfx9): six VALU adds, no LDS round trips.
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);   // row_shr:1
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);   // row_shr:2
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);   // row_shr:4
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);   // row_shr:8
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);   // row_bcast:15
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);   // row_bcast:31
-    return x;
-}
 
 // Sum over each row of 16 lanes, in the row's last lane (the first four steps of wave_incl_scan).
 __device__ __forceinline__ uint32_t row16_incl_scan(uint32_t x) {
@@ -80,11 +64,6 @@ __device__ __forceinline__ uint32_t msb_nibble(uint32_t d) {
 // 16 bytes as a 16-bit mask of "continuation" bytes (bit j = byte j has 0x80).
 __device__ __forceinline__ uint32_t cont_mask(uint4 w) {
     return msb_nibble(w.x) | (msb_nibble(w.y) << 4) | (msb_nibble(w.z) << 8) | (msb_nibble(w.w) << 12);
-}
-
-__device__ __forceinline__ uint8_t byte_of(const uint4& w, int j) {
-    const uint32_t d = j < 4 ? w.x : (j < 8 ? w.y : (j < 12 ? w.z : w.w));
-    return (uint8_t)(d >> (8 * (j & 3)));
 }
 
 // The region word this thread owns and its 32-byte window (previous word + own word):
@@ -645,7 +624,6 @@ __device__ __forceinline__ Window window_rel(uint32_t cm, int32_t w0, int32_t lo
     return W;
 }
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 nt_word(const uint8_t* bytes, uint64_t w) {      // read once: non-temporal
     const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(bytes) + w);
     return make_uint4(v[0], v[1], v[2], v[3]);
@@ -843,388 +821,6 @@ __global__ void varint_sequential_kernel(const uint8_t* __restrict__ bytes, cons
     if (!out) blob_count[b] = c;
 }
 
-// ---------------- encode ----------------
-__device__ __forceinline__ uint32_t varint_size(int64_t v) {
-    const uint64_t z = ((uint64_t)v << 1) ^ (uint64_t)(v >> 63);
-    const int bits = 64 - __builtin_clzll(z | 1);
-    return (uint32_t)((bits + 6) / 7);
-}
-
-constexpr uint32_t kEncChunk = 2048;          // elements per encode block
-constexpr uint32_t kEncPer = kEncChunk / kThreads;
-constexpr uint32_t kEncPairs = kEncPer / 2;   // size pass: rounds of one adjacent element pair per lane
-#ifndef SDA_ENC_EPL
-#define SDA_ENC_EPL 2
-#endif
-constexpr uint32_t kEncEpl = SDA_ENC_EPL;     // write pass: adjacent elements per lane per round (even)
-constexpr uint32_t kEncRounds = kEncChunk / (kEncEpl * kThreads);
-typedef int64_t i64x2 __attribute__((ext_vector_type(2)));
-// A full chunk whose first element is 16-byte aligned is read as element pairs (one 16-byte load per
-// lane: a wave moves 1 KiB per load instruction instead of 512 B).
-__device__ __forceinline__ bool enc_pairs_ok(const int64_t* rowp, uint64_t e0, uint64_t len) {
-    return e0 + kEncChunk <= len && ((uintptr_t)(rowp + e0) & 15) == 0;
-}
-
-// sizes of each [row][chunk] block of elements
-__global__ __launch_bounds__(kThreads) void varint_size_kernel(const int64_t* __restrict__ vals, uint64_t len,
-                                                               uint64_t stride, uint32_t chunks,
-                                                               uint64_t* __restrict__ chunk_bytes) {
-    const uint32_t c = blockIdx.x, row = blockIdx.y;
-    const uint64_t e0 = (uint64_t)c * kEncChunk;
-    const int64_t* rowp = vals + (uint64_t)row * stride;
-    uint64_t n = 0;
-    if (enc_pairs_ok(rowp, e0, len)) {          // 16-byte loads: element pairs (order is irrelevant here)
-#pragma unroll
-        for (uint32_t q = 0; q < kEncPairs; ++q) {
-            const i64x2 x = __builtin_nontemporal_load(reinterpret_cast<const i64x2*>(rowp + e0) + q * kThreads + threadIdx.x);
-            n += varint_size(x[0]) + varint_size(x[1]);
-        }
-    } else {
-#pragma unroll
-        for (uint32_t q = 0; q < kEncPer; ++q) {
-            const uint64_t e = e0 + q * kThreads + threadIdx.x;
-            if (e < len) n += varint_size(rowp[e]);
-        }
-    }
-    __shared__ uint64_t red[kThreads / 64];
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t s = 0;
-        for (int i = 0; i < kThreads / 64; ++i) s += red[i];
-        chunk_bytes[(uint64_t)row * chunks + c] = s;
-    }
-}
-
-// inverse of leb_pack8: 7-bit groups of z -> bytes (group i in byte i), continuation bits not set
-__device__ __forceinline__ uint64_t leb_spread8(uint64_t z) {
-    uint64_t x = z & 0x00FFFFFFFFFFFFFFull;
-    x = (x & 0x000000000FFFFFFFull) | ((x & 0x00FFFFFFF0000000ull) << 4);
-    x = (x & 0x00003FFF00003FFFull) | ((x & 0x0FFFC0000FFFC000ull) << 2);
-    x = (x & 0x007F007F007F007Full) | ((x & 0x3F803F803F803F80ull) << 1);
-    return x;
-}
-
-// write: coalesced 16-byte loads (lane t: kEncEpl adjacent elements per round q), one block-wide
-// scan of the lane sizes per q, each element's bytes ORed into a zeroed LDS image of the chunk's output (its 8 + 2 bytes shifted
-// to their byte offset: 2-4 ds_or_b32, no per-byte stores), the image aligned to the chunk's global
-// byte offset mod 16 so that the interior leaves as 16-byte stores; the two partial 16-byte words at
-// the ends (shared with the neighbouring chunks) are written byte-wise.
-// Chunk (c, row) starts at dst + row_base[row] + chunk_off (the exclusive scan of the row's chunk_bytes);
-// nothing is written when *too_big (the rows do not fit dst_cap).
-template <bool NT>
-__global__ __launch_bounds__(kThreads) void varint_write_kernel(const int64_t* __restrict__ vals, uint64_t len,
-                                                                uint64_t stride, uint32_t chunks,
-                                                                const uint64_t* __restrict__ chunk_off,
-                                                                const uint64_t* __restrict__ row_base,
-                                                                const uint32_t* __restrict__ too_big,
-                                                                uint8_t* __restrict__ dst) {
-    const uint32_t c = blockIdx.x, row = blockIdx.y;
-    if (*too_big) return;
-    const uint64_t e0 = (uint64_t)c * kEncChunk;
-    constexpr uint32_t kBufQuads = (kEncChunk * 10 + 32) / 16;      // lead < 16, + the shifted tail dwords
-    __shared__ uint4 buf4[kBufQuads];
-    __shared__ uint32_t wsum[kThreads / 64];
-    uint32_t* buf = reinterpret_cast<uint32_t*>(buf4);
-    const uint8_t* b8 = reinterpret_cast<const uint8_t*>(buf4);
-    uint8_t* gdst = dst + row_base[row] + chunk_off[(uint64_t)row * chunks + c];
-    const uint32_t lead = (uint32_t)((uintptr_t)gdst & 15);
-    for (uint32_t k = threadIdx.x; k < kBufQuads; k += kThreads) buf4[k] = make_uint4(0, 0, 0, 0);
-    // round q: lane t owns the kEncEpl adjacent elements e0 + R q + kEncEpl t + j (R = kEncEpl * 256;
-    // 16-byte loads when the chunk allows it), so one block-wide scan of the lane sizes places R elements
-    const int64_t* rowp = vals + (uint64_t)row * stride;
-    int64_t v[kEncRounds][kEncEpl];
-    if (enc_pairs_ok(rowp, e0, len)) {
-#pragma unroll
-        for (uint32_t q = 0; q < kEncRounds; ++q)
-#pragma unroll
-            for (uint32_t j = 0; j < kEncEpl / 2; ++j) {
-                const i64x2 x = __builtin_nontemporal_load(
-                    reinterpret_cast<const i64x2*>(rowp + e0 + kEncEpl * (q * kThreads + threadIdx.x)) + j);
-                v[q][2 * j] = x[0];
-                v[q][2 * j + 1] = x[1];
-            }
-    } else {
-#pragma unroll
-        for (uint32_t q = 0; q < kEncRounds; ++q)
-#pragma unroll
-            for (uint32_t j = 0; j < kEncEpl; ++j) {
-                const uint64_t e = e0 + kEncEpl * (q * kThreads + threadIdx.x) + j;
-                v[q][j] = e < len ? rowp[e] : 0;
-            }
-    }
-    uint32_t base = lead;
-#pragma unroll
-    for (uint32_t q = 0; q < kEncRounds; ++q) {
-        const uint64_t e = e0 + kEncEpl * (q * kThreads + threadIdx.x);
-        uint32_t ns[kEncEpl], pre[kEncEpl], np = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kEncEpl; ++j) {
-            ns[j] = e + j < len ? varint_size(v[q][j]) : 0u;
-            pre[j] = np;
-            np += ns[j];
-        }
-        const uint32_t incl = wave_incl_scan(np);
-        __syncthreads();                                     // wsum of the previous q consumed (and, at
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;    // q = 0, the zeroed image visible)
-        __syncthreads();
-        uint32_t off0 = base + incl - np, total = 0;
-        for (uint32_t w = 0; w < kThreads / 64; ++w) {
-            if (w < (threadIdx.x >> 6)) off0 += wsum[w];
-            total += wsum[w];
-        }
-        base += total;
-#pragma unroll
-        for (uint32_t h = 0; h < kEncEpl; ++h) {
-            const uint32_t n = ns[h], off = off0 + pre[h];
-            const uint64_t z = ((uint64_t)v[q][h] << 1) ^ (uint64_t)(v[q][h] >> 63);
-            if (n) {
-                // bytes 0..7: groups 0..7, continuation bit on every byte but the element's last;
-                // bytes 8, 9 (n > 8): groups 8 and 9
-                const uint32_t nc = n - 1;
-                const uint64_t cont = nc >= 8 ? 0x8080808080808080ull : (0x8080808080808080ull & ((1ull << (8 * nc)) - 1));
-                const uint64_t W = leb_spread8(z) | cont;
-                const uint32_t g8 = (uint32_t)(z >> 56) & 0x7Fu, g9 = (uint32_t)(z >> 63);
-                const uint32_t E = n > 8 ? (g8 | (n > 9 ? 0x80u : 0u) | (g9 << 8)) : 0u;
-                const uint32_t sh = (off & 3) * 8, dw = off >> 2;
-                const uint32_t o0 = (uint32_t)W << sh;
-                const uint32_t o1 = (uint32_t)(W >> (32 - sh));                          // sh = 0: W's high word
-                const uint32_t o2 = (uint32_t)(((((uint64_t)E) << 32) | (uint32_t)(W >> 32)) >> (32 - sh));
-                const uint32_t o3 = sh ? E >> (32 - sh) : 0u;
-                atomicOr(&buf[dw], o0);                                                  // ds_or_b32
-                if (o1) atomicOr(&buf[dw + 1], o1);
-                if (o2) atomicOr(&buf[dw + 2], o2);
-                if (o3) atomicOr(&buf[dw + 3], o3);
-            }
-        }
-    }
-    __syncthreads();
-    const uint32_t end = base;                               // lead + chunk bytes
-    uint4* d128 = reinterpret_cast<uint4*>(gdst - lead);
-    uint8_t* d8 = gdst - lead;
-    const uint32_t nq = (end + 15) / 16;
-    for (uint32_t k = threadIdx.x; k < nq; k += kThreads) {
-        const uint32_t lo = k * 16, hi = lo + 16;
-        if (lo >= lead && hi <= end) {
-            if constexpr (NT)
-                __builtin_nontemporal_store(reinterpret_cast<const u32x4*>(buf4)[k], reinterpret_cast<u32x4*>(d128) + k);
-            else d128[k] = buf4[k];
-        } else {
-            for (uint32_t i = lo; i < hi; ++i)
-                if (i >= lead && i < end) d8[i] = b8[i];
-        }
-    }
-}
-
-// ---------------- encode, int32 rows ----------------
-// The same byte stream from int32 rows (a field share below 2^31): an element takes at most 5 bytes, so the
-// zigzag, the size and the byte image stay in 32-bit registers, an element touches at most two LDS dwords, and
-// the chunk's LDS image is 5 bytes per element instead of 10.
-#ifndef SDA_ENC32_CHUNK
-#define SDA_ENC32_CHUNK 2048                  // A/B against 4096: DESIGN.md §4.5
-#endif
-constexpr uint32_t kEnc32Chunk = SDA_ENC32_CHUNK;   // elements per int32 encode block
-constexpr uint32_t kEnc32Epl = 4;             // adjacent elements per lane per round: one 16-byte load
-constexpr uint32_t kEnc32Rounds = kEnc32Chunk / (kEnc32Epl * kThreads);
-static_assert(kEnc32Chunk % (kEnc32Epl * kThreads) == 0 && kEnc32Chunk * 5 / 16 <= kEncChunk * 10 / 16,
-              "int32 encode chunk: whole rounds, and an LDS image no larger than the i64 kernel's");
-typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t zigzag32(int32_t v) { return ((uint32_t)v << 1) ^ (uint32_t)(v >> 31); }
-__device__ __forceinline__ uint32_t varint_size32(uint32_t z) { return (uint32_t)(32 - __builtin_clz(z | 1) + 6) / 7; }
-// A full chunk whose first element is 16-byte aligned is read as element quads.  A row of int32 starts 0, 4, 8
-// or 12 bytes off a 16-byte boundary (stride and base are only 4-byte aligned), and every chunk of the row
-// shares that offset (the chunk is a multiple of 4 elements): only offset 0 takes the 16-byte loads.
-__device__ __forceinline__ bool enc32_quads_ok(const int32_t* rowp, uint64_t e0, uint64_t len) {
-    return e0 + kEnc32Chunk <= len && ((uintptr_t)(rowp + e0) & 15) == 0;
-}
-
-__global__ __launch_bounds__(kThreads) void varint_size32_kernel(const int32_t* __restrict__ vals, uint64_t len,
-                                                                 uint64_t stride, uint32_t chunks,
-                                                                 uint64_t* __restrict__ chunk_bytes) {
-    const uint32_t c = blockIdx.x, row = blockIdx.y;
-    const uint64_t e0 = (uint64_t)c * kEnc32Chunk;
-    const int32_t* rowp = vals + (uint64_t)row * stride;
-    uint32_t n = 0;                                          // <= 5 * kEnc32Chunk
-    if (enc32_quads_ok(rowp, e0, len)) {
-#pragma unroll
-        for (uint32_t q = 0; q < kEnc32Rounds; ++q) {
-            const i32x4 x = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(rowp + e0) + q * kThreads + threadIdx.x);
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) n += varint_size32(zigzag32(x[j]));
-        }
-    } else {
-#pragma unroll
-        for (uint32_t q = 0; q < kEnc32Chunk / kThreads; ++q) {
-            const uint64_t e = e0 + q * kThreads + threadIdx.x;
-            if (e < len) n += varint_size32(zigzag32(rowp[e]));
-        }
-    }
-    __shared__ uint32_t red[kThreads / 64];
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t s = 0;
-        for (int i = 0; i < kThreads / 64; ++i) s += red[i];
-        chunk_bytes[(uint64_t)row * chunks + c] = s;
-    }
-}
-
-// write: varint_write_kernel's structure (rounds of coalesced loads, one block-wide scan of the lane sizes per
-// round, a zeroed LDS image aligned to the chunk's global byte offset mod 16, 16-byte interior stores and
-// byte-wise partial end words).  Per element: groups 0..3 spread into one dword, group 4 in a fifth byte; the 40
-// bits shifted to the byte offset are one or two ds_or_b32.  The image is lead (< 16) + at most
-// 5 * kEnc32Chunk bytes; a dword past an element's last byte is never touched (o1 == 0 is skipped).
-template <bool NT>
-__global__ __launch_bounds__(kThreads) void varint_write32_kernel(const int32_t* __restrict__ vals, uint64_t len,
-                                                                  uint64_t stride, uint32_t chunks,
-                                                                  const uint64_t* __restrict__ chunk_off,
-                                                                  const uint64_t* __restrict__ row_base,
-                                                                  const uint32_t* __restrict__ too_big,
-                                                                  uint8_t* __restrict__ dst) {
-    const uint32_t c = blockIdx.x, row = blockIdx.y;
-    if (*too_big) return;
-    const uint64_t e0 = (uint64_t)c * kEnc32Chunk;
-    constexpr uint32_t kBufQuads = (kEnc32Chunk * 5 + 15 + 15) / 16;     // lead <= 15, rounded up to a quad
-    __shared__ uint4 buf4[kBufQuads];
-    __shared__ uint32_t wsum[kThreads / 64];
-    uint32_t* buf = reinterpret_cast<uint32_t*>(buf4);
-    const uint8_t* b8 = reinterpret_cast<const uint8_t*>(buf4);
-    uint8_t* gdst = dst + row_base[row] + chunk_off[(uint64_t)row * chunks + c];
-    const uint32_t lead = (uint32_t)((uintptr_t)gdst & 15);
-    for (uint32_t k = threadIdx.x; k < kBufQuads; k += kThreads) buf4[k] = make_uint4(0, 0, 0, 0);
-    // round q: lane t owns the 4 adjacent elements e0 + 1024 q + 4 t + j
-    const int32_t* rowp = vals + (uint64_t)row * stride;
-    uint32_t z[kEnc32Rounds][kEnc32Epl];
-    const bool full = e0 + kEnc32Chunk <= len;
-    if (enc32_quads_ok(rowp, e0, len)) {
-#pragma unroll
-        for (uint32_t q = 0; q < kEnc32Rounds; ++q) {
-            const i32x4 x = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(rowp + e0) + q * kThreads + threadIdx.x);
-#pragma unroll
-            for (uint32_t j = 0; j < kEnc32Epl; ++j) z[q][j] = zigzag32(x[j]);
-        }
-    } else {
-#pragma unroll
-        for (uint32_t q = 0; q < kEnc32Rounds; ++q)
-#pragma unroll
-            for (uint32_t j = 0; j < kEnc32Epl; ++j) {
-                const uint64_t e = e0 + kEnc32Epl * (q * kThreads + threadIdx.x) + j;
-                z[q][j] = e < len ? zigzag32(rowp[e]) : 0u;
-            }
-    }
-    uint32_t base = lead;
-#pragma unroll
-    for (uint32_t q = 0; q < kEnc32Rounds; ++q) {
-        const uint64_t e = e0 + kEnc32Epl * (q * kThreads + threadIdx.x);
-        uint32_t ns[kEnc32Epl], pre[kEnc32Epl], np = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kEnc32Epl; ++j) {
-            ns[j] = (full || e + j < len) ? varint_size32(z[q][j]) : 0u;
-            pre[j] = np;
-            np += ns[j];
-        }
-        const uint32_t incl = wave_incl_scan(np);
-        __syncthreads();                                     // wsum of the previous q consumed (and, at
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;    // q = 0, the zeroed image visible)
-        __syncthreads();
-        uint32_t off0 = base + incl - np, total = 0;
-        for (uint32_t w = 0; w < kThreads / 64; ++w) {
-            if (w < (threadIdx.x >> 6)) off0 += wsum[w];
-            total += wsum[w];
-        }
-        base += total;
-#pragma unroll
-        for (uint32_t h = 0; h < kEnc32Epl; ++h) {
-            const uint32_t n = ns[h], off = off0 + pre[h], zz = z[q][h];
-            if (n) {
-                // bytes 0..3: groups 0..3, continuation bit on every byte but the element's last; byte 4: group 4
-                uint32_t x = zz & 0x0FFFFFFFu;
-                x = (x & 0x00003FFFu) | ((x & 0x0FFFC000u) << 2);
-                x = (x & 0x007F007Fu) | ((x & 0x3F803F80u) << 1);
-                const uint32_t nc = n - 1;
-                const uint32_t lo = x | (nc >= 4 ? 0x80808080u : (0x80808080u & ((1u << (8 * nc)) - 1)));
-                const uint32_t hi = zz >> 28;                                // 0 unless n == 5
-                const uint32_t sh = (off & 3) * 8, dw = off >> 2;
-                const uint32_t o0 = lo << sh;
-                const uint32_t o1 = sh ? __builtin_amdgcn_alignbit(hi, lo, 32 - sh) : hi;
-                atomicOr(&buf[dw], o0);                                      // ds_or_b32
-                if (o1) atomicOr(&buf[dw + 1], o1);
-            }
-        }
-    }
-    __syncthreads();
-    const uint32_t end = base;                               // lead + chunk bytes
-    uint4* d128 = reinterpret_cast<uint4*>(gdst - lead);
-    uint8_t* d8 = gdst - lead;
-    const uint32_t nq = (end + 15) / 16;
-    for (uint32_t k = threadIdx.x; k < nq; k += kThreads) {
-        const uint32_t lo = k * 16, hi = lo + 16;
-        if (lo >= lead && hi <= end) {
-            if constexpr (NT)
-                __builtin_nontemporal_store(reinterpret_cast<const u32x4*>(buf4)[k], reinterpret_cast<u32x4*>(d128) + k);
-            else d128[k] = buf4[k];
-        } else {
-            for (uint32_t i = lo; i < hi; ++i)
-                if (i >= lead && i < end) d8[i] = b8[i];
-        }
-    }
-}
-
-// exclusive scan of chunk_bytes per row (one block per row) + row base; row_bytes = total
-// One workgroup: rows placed back to back -- row_base = exclusive scan of row_bytes; *too_big = the total
-// exceeds cap (the write pass then writes nothing and the host reports it).
-__global__ __launch_bounds__(kThreads) void varint_rows_kernel(const uint64_t* __restrict__ row_bytes, uint64_t rows,
-                                                               uint64_t cap, uint64_t* __restrict__ row_base,
-                                                               uint32_t* __restrict__ too_big) {
-    __shared__ uint64_t part[kThreads];
-    uint64_t carry = 0;
-    for (uint64_t base = 0; base < rows; base += kThreads) {
-        const uint64_t r = base + threadIdx.x;
-        const uint64_t v = r < rows ? row_bytes[r] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < kThreads; o <<= 1) {
-            const uint64_t add = threadIdx.x >= (uint32_t)o ? part[threadIdx.x - o] : 0;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (r < rows) row_base[r] = carry + part[threadIdx.x] - v;
-        carry += part[kThreads - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *too_big = carry > cap ? 1u : 0u;
-}
-
-__global__ __launch_bounds__(kThreads) void varint_offsets_kernel(const uint64_t* __restrict__ chunk_bytes,
-                                                                  uint32_t chunks, const uint64_t* __restrict__ row_base,
-                                                                  uint64_t* __restrict__ chunk_off,
-                                                                  uint64_t* __restrict__ row_bytes) {
-    const uint32_t row = blockIdx.x;
-    __shared__ uint64_t part[kThreads];
-    uint64_t carry = row_base ? row_base[row] : 0, total = 0;
-    for (uint32_t base = 0; base < chunks; base += kThreads) {
-        const uint32_t c = base + threadIdx.x;
-        const uint64_t v = c < chunks ? chunk_bytes[(uint64_t)row * chunks + c] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < kThreads; o <<= 1) {
-            const uint64_t add = threadIdx.x >= (uint32_t)o ? part[threadIdx.x - o] : 0;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (c < chunks) chunk_off[(uint64_t)row * chunks + c] = carry + part[threadIdx.x] - v;
-        carry += part[kThreads - 1];
-        total += part[kThreads - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && row_bytes) row_bytes[row] = total;
-}
-
 }  // namespace
 
 // ---------------- host-side planning ----------------
@@ -1272,32 +868,90 @@ uint64_t varint_tile_plan_bytes(uint64_t n_blobs, uint64_t dim) {
 }
 uint64_t varint_fused_tiles(uint64_t dim) { return (dim + kDcTile - 1) / kDcTile; }
 
-hipError_t launch_varint_count(const uint8_t* bytes, const uint64_t* blob_off_host, uint64_t n_blobs,
-                               const VarintPlan& plan, void* work, uint64_t* counts_host, bool* irregular_any,
-                               hipStream_t s, bool sub_counts, bool* long_any) {
-    const size_t R = plan.regions;
-    DecodeWork w = carve(work, R, n_blobs);
+// ---------------- launch sequences the launchers share ----------------
+// The job's plan on the device (blob_off, blob_region), then the flags the caller's kernels raise, zeroed.
+static hipError_t upload_plan(const DecodeWork& w, const uint64_t* blob_off_host, uint64_t n_blobs,
+                              const VarintPlan& plan, bool zero_irregular, bool zero_wide, hipStream_t s) {
     hipError_t e;
     if ((e = hipMemcpyAsync(w.blob_off, blob_off_host, (n_blobs + 1) * 8, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(w.blob_region, plan.blob_region.data(), (n_blobs + 1) * 8, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(w.irregular, 0, n_blobs * 4, s)) != hipSuccess) return e;
-    for (uint64_t y0 = 0; R && y0 < n_blobs; y0 += 65535) {
-        const unsigned ny = (unsigned)(n_blobs - y0 < 65535 ? n_blobs - y0 : 65535);
-        hipLaunchKernelGGL(varint_count_kernel, dim3((unsigned)plan.max_regions, ny), dim3(kThreads), 0, s, bytes,
-                           w.blob_region, w.blob_off, (uint32_t)y0, w.region_count, w.irregular,
-                           sub_counts ? w.sub_count : nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (zero_irregular && (e = hipMemsetAsync(w.irregular, 0, n_blobs * 4, s)) != hipSuccess) return e;
+    if (zero_wide && (e = hipMemsetAsync(w.wide, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
+// launch(y0, ny) once per slice of at most 65,535 blobs (the grid.y limit); info->passes counts the slices.
+template <class Launch>
+static hipError_t each_blob_slice(uint64_t n_blobs, CodecLaunchInfo* info, Launch&& launch) {
+    for (uint64_t y0 = 0; y0 < n_blobs; y0 += 65535) {
+        launch((uint32_t)y0, (unsigned)(n_blobs - y0 < 65535 ? n_blobs - y0 : 65535));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        if (info) ++info->passes;
     }
-    hipLaunchKernelGGL(varint_scan_kernel, dim3((unsigned)n_blobs), dim3(kThreads), 0, s, w.region_count,
-                       w.blob_region, w.region_base, w.blob_count);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return hipSuccess;
+}
+
+// pass B over blobs [b0, b0 + nb)
+static hipError_t launch_scan(const DecodeWork& w, uint64_t b0, uint64_t nb, hipStream_t s) {
+    hipLaunchKernelGGL(varint_scan_kernel, dim3((unsigned)nb), dim3(kThreads), 0, s, w.region_count, w.blob_region,
+                       w.region_base, w.blob_count, (uint32_t)b0);
+    return hipGetLastError();
+}
+
+// the irregular blobs: counted (out == nullptr) or decoded, at most cap values each
+static hipError_t launch_sequential(const uint8_t* bytes, uint64_t n_blobs, const DecodeWork& w, int64_t* out,
+                                    uint64_t out_stride, uint64_t cap, const uint32_t* skip, hipStream_t s) {
     hipLaunchKernelGGL(varint_sequential_kernel, dim3((unsigned)((n_blobs + 63) / 64)), dim3(64), 0, s, bytes,
-                       w.blob_off, (uint32_t)n_blobs, w.irregular, w.blob_count, (int64_t*)nullptr, 0, 0);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+                       w.blob_off, (uint32_t)n_blobs, w.irregular, w.blob_count, out, out_stride, cap, skip);
+    return hipGetLastError();
+}
+
+// count -> scan -> sequential count: every blob's element count and flags (sub_count: pass A's sub-chunk counts)
+static hipError_t enqueue_count(const uint8_t* bytes, uint64_t n_blobs, const VarintPlan& plan, const DecodeWork& w,
+                                uint16_t* sub_count, hipStream_t s) {
+    hipError_t e = each_blob_slice(plan.regions ? n_blobs : 0, nullptr, [&](uint32_t y0, unsigned ny) {
+        hipLaunchKernelGGL(varint_count_kernel, dim3((unsigned)plan.max_regions, ny), dim3(kThreads), 0, s, bytes,
+                           w.blob_region, w.blob_off, y0, w.region_count, w.irregular, sub_count);
+    });
+    if (e != hipSuccess) return e;
+    if ((e = launch_scan(w, 0, n_blobs, s)) != hipSuccess) return e;
+    return launch_sequential(bytes, n_blobs, w, nullptr, 0, 0, nullptr, s);
+}
+
+// pass C over every blob, one launch per slice
+template <typename OutT, bool SPARSE>
+static hipError_t enqueue_decode(const uint8_t* bytes, uint64_t n_blobs, const VarintPlan& plan, const DecodeWork& w,
+                                 OutT* out, uint64_t out_stride, uint32_t* wide, const uint32_t* skip, hipStream_t s,
+                                 CodecLaunchInfo* info) {
+    return each_blob_slice(plan.regions ? n_blobs : 0, info, [&](uint32_t y0, unsigned ny) {
+        hipLaunchKernelGGL((dec_kernel<OutT, SPARSE>()), dim3((unsigned)plan.max_regions, ny), dim3(kThreads), 0, s,
+                           bytes, w.blob_region, w.blob_off, y0, SPARSE ? (const uint64_t*)nullptr : w.region_base,
+                           SPARSE ? (const uint32_t*)nullptr : w.irregular, out, out_stride, wide,
+                           SPARSE ? w.region_count : (uint32_t*)nullptr, skip);
+    });
+}
+
+// The call's one wait: the blob counts (counts_host != nullptr) and n_flags flag words come back, after the
+// whole job.
+static hipError_t read_back(const DecodeWork& w, uint64_t n_blobs, uint64_t* counts_host, const uint32_t* flags,
+                            uint64_t n_flags, uint32_t* flags_host, hipStream_t s) {
+    hipError_t e;
+    if (counts_host && (e = hipMemcpyAsync(counts_host, w.blob_count, n_blobs * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(flags_host, flags, n_flags * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    return hipStreamSynchronize(s);
+}
+
+// ---------------- the decode launchers ----------------
+hipError_t launch_varint_count(const uint8_t* bytes, const uint64_t* blob_off_host, uint64_t n_blobs,
+                               const VarintPlan& plan, void* work, uint64_t* counts_host, bool* irregular_any,
+                               hipStream_t s, bool sub_counts, bool* long_any) {
+    DecodeWork w = carve(work, plan.regions, n_blobs);
+    hipError_t e;
+    if ((e = upload_plan(w, blob_off_host, n_blobs, plan, true, false, s)) != hipSuccess) return e;
+    if ((e = enqueue_count(bytes, n_blobs, plan, w, sub_counts ? w.sub_count : nullptr, s)) != hipSuccess) return e;
     std::vector<uint32_t> irr(n_blobs);
-    if ((e = hipMemcpyAsync(counts_host, w.blob_count, n_blobs * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(irr.data(), w.irregular, n_blobs * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+    if ((e = read_back(w, n_blobs, counts_host, w.irregular, n_blobs, irr.data(), s)) != hipSuccess) return e;
     *irregular_any = false;
     bool lng = false;
     for (uint64_t b = 0; b < n_blobs; ++b) {
@@ -1311,23 +965,13 @@ hipError_t launch_varint_count(const uint8_t* bytes, const uint64_t* blob_off_ho
 hipError_t launch_varint_decode(const uint8_t* bytes, uint64_t n_blobs, const VarintPlan& plan, void* work,
                                 int64_t* out, uint64_t out_stride, uint64_t len, bool irregular_any,
                                 hipStream_t s, CodecLaunchInfo* info) {
-    const size_t R = plan.regions;
-    DecodeWork w = carve(work, R, n_blobs);
+    DecodeWork w = carve(work, plan.regions, n_blobs);
     hipError_t e;
     if (info) info->passes = 0;
-    for (uint64_t y0 = 0; R && y0 < n_blobs; y0 += 65535) {
-        const unsigned ny = (unsigned)(n_blobs - y0 < 65535 ? n_blobs - y0 : 65535);
-        hipLaunchKernelGGL(dec_kernel<int64_t>(), dim3((unsigned)plan.max_regions, ny), dim3(kThreads), 0, s,
-                           bytes, w.blob_region, w.blob_off, (uint32_t)y0, w.region_base, w.irregular, out, out_stride,
-                           w.wide, (uint32_t*)nullptr, (const uint32_t*)nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (info) ++info->passes;
-    }
+    if ((e = enqueue_decode<int64_t, false>(bytes, n_blobs, plan, w, out, out_stride, w.wide, nullptr, s, info)) != hipSuccess) return e;
     if (irregular_any) {
         if (info) info->fell_back |= kCodecSequential;
-        hipLaunchKernelGGL(varint_sequential_kernel, dim3((unsigned)((n_blobs + 63) / 64)), dim3(64), 0, s, bytes,
-                           w.blob_off, (uint32_t)n_blobs, w.irregular, w.blob_count, out, out_stride, len);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = launch_sequential(bytes, n_blobs, w, out, out_stride, len, nullptr, s)) != hipSuccess) return e;
     }
     return hipSuccess;
 }
@@ -1335,44 +979,17 @@ hipError_t launch_varint_decode(const uint8_t* bytes, uint64_t n_blobs, const Va
 hipError_t launch_varint_decode_one_wait(const uint8_t* bytes, const uint64_t* blob_off_host, uint64_t n_blobs,
                                         const VarintPlan& plan, void* work, int64_t* out, uint64_t out_stride,
                                         uint64_t* counts_host, bool* too_long, hipStream_t s) {
-    const size_t R = plan.regions;
-    DecodeWork w = carve(work, R, n_blobs);
+    DecodeWork w = carve(work, plan.regions, n_blobs);
     hipError_t e;
-    if ((e = hipMemcpyAsync(w.blob_off, blob_off_host, (n_blobs + 1) * 8, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(w.blob_region, plan.blob_region.data(), (n_blobs + 1) * 8, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(w.irregular, 0, n_blobs * 4, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(w.wide, 0, sizeof(uint32_t), s)) != hipSuccess) return e;      // the capacity flag
-    for (uint64_t y0 = 0; R && y0 < n_blobs; y0 += 65535) {
-        const unsigned ny = (unsigned)(n_blobs - y0 < 65535 ? n_blobs - y0 : 65535);
-        hipLaunchKernelGGL(varint_count_kernel, dim3((unsigned)plan.max_regions, ny), dim3(kThreads), 0, s, bytes,
-                           w.blob_region, w.blob_off, (uint32_t)y0, w.region_count, w.irregular, (uint16_t*)nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(varint_scan_kernel, dim3((unsigned)n_blobs), dim3(kThreads), 0, s, w.region_count,
-                       w.blob_region, w.region_base, w.blob_count);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const unsigned seq_grid = (unsigned)((n_blobs + 63) / 64);
-    hipLaunchKernelGGL(varint_sequential_kernel, dim3(seq_grid), dim3(64), 0, s, bytes, w.blob_off, (uint32_t)n_blobs,
-                       w.irregular, w.blob_count, (int64_t*)nullptr, 0, 0, (const uint32_t*)nullptr);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = upload_plan(w, blob_off_host, n_blobs, plan, true, true, s)) != hipSuccess) return e;   // wide: the capacity flag
+    if ((e = enqueue_count(bytes, n_blobs, plan, w, nullptr, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(varint_cap_kernel, dim3(1), dim3(kThreads), 0, s, (const uint64_t*)w.blob_count, n_blobs,
                        out_stride, w.wide);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    for (uint64_t y0 = 0; R && y0 < n_blobs; y0 += 65535) {
-        const unsigned ny = (unsigned)(n_blobs - y0 < 65535 ? n_blobs - y0 : 65535);
-        hipLaunchKernelGGL(dec_kernel<int64_t>(), dim3((unsigned)plan.max_regions, ny), dim3(kThreads), 0, s,
-                           bytes, w.blob_region, w.blob_off, (uint32_t)y0, w.region_base, w.irregular, out, out_stride,
-                           (uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)w.wide);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(varint_sequential_kernel, dim3(seq_grid), dim3(64), 0, s, bytes, w.blob_off, (uint32_t)n_blobs,
-                       w.irregular, w.blob_count, out, out_stride, out_stride, (const uint32_t*)w.wide);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    // the call's one wait: the counts and the capacity flag, after the whole job
+    if ((e = enqueue_decode<int64_t, false>(bytes, n_blobs, plan, w, out, out_stride, nullptr, w.wide, s, nullptr)) != hipSuccess) return e;
+    if ((e = launch_sequential(bytes, n_blobs, w, out, out_stride, out_stride, w.wide, s)) != hipSuccess) return e;
     uint32_t flag = 0;
-    if ((e = hipMemcpyAsync(counts_host, w.blob_count, n_blobs * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(&flag, w.wide, sizeof(flag), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+    if ((e = read_back(w, n_blobs, counts_host, w.wide, 1, &flag, s)) != hipSuccess) return e;
     *too_long = flag != 0;
     return hipSuccess;
 }
@@ -1380,22 +997,13 @@ hipError_t launch_varint_decode_one_wait(const uint8_t* bytes, const uint64_t* b
 hipError_t launch_varint_decode_narrow(const uint8_t* bytes, uint64_t n_blobs, const VarintPlan& plan, void* work,
                                        int32_t* out, uint64_t out_stride, bool* wide_host, hipStream_t s,
                                        CodecLaunchInfo* info) {
-    const size_t R = plan.regions;
-    DecodeWork w = carve(work, R, n_blobs);
+    DecodeWork w = carve(work, plan.regions, n_blobs);
     hipError_t e;
     if ((e = hipMemsetAsync(w.wide, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
     if (info) info->passes = 0;
-    for (uint64_t y0 = 0; R && y0 < n_blobs; y0 += 65535) {
-        const unsigned ny = (unsigned)(n_blobs - y0 < 65535 ? n_blobs - y0 : 65535);
-        hipLaunchKernelGGL(dec_kernel<int32_t>(), dim3((unsigned)plan.max_regions, ny), dim3(kThreads), 0, s,
-                           bytes, w.blob_region, w.blob_off, (uint32_t)y0, w.region_base, w.irregular, out, out_stride,
-                           w.wide, (uint32_t*)nullptr, (const uint32_t*)nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (info) ++info->passes;
-    }
+    if ((e = enqueue_decode<int32_t, false>(bytes, n_blobs, plan, w, out, out_stride, w.wide, nullptr, s, info)) != hipSuccess) return e;
     uint32_t flag = 0;
-    if ((e = hipMemcpyAsync(&flag, w.wide, sizeof(flag), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+    if ((e = read_back(w, n_blobs, nullptr, w.wide, 1, &flag, s)) != hipSuccess) return e;
     *wide_host = flag != 0;
     return hipSuccess;
 }
@@ -1437,6 +1045,38 @@ size_t varint_slot_bytes(const VarintPlan& plan, uint64_t n_blobs, uint64_t dim)
     return slot_area_bytes(sg.regions) + ntiles * (sg.G ? sg.G : n_blobs) * 8 + (sg.G ? dim * 8 : 0) + 256;
 }
 
+// What every slot_combine_kernel launch of a job shares; a launch adds its blobs, its destination and the state
+// it continues from.
+struct SlotCombine {
+    unsigned ntiles;
+    const int32_t* slots;
+    const uint64_t* tplan;
+    const uint64_t* blob_count;
+    const uint32_t* flags;
+    uint64_t out_cap;
+    Mod64 M;
+    bool small_m;
+    hipStream_t s;
+};
+template <int CPL>
+static hipError_t launch_slot_combine_cpl(const SlotCombine& c, uint64_t nb, int64_t* dst, const int64_t* acc_in) {
+    if (c.small_m)
+        hipLaunchKernelGGL((slot_combine_kernel<CPL, 8, true>), dim3(c.ntiles), dim3(kThreads), 0, c.s, c.slots,
+                           c.tplan, nb, c.blob_count, c.flags, c.out_cap, dst, c.M, acc_in);
+    else
+        hipLaunchKernelGGL((slot_combine_kernel<CPL, 8, false>), dim3(c.ntiles), dim3(kThreads), 0, c.s, c.slots,
+                           c.tplan, nb, c.blob_count, c.flags, c.out_cap, dst, c.M, acc_in);
+    return hipGetLastError();
+}
+static hipError_t launch_slot_combine(const SlotCombine& c, uint32_t cpl, uint64_t nb, int64_t* dst,
+                                      const int64_t* acc_in) {
+    switch (cpl) {
+        case 4: return launch_slot_combine_cpl<4>(c, nb, dst, acc_in);
+        case 2: return launch_slot_combine_cpl<2>(c, nb, dst, acc_in);
+        default: return launch_slot_combine_cpl<1>(c, nb, dst, acc_in);
+    }
+}
+
 hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64_t* blob_off_host, uint64_t n_blobs,
                                               const VarintPlan& plan, void* work, void* slot_buf, int64_t* out,
                                               uint64_t out_cap, int64_t modulus, uint64_t* counts_host,
@@ -1456,21 +1096,11 @@ hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64
     const uint64_t ntiles = (blob_off_host[1] - blob_off_host[0] + tile - 1) / tile;
     if (ntiles > 0x7FFFFFFFull || R * kSlotCap >= (1ull << 39)) return hipErrorInvalidValue;
     hipError_t e;
-    if ((e = hipMemcpyAsync(w.blob_off, blob_off_host, (n_blobs + 1) * 8, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(w.blob_region, plan.blob_region.data(), (n_blobs + 1) * 8, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(w.wide, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
-    const Mod64 M = make_mod64(modulus > 0 ? modulus : 1);
-    const bool small_m = modulus <= ((int64_t)1 << 62);
-#define SLOT_COMBINE(C, SM, NB, DST, ACC_IN)                                                                       \
-    hipLaunchKernelGGL((slot_combine_kernel<C, 8, SM>), dim3((unsigned)ntiles), dim3(kThreads), 0, s, slots,         \
-                       (const uint64_t*)tplan, NB, (const uint64_t*)w.blob_count, (const uint32_t*)w.wide, out_cap, \
-                       DST, M, ACC_IN)
-#define SLOT_COMBINE_ANY(NB, DST, ACC_IN)                                                                            \
-    do {                                                                                                             \
-        if (cpl == 4) { if (small_m) SLOT_COMBINE(4, true, NB, DST, ACC_IN); else SLOT_COMBINE(4, false, NB, DST, ACC_IN); } \
-        else if (cpl == 2) { if (small_m) SLOT_COMBINE(2, true, NB, DST, ACC_IN); else SLOT_COMBINE(2, false, NB, DST, ACC_IN); } \
-        else { if (small_m) SLOT_COMBINE(1, true, NB, DST, ACC_IN); else SLOT_COMBINE(1, false, NB, DST, ACC_IN); } \
-    } while (0)
+    if ((e = upload_plan(w, blob_off_host, n_blobs, plan, false, true, s)) != hipSuccess) return e;
+    const SlotCombine comb = {(unsigned)ntiles, slots, tplan, w.blob_count, w.wide, out_cap,
+                              make_mod64(modulus > 0 ? modulus : 1), modulus <= ((int64_t)1 << 62), s};
+    const bool combine = ntiles && modulus > 0;  // modulus 0: invalid -- no combine (an error if the dimension is > 0)
+    const unsigned plan_gx = (unsigned)((plan.max_regions + kThreads - 1) / kThreads);   // slot_plan_kernel: one lane per region
     if (sg.G) {
         // grouped: decode, scan, check and combine one group of blobs at a time through the one slot buffer
         // (region r of the group starting at blob g0 sits at slot (r - blob_region[g0]) * kSlotCap); the
@@ -1487,104 +1117,71 @@ hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64
                                    w.region_count, (const uint32_t*)nullptr);
                 if ((e = hipGetLastError()) != hipSuccess) return e;
             }
-            hipLaunchKernelGGL(varint_scan_kernel, dim3((unsigned)ng), dim3(kThreads), 0, s, w.region_count,
-                               w.blob_region, w.region_base, w.blob_count, (uint32_t)g0);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
+            if ((e = launch_scan(w, g0, ng, s)) != hipSuccess) return e;
             hipLaunchKernelGGL(slot_dims_kernel, dim3(1), dim3(kThreads), 0, s, (const uint64_t*)w.blob_count, g1,
                                w.wide, g0);
             if ((e = hipGetLastError()) != hipSuccess) return e;
-            if (ntiles && modulus > 0) {
-                hipLaunchKernelGGL(slot_plan_kernel, dim3((unsigned)((plan.max_regions + kThreads - 1) / kThreads),
-                                   (unsigned)ng), dim3(kThreads), 0, s, w.blob_region, w.region_base, w.region_count,
-                                   0u, ng, ntiles, tile, (const uint32_t*)w.wide, tplan, g0, R0);
+            if (combine) {
+                hipLaunchKernelGGL(slot_plan_kernel, dim3(plan_gx, (unsigned)ng), dim3(kThreads), 0, s,
+                                   w.blob_region, w.region_base, w.region_count, 0u, ng, ntiles, tile,
+                                   (const uint32_t*)w.wide, tplan, g0, R0);
                 if ((e = hipGetLastError()) != hipSuccess) return e;
-                SLOT_COMBINE_ANY(ng, acc, g0 ? (const int64_t*)acc : (const int64_t*)nullptr);
-                if ((e = hipGetLastError()) != hipSuccess) return e;
+                if ((e = launch_slot_combine(comb, cpl, ng, acc, g0 ? acc : nullptr)) != hipSuccess) return e;
             }
         }
-        if (ntiles && modulus > 0) {
+        if (combine) {
             hipLaunchKernelGGL(slot_commit_kernel, dim3(2048), dim3(kThreads), 0, s, (const int64_t*)acc,
                                (const uint64_t*)w.blob_count, (const uint32_t*)w.wide, out_cap, out);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
-        if ((e = hipMemcpyAsync(counts_host, w.blob_count, n_blobs * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(flags_host, w.wide, sizeof(uint32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-        return hipStreamSynchronize(s);
+        return read_back(w, n_blobs, counts_host, w.wide, 1, flags_host, s);
     }
-    for (uint64_t y0 = 0; R && y0 < n_blobs; y0 += 65535) {
-        const unsigned ny = (unsigned)(n_blobs - y0 < 65535 ? n_blobs - y0 : 65535);
-        hipLaunchKernelGGL((dec_kernel<int32_t, true>()), dim3((unsigned)plan.max_regions, ny), dim3(kThreads),
-                           0, s, bytes, w.blob_region, w.blob_off, (uint32_t)y0, (const uint64_t*)nullptr,
-                           (const uint32_t*)nullptr, slots, 0, w.wide, w.region_count, (const uint32_t*)nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (info) ++info->passes;
-    }
-    hipLaunchKernelGGL(varint_scan_kernel, dim3((unsigned)n_blobs), dim3(kThreads), 0, s, w.region_count,
-                       w.blob_region, w.region_base, w.blob_count);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = enqueue_decode<int32_t, true>(bytes, n_blobs, plan, w, slots, 0, w.wide, nullptr, s, info)) != hipSuccess) return e;
+    if ((e = launch_scan(w, 0, n_blobs, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(slot_dims_kernel, dim3(1), dim3(kThreads), 0, s, (const uint64_t*)w.blob_count, n_blobs, w.wide);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ntiles && modulus > 0) {       // modulus 0: invalid -- no combine (an error if the dimension is > 0)
-        for (uint64_t y0 = 0; y0 < n_blobs; y0 += 65535) {
-            const unsigned ny = (unsigned)(n_blobs - y0 < 65535 ? n_blobs - y0 : 65535);
-            hipLaunchKernelGGL(slot_plan_kernel, dim3((unsigned)((plan.max_regions + kThreads - 1) / kThreads), ny),
-                               dim3(kThreads), 0, s, w.blob_region, w.region_base, w.region_count, (uint32_t)y0,
-                               n_blobs, ntiles, tile, (const uint32_t*)w.wide, tplan);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-        }
-        SLOT_COMBINE_ANY(n_blobs, out, (const int64_t*)nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (combine) {
+        e = each_blob_slice(n_blobs, nullptr, [&](uint32_t y0, unsigned ny) {
+            hipLaunchKernelGGL(slot_plan_kernel, dim3(plan_gx, ny), dim3(kThreads), 0, s, w.blob_region,
+                               w.region_base, w.region_count, y0, n_blobs, ntiles, tile, (const uint32_t*)w.wide, tplan);
+        });
+        if (e != hipSuccess) return e;
+        if ((e = launch_slot_combine(comb, cpl, n_blobs, out, nullptr)) != hipSuccess) return e;
     }
-#undef SLOT_COMBINE_ANY
-#undef SLOT_COMBINE
-    // the call's one wait: the counts and the flags, after the whole job
-    if ((e = hipMemcpyAsync(counts_host, w.blob_count, n_blobs * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(flags_host, w.wide, sizeof(uint32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    return hipStreamSynchronize(s);
+    return read_back(w, n_blobs, counts_host, w.wide, 1, flags_host, s);
+}
+
+template <int DEPTH, bool MULTI>
+static uint32_t launch_fused(const uint8_t* bytes, const uint64_t* blob_off, uint64_t n_blobs,
+                             const uint64_t* tile_plan, uint64_t ntiles, uint64_t dim, int64_t* out, const Mod64& M,
+                             bool small_m, hipStream_t s) {
+    hipLaunchKernelGGL((varint_decode_combine_kernel<DEPTH, MULTI>), dim3((unsigned)ntiles), dim3(kDcThreads), 0, s,
+                       bytes, blob_off, n_blobs, tile_plan, ntiles, dim, out, M, small_m);
+    return DEPTH;                                // the DEPTH of the instantiation launched
 }
 
 hipError_t launch_varint_decode_combine(const uint8_t* bytes, uint64_t n_blobs, const VarintPlan& plan, void* work,
                                         uint64_t* tile_plan, uint64_t dim, int64_t* out, int64_t modulus,
                                         bool multi, hipStream_t s, CodecLaunchInfo* info) {
     if (dim == 0 || n_blobs == 0) return hipSuccess;
-    const size_t R = plan.regions;
-    DecodeWork w = carve(work, R, n_blobs);
+    DecodeWork w = carve(work, plan.regions, n_blobs);
     const uint64_t ntiles = varint_fused_tiles(dim);
     if (ntiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipError_t e;
     if (info) info->passes = 0;
-    for (uint64_t y0 = 0; y0 < n_blobs; y0 += 65535) {
-        const unsigned ny = (unsigned)(n_blobs - y0 < 65535 ? n_blobs - y0 : 65535);
-        if (info) ++info->passes;
+    e = each_blob_slice(n_blobs, info, [&](uint32_t y0, unsigned ny) {
         hipLaunchKernelGGL(varint_tile_plan_kernel, dim3((unsigned)((plan.max_regions + kThreads - 1) / kThreads), ny),
-                           dim3(kThreads), 0, s, w.blob_off, w.blob_region, w.region_base, w.sub_count, (uint32_t)y0,
-                           n_blobs, ntiles, tile_plan);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+                           dim3(kThreads), 0, s, w.blob_off, w.blob_region, w.region_base, w.sub_count, y0, n_blobs,
+                           ntiles, tile_plan);
+    });
+    if (e != hipSuccess) return e;
     const Mod64 M = make_mod64(modulus);
     const bool small_m = modulus <= ((int64_t)1 << 62);
     const char* env = getenv("SDA_DC_DEPTH");                  // A/B knob: blobs prefetched ahead
     const int depth = env ? atoi(env) : 4;
-    const dim3 grid((unsigned)ntiles), block(kDcThreads);
-    const uint64_t* tp = tile_plan;
-    uint32_t ran = 0;                            // the DEPTH of the instantiation launched
-    if (multi) {
-        ran = 2;
-        hipLaunchKernelGGL((varint_decode_combine_kernel<2, true>), grid, block, 0, s, bytes, w.blob_off, n_blobs,
-                           tp, ntiles, dim, out, M, small_m);
-    } else if (depth == 2) {
-        ran = 2;
-        hipLaunchKernelGGL((varint_decode_combine_kernel<2, false>), grid, block, 0, s, bytes, w.blob_off, n_blobs,
-                           tp, ntiles, dim, out, M, small_m);
-    } else if (depth == 8) {
-        ran = 8;
-        hipLaunchKernelGGL((varint_decode_combine_kernel<8, false>), grid, block, 0, s, bytes, w.blob_off, n_blobs,
-                           tp, ntiles, dim, out, M, small_m);
-    } else {
-        ran = 4;
-        hipLaunchKernelGGL((varint_decode_combine_kernel<4, false>), grid, block, 0, s, bytes, w.blob_off, n_blobs,
-                           tp, ntiles, dim, out, M, small_m);
-    }
+    auto run = [&](auto launch) { return launch(bytes, w.blob_off, n_blobs, tile_plan, ntiles, dim, out, M, small_m, s); };
+    const uint32_t ran = multi ? run(launch_fused<2, true>) : depth == 2 ? run(launch_fused<2, false>)
+                       : depth == 8 ? run(launch_fused<8, false>) : run(launch_fused<4, false>);
     if (info) {
         info->path = multi ? kCodecFusedMulti : kCodecFused;
         info->width = ran;
@@ -1592,98 +1189,5 @@ hipError_t launch_varint_decode_combine(const uint8_t* bytes, uint64_t n_blobs, 
     return hipGetLastError();
 }
 
-size_t varint_encode_work_bytes(uint64_t rows, uint64_t len) {
-    const uint64_t chunks = (len + kEncChunk - 1) / kEncChunk;
-    return 2 * rows * (chunks ? chunks : 1) * 8 + 2 * rows * 8 + 1024 + 256;
-}
-
-hipError_t launch_varint_encode(const int64_t* vals, uint64_t rows, uint64_t len, uint64_t stride, uint8_t* dst,
-                                uint64_t dst_cap, void* work, uint64_t* row_bytes_host, hipStream_t s) {
-    const uint64_t chunks = (len + kEncChunk - 1) / kEncChunk;
-    if (rows == 0) return hipSuccess;
-    uint64_t* chunk_bytes = static_cast<uint64_t*>(work);
-    uint64_t* chunk_off = chunk_bytes + rows * (chunks ? chunks : 1);
-    uint64_t* row_base = chunk_off + rows * (chunks ? chunks : 1);
-    uint64_t* rbytes = row_base + rows;
-    uint32_t* too_big = reinterpret_cast<uint32_t*>(rbytes + rows);
-    hipError_t e;
-    if (chunks == 0) {
-        for (uint64_t r = 0; r < rows; ++r) row_bytes_host[r] = 0;
-        return hipSuccess;
-    }
-    hipLaunchKernelGGL(varint_size_kernel, dim3((unsigned)chunks, (unsigned)rows), dim3(kThreads), 0, s, vals, len,
-                       stride, (uint32_t)chunks, chunk_bytes);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    // per row: its chunks' offsets and its total; then the rows back to back -- all on the device, so the
-    // only host wait is the row sizes' copy at the end
-    hipLaunchKernelGGL(varint_offsets_kernel, dim3((unsigned)rows), dim3(kThreads), 0, s, chunk_bytes,
-                       (uint32_t)chunks, (const uint64_t*)nullptr, chunk_off, rbytes);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(varint_rows_kernel, dim3(1), dim3(kThreads), 0, s, (const uint64_t*)rbytes, rows, dst_cap,
-                       row_base, too_big);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    // nontemporal payload stores: encode -5.5 % in-process (3.770 -> 3.563 ms at 1000 x 1M, profiles/r06ad);
-    // SDA_ENC_NT=0 (read per call) keeps cached stores for A/B
-    const char* nt = getenv("SDA_ENC_NT");
-    if (!(nt && nt[0] == '0'))
-        hipLaunchKernelGGL(varint_write_kernel<true>, dim3((unsigned)chunks, (unsigned)rows), dim3(kThreads), 0, s,
-                           vals, len, stride, (uint32_t)chunks, (const uint64_t*)chunk_off,
-                           (const uint64_t*)row_base, (const uint32_t*)too_big, dst);
-    else
-        hipLaunchKernelGGL(varint_write_kernel<false>, dim3((unsigned)chunks, (unsigned)rows), dim3(kThreads), 0, s,
-                           vals, len, stride, (uint32_t)chunks, (const uint64_t*)chunk_off,
-                           (const uint64_t*)row_base, (const uint32_t*)too_big, dst);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(row_bytes_host, rbytes, rows * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-    uint64_t acc = 0;
-    for (uint64_t r = 0; r < rows; ++r) acc += row_bytes_host[r];
-    return acc > dst_cap ? hipErrorInvalidValue : hipSuccess;     // nothing was written (too_big)
-}
-
-// int32 rows: launch_varint_encode's work-buffer layout with chunks of kEnc32Chunk elements, its three scan
-// kernels, its one wait and its SDA_ENC_NT knob
-size_t varint_encode32_work_bytes(uint64_t rows, uint64_t len) {
-    const uint64_t chunks = (len + kEnc32Chunk - 1) / kEnc32Chunk;
-    return 2 * rows * (chunks ? chunks : 1) * 8 + 2 * rows * 8 + 1024 + 256;
-}
-
-hipError_t launch_varint_encode32(const int32_t* vals, uint64_t rows, uint64_t len, uint64_t stride, uint8_t* dst,
-                                  uint64_t dst_cap, void* work, uint64_t* row_bytes_host, hipStream_t s) {
-    const uint64_t chunks = (len + kEnc32Chunk - 1) / kEnc32Chunk;
-    if (rows == 0) return hipSuccess;
-    if (chunks == 0) {
-        for (uint64_t r = 0; r < rows; ++r) row_bytes_host[r] = 0;
-        return hipSuccess;
-    }
-    uint64_t* chunk_bytes = static_cast<uint64_t*>(work);
-    uint64_t* chunk_off = chunk_bytes + rows * chunks;
-    uint64_t* row_base = chunk_off + rows * chunks;
-    uint64_t* rbytes = row_base + rows;
-    uint32_t* too_big = reinterpret_cast<uint32_t*>(rbytes + rows);
-    const dim3 grid((unsigned)chunks, (unsigned)rows), block(kThreads);
-    hipError_t e;
-    hipLaunchKernelGGL(varint_size32_kernel, grid, block, 0, s, vals, len, stride, (uint32_t)chunks, chunk_bytes);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(varint_offsets_kernel, dim3((unsigned)rows), block, 0, s, (const uint64_t*)chunk_bytes,
-                       (uint32_t)chunks, (const uint64_t*)nullptr, chunk_off, rbytes);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(varint_rows_kernel, dim3(1), block, 0, s, (const uint64_t*)rbytes, rows, dst_cap, row_base,
-                       too_big);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const char* nt = getenv("SDA_ENC_NT");
-    if (!(nt && nt[0] == '0'))
-        hipLaunchKernelGGL(varint_write32_kernel<true>, grid, block, 0, s, vals, len, stride, (uint32_t)chunks,
-                           (const uint64_t*)chunk_off, (const uint64_t*)row_base, (const uint32_t*)too_big, dst);
-    else
-        hipLaunchKernelGGL(varint_write32_kernel<false>, grid, block, 0, s, vals, len, stride, (uint32_t)chunks,
-                           (const uint64_t*)chunk_off, (const uint64_t*)row_base, (const uint32_t*)too_big, dst);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(row_bytes_host, rbytes, rows * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-    uint64_t acc = 0;
-    for (uint64_t r = 0; r < rows; ++r) acc += row_bytes_host[r];
-    return acc > dst_cap ? hipErrorInvalidValue : hipSuccess;     // nothing was written (too_big)
-}
-
 }  // namespace sda
+

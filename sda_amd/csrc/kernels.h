@@ -180,7 +180,7 @@ hipError_t launch_packed_reveal_wide(const PackedRevealArgs& a, const uint64_t* 
                                      uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, int mode,
                                      DeviceTable& tab, hipStream_t s);
 
-// ---- codec.hip (share payload codec: sodium.rs:36-41 / :82-88, integer-encoding 1.0 VarInt) ----
+// ---- codec_decode.hip (share payload codec: sodium.rs:36-41 / :82-88, integer-encoding 1.0 VarInt) ----
 // Host-side plan of the decode: blobs are split into 4 KiB regions aligned to the (16-byte
 // aligned) byte buffer; a region shared by two blobs appears once per blob.
 struct VarintPlan {
@@ -256,6 +256,7 @@ hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64
                                               const VarintPlan& plan, void* work, void* slot_buf, int64_t* out,
                                               uint64_t out_cap, int64_t modulus, uint64_t* counts_host,
                                               uint32_t* flags_host, hipStream_t s, CodecLaunchInfo* info = nullptr);
+// ---- codec_encode.hip (the same codec's encoder: one size body and one write body over i64 or int32 rows) ----
 size_t varint_encode_work_bytes(uint64_t rows, uint64_t len);
 // encode rows [rows][stride] (first len elements) back to back into dst; row_bytes_host gets each
 // row's byte count (synchronous).  hipErrorInvalidValue if dst_cap is too small.

@@ -1,7 +1,7 @@
 """The share payload codec's dispatch, restated once for the tests (CPU only, numpy; no product import).
 
 Everything here is computed from a job's payload bytes and blob offsets alone -- the same inputs
-`decode_combine()` (sda_amd/csrc/engine_codec.cpp) and the launchers of sda_amd/csrc/codec.hip decide from:
+`decode_combine()` (sda_amd/csrc/engine_codec.cpp) and the launchers of sda_amd/csrc/codec_decode.hip decide from:
 
   regions        16 KiB regions aligned to the byte buffer (kRegionBytes; varint_plan);
   terminators    bytes without 0x80 inside a blob, and a blob's last byte when it continues (a truncated tail
@@ -19,12 +19,12 @@ Everything here is computed from a job's payload bytes and blob offsets alone --
 """
 import numpy as np
 
-REGION = 16384            # codec.hip: kRegionBytes
-SUB_REGION = 4096         # codec.hip: kSubBytes
-SLOT_CAP = 4096           # codec.hip: kSlotCap
+REGION = 16384            # codec_decode.hip: kRegionBytes
+SUB_REGION = 4096         # codec_decode.hip: kSubBytes
+SLOT_CAP = 4096           # codec_decode.hip: kSlotCap
 GRID_Y = 65535            # the y0 slices of every per-blob grid
-ENC_CHUNK = 2048          # codec.hip: kEncChunk
-THREADS = 256             # codec.hip: kThreads
+ENC_CHUNK = 2048          # codec_encode.hip: kEncChunk
+THREADS = 256             # codec_common.h: kThreads
 
 # sda_codec_last_launch (include/sda_engine.h)
 NONE, SLOTS, SLOTS_GROUPED, FUSED, FUSED_MULTI, MATRIX32, MATRIX64 = range(7)
@@ -130,7 +130,7 @@ def slices(n_blobs):
 
 
 def dec_kernel(out32, sparse, knobs):
-    """codec.hip dec_kernel<OutT, SPARSE>(): SDA_DEC_NT = 0 / 1 forces the store kind, else nontemporal for the slots"""
+    """codec_decode.hip dec_kernel<OutT, SPARSE>(): SDA_DEC_NT = 0 / 1 forces the store kind, else nontemporal for the slots"""
     e = knobs.get("SDA_DEC_NT")
     nt = (e[0] == "1") if e and e[0] in "01" else sparse
     return f"varint_decode_kernel<{'int' if out32 else 'long'}, {_b(sparse)}, {_b(nt)}>"

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-ENC32_CHUNK = 2048         # sda_amd/csrc/codec.hip: SDA_ENC32_CHUNK (kEnc32Chunk), elements per int32 encode block
+ENC32_CHUNK = 2048         # sda_amd/csrc/codec_encode.hip: SDA_ENC32_CHUNK (kEnc32Chunk), elements per int32 encode block
 C = ENC32_CHUNK
 
 INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1

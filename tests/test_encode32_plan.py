@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_chunk_constant_mirrors_the_source():
-    src = open(os.path.join(ROOT, "sda_amd", "csrc", "codec.hip")).read()
+    src = open(os.path.join(ROOT, "sda_amd", "csrc", "codec_encode.hip")).read()
     m = re.search(r"^#define SDA_ENC32_CHUNK (\d+)", src, flags=re.M)
     assert m and int(m[1]) == EC.ENC32_CHUNK
     assert "constexpr uint32_t kEnc32Chunk = SDA_ENC32_CHUNK;" in src

@@ -1,4 +1,4 @@
-"""GPU parity of the clerk's fused decode -> combine (codec.hip varint_decode_combine_kernel) against
+"""GPU parity of the clerk's fused decode -> combine (codec_decode.hip varint_decode_combine_kernel) against
 the oracle: clerk.rs:79-86 decodes every decrypted participation (sodium.rs:82-88, integer-encoding
 VarInt) and folds it into ShareCombiner::combine (combiner.rs:16-28), exact and order-dependent for
 signed shares.  Bit-exact.

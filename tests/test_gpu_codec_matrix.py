@@ -1,4 +1,4 @@
-"""GPU: the share payload codec's dispatch matrix (codec.hip) against the oracle, with the kernel that ran asserted.
+"""GPU: the share payload codec's dispatch matrix (codec_decode.hip, codec_encode.hip) against the oracle, with the kernel that ran asserted.
 
 Every case of tests/codec_matrix_cases.py runs bit-exactly against oracle.combine, oracle.varint_decode or
 oracle.varint_encode, writes into a poisoned buffer, and -- for sda_clerk_decode_combine_dev -- must report through

@@ -1,5 +1,5 @@
 // ubench_mall.hip -- can the clerk's decode -> combine keep its int32 slots in the 256 MiB Infinity Cache?
-// Memory-only model of codec.hip's slot path (1,000 payloads x 1M field shares: 4.94 GB of payload, 4 B of
+// Memory-only model of codec_decode.hip's slot path (1,000 payloads x 1M field shares: 4.94 GB of payload, 4 B of
 // slot per share): kernel A streams a payload slice in and writes the group's slots, kernel B reads the slots
 // back (and would combine them).  Variants:
 //   whole job   : A over all 1,000 blobs into a 4 GB slot buffer, then B over it (today's two passes)
