@@ -208,6 +208,17 @@ extern "C" {
                                  dst: *mut u8, dst_cap: u64, row_bytes: *mut u64, stream: *mut c_void) -> SdaStatus;
     pub fn sda_varint_encode32_dev(h: *mut SdaEngine, vals: *const i32, rows: u64, len: u64, stride: u64,
                                    dst: *mut u8, dst_cap: u64, row_bytes: *mut u64, stream: *mut c_void) -> SdaStatus;
+    // The clerk's whole arithmetic step (clerk.rs:63-107): decode, combine (continued from `state` when
+    // first_participation > 0) and the recipient's payload in one call; sda_clerk_job is the host-memory form
+    pub fn sda_clerk_job_dev(h: *mut SdaEngine, modulus: i64, bytes: *const u8, blob_off: *const u64, n_blobs: u64,
+                             first_participation: u64, prior_dim: u64, state: *mut i64, state_cap: u64,
+                             dim_out: *mut u64, payload: *mut u8, payload_cap: u64, payload_len: *mut u64,
+                             stream: *mut c_void) -> SdaStatus;
+    pub fn sda_clerk_job(h: *mut SdaEngine, s: *const SdaSharingScheme, blobs: *const *const u8,
+                         blob_lens: *const u64, n_blobs: u64, out: *mut i64, out_cap: u64, out_len: *mut u64,
+                         payload: *mut u8, payload_cap: u64, payload_len: *mut u64) -> SdaStatus;
+    pub fn sda_clerk_job_last_launch(h: *mut SdaEngine, continued: *mut u32, encode_route: *mut u32,
+                                     encode_chunks: *mut u64) -> SdaStatus;
 
     // ---- snapshot transposition (server/src/stores.rs:86-101) ----
     pub fn sda_snapshot_transpose_dev(h: *mut SdaEngine, src: *const u8, part_off: *const u64,

@@ -270,10 +270,12 @@ sda_status sda_packed_fixup_count(sda_engine* h, uint64_t* batches);
  * No pointer may be NULL. */
 sda_status sda_chacha_last_launch(sda_engine* h, uint32_t* path, uint64_t* grid_y, uint64_t* fixups);
 
-/* Diagnostic (read-only): how the handle's most recent sda_clerk_decode_combine_dev produced its result.  The
- * record is NONE from the call's entry until it returns SDA_OK, so a failed call leaves NONE; the host streaming
- * entry point (sda_clerk_decode_combine) keeps no record and leaves NONE as well, and so does a job whose
- * payloads decode to no element after its count pass (nothing is launched).
+/* Diagnostic (read-only): how the handle's most recent sda_clerk_decode_combine_dev or sda_clerk_job_dev produced
+ * its result.  The record is NONE from the call's entry until it returns SDA_OK, so a failed call leaves NONE; the
+ * host streaming entry points (sda_clerk_decode_combine, sda_clerk_job) keep no record and leave NONE as well, and
+ * so does a job whose payloads decode to no element after its count pass (nothing is launched), and a
+ * sda_clerk_job_dev call without blobs (the finish call).  One failing call writes it: a sda_clerk_job_dev whose
+ * payload_cap was too small has completed its decode -> combine, and the record describes that.
  *   path       0  NONE
  *              1  SLOTS          one decode into int32 slots per 16 KiB region + the combine over the slots
  *              2  SLOTS_GROUPED  the same, `passes` groups of blobs through one reused slot buffer (SDA_CODEC_GROUP)
@@ -297,7 +299,7 @@ sda_status sda_codec_last_launch(sda_engine* h, uint32_t* path, uint32_t* width,
 /* Diagnostic (read-only): which share-combine kernel the handle launched most recently and on what grid -- by any
  * entry point that ends in one: sda_combine_dev / sda_combine32_dev and their _accumulate forms, sda_combine_split_dev,
  * sda_combine_split_replay_dev, the host entry points' streamed tiles (the last tile's launch), the matrix paths of
- * the clerk's decode -> combine, the recipient pipeline.  A call that launches nothing (dim == 0, an accumulate,
+ * the clerk's decode -> combine (sda_clerk_decode_combine_dev, sda_clerk_job_dev), the recipient pipeline.  A call that launches nothing (dim == 0, an accumulate,
  * split or replay with n == 0) leaves the record, and so does a launch the runtime refuses (the call then returns
  * SDA_ERR_DEVICE).  The ChaCha stream path's internal combine is not recorded here (sda_chacha_last_launch describes
  * that launch).
@@ -591,6 +593,59 @@ sda_status sda_varint_encode_dev(sda_engine* h, const int64_t* vals, uint64_t ro
 sda_status sda_varint_encode32_dev(sda_engine* h, const int32_t* vals, uint64_t rows, uint64_t len,
                                    uint64_t stride, uint8_t* dst, uint64_t dst_cap,
                                    uint64_t* row_bytes, void* stream);
+
+/* The clerk's whole arithmetic step (process_clerking_job, client/src/clerk.rs:63-107, between opening the
+ * participations' sealed boxes and sealing the result): decode every blob, combine, and encode the combined
+ * shares as the recipient's payload -- one call, one wait, and continuable tile by tile so that a job's
+ * participations need not fit in HBM together.  bytes and blob_off are as for sda_clerk_decode_combine_dev.
+ *   Fresh call (first_participation == 0; prior_dim is ignored): state[0 .. dim) and *dim_out are what
+ *     sda_clerk_decode_combine_dev writes to out and *out_len, with its checks, their order and its statuses.
+ *   Continuing call (first_participation > 0): state holds the prior_dim values earlier calls left for
+ *     participations [0, first_participation).  Every blob of this call, its blob 0 included, must decode to
+ *     exactly prior_dim values, else SDA_ERR_WRONG_DIMENSION naming participation first_participation + i.  With
+ *     prior_dim > 0 a modulus of 0 or INT64_MIN fails first (row 0 was folded by an earlier call); prior_dim >
+ *     state_cap is SDA_ERR_INVALID_ARGUMENT.  combiner.rs:16-28's recurrence continues from state in place:
+ *     after any split of the blobs into calls, state is bit-identical to one sda_clerk_decode_combine_dev over
+ *     all of them (signed shares make the recurrence order-dependent).  *dim_out = prior_dim.
+ *   Continuing call with n_blobs == 0: state is left alone; with a payload this is the job's finish call, and
+ *     the retry after a payload buffer that was too small.
+ *   payload != NULL (device): state[0 .. dim) encoded as Encryptor::encrypt encodes it (sodium.rs:36-41), the
+ *     bytes sda_varint_encode_dev(state, 1, dim, dim, ...) writes; *payload_len = their count.  A payload_cap
+ *     below it returns SDA_ERR_INVALID_ARGUMENT with no payload byte written, *payload_len the count needed, and
+ *     state, *dim_out and sda_codec_last_launch's record those of the completed combine: finish with an
+ *     n_blobs == 0 call.  payload == NULL: no encode (an intermediate tile); payload_len may then be NULL.
+ *   Every other failing call leaves state and payload exactly as they were.
+ * The decode paths and their dispatch are sda_clerk_decode_combine_dev's, and sda_codec_last_launch and
+ * sda_combine_last_launch report these calls as they report that one (a continuing call's matrix paths combine
+ * with the accumulate variant), except that a continuing call under SDA_CODEC_PATH=fused takes the count pass and
+ * the matrix path (the fused kernel has no accumulating form).  On the slot path the payload is encoded behind the
+ * combine by kernels that read the dimension on the device, before the call's single wait.  Runs on ordinals[0] of
+ * a multi-device handle; stream ordering on the handle is that of every _dev call. */
+sda_status sda_clerk_job_dev(sda_engine* h, int64_t modulus, const uint8_t* bytes, const uint64_t* blob_off,
+                             uint64_t n_blobs, uint64_t first_participation, uint64_t prior_dim,
+                             int64_t* state, uint64_t state_cap, uint64_t* dim_out,
+                             uint8_t* payload, uint64_t payload_cap, uint64_t* payload_len, void* stream);
+/* The same job from host memory (the Rust clerk's call): the blobs stream as in sda_clerk_decode_combine, the
+ * accumulator is encoded on the device and the payload (about 4.9 bytes per field share instead of 8) is copied
+ * to payload (host).  out (host) may be NULL; else it gets the *out_len combined shares as
+ * sda_clerk_decode_combine writes them.  Errors are that call's; a payload_cap below the payload's size (or a
+ * NULL payload) returns SDA_ERR_INVALID_ARGUMENT with *payload_len the count needed. */
+sda_status sda_clerk_job(sda_engine* h, const sda_sharing_scheme* s, const uint8_t* const* blobs,
+                         const uint64_t* blob_lens, uint64_t n_blobs, int64_t* out, uint64_t out_cap,
+                         uint64_t* out_len, uint8_t* payload, uint64_t payload_cap, uint64_t* payload_len);
+/* Diagnostic (read-only): how the handle's most recent sda_clerk_job_dev / sda_clerk_job ran.  Written when such a
+ * call returns SDA_OK after launching something; a failed call and a call that launches nothing (no blobs and
+ * nothing to encode) leave it as it was.  Before any such call every field is 0.
+ *   continued      0  a fresh call; 1  a continuing one
+ *   encode_route   0  no payload was asked for
+ *                  1  the device-length encode, queued behind the combine before the call's single wait
+ *                  2  the host-length encode after the counts were read (the count-pass paths, the finish call,
+ *                     sda_clerk_job)
+ *   encode_chunks  the chunks of the encode's grid: route 1 sizes it by the host's bound on the dimension (blob
+ *                  0's bytes, or prior_dim), route 2 by the dimension; 0 when nothing was encoded
+ * A host-side record: nothing is waited for or copied.  No pointer may be NULL. */
+sda_status sda_clerk_job_last_launch(sda_engine* h, uint32_t* continued, uint32_t* encode_route,
+                                     uint64_t* encode_chunks);
 
 /* ---------------- snapshot transposition ----------------
  * Replaces AggregationsStore::iter_snapshot_clerk_jobs_data (server/src/stores.rs:86-101; the Mongo

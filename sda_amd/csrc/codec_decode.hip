@@ -452,11 +452,14 @@ __global__ __launch_bounds__(kThreads) void varint_cap_kernel(const uint64_t* __
     if (over) atomicOr(flag, 1u);
 }
 
-// blobs [b0, b1) against blob 0's count
+// blobs [b0, b1) against blob 0's count, or against *expect: the dimension earlier calls of a continued job
+// established (sda_clerk_job_dev), which blob 0 of this call has to meet as well
 __global__ __launch_bounds__(kThreads) void slot_dims_kernel(const uint64_t* __restrict__ blob_count, uint64_t b1,
-                                                             uint32_t* __restrict__ flags, uint64_t b0 = 0) {
+                                                             uint32_t* __restrict__ flags, uint64_t b0 = 0,
+                                                             const uint64_t* __restrict__ expect = nullptr) {
     bool bad = false;
-    for (uint64_t b = b0 + threadIdx.x; b < b1; b += kThreads) bad |= blob_count[b] != blob_count[0];
+    const uint64_t dim = expect ? *expect : blob_count[0];
+    for (uint64_t b = b0 + threadIdx.x; b < b1; b += kThreads) bad |= blob_count[b] != dim;
     if (bad) atomicOr(flags, 2u);
 }
 
@@ -1051,7 +1054,7 @@ struct SlotCombine {
     unsigned ntiles;
     const int32_t* slots;
     const uint64_t* tplan;
-    const uint64_t* blob_count;
+    const uint64_t* dim_p;       // the job's dimension: blob 0's count, or a continued job's established one
     const uint32_t* flags;
     uint64_t out_cap;
     Mod64 M;
@@ -1062,10 +1065,10 @@ template <int CPL>
 static hipError_t launch_slot_combine_cpl(const SlotCombine& c, uint64_t nb, int64_t* dst, const int64_t* acc_in) {
     if (c.small_m)
         hipLaunchKernelGGL((slot_combine_kernel<CPL, 8, true>), dim3(c.ntiles), dim3(kThreads), 0, c.s, c.slots,
-                           c.tplan, nb, c.blob_count, c.flags, c.out_cap, dst, c.M, acc_in);
+                           c.tplan, nb, c.dim_p, c.flags, c.out_cap, dst, c.M, acc_in);
     else
         hipLaunchKernelGGL((slot_combine_kernel<CPL, 8, false>), dim3(c.ntiles), dim3(kThreads), 0, c.s, c.slots,
-                           c.tplan, nb, c.blob_count, c.flags, c.out_cap, dst, c.M, acc_in);
+                           c.tplan, nb, c.dim_p, c.flags, c.out_cap, dst, c.M, acc_in);
     return hipGetLastError();
 }
 static hipError_t launch_slot_combine(const SlotCombine& c, uint32_t cpl, uint64_t nb, int64_t* dst,
@@ -1080,7 +1083,8 @@ static hipError_t launch_slot_combine(const SlotCombine& c, uint32_t cpl, uint64
 hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64_t* blob_off_host, uint64_t n_blobs,
                                               const VarintPlan& plan, void* work, void* slot_buf, int64_t* out,
                                               uint64_t out_cap, int64_t modulus, uint64_t* counts_host,
-                                              uint32_t* flags_host, hipStream_t s, CodecLaunchInfo* info) {
+                                              uint32_t* flags_host, hipStream_t s, CodecLaunchInfo* info,
+                                              SlotJob* job) {
     const size_t R = plan.regions;
     DecodeWork w = carve(work, R, n_blobs);
     const SlotGroups sg = slot_groups(plan, n_blobs);
@@ -1092,13 +1096,41 @@ hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64
     uint64_t* tplan = reinterpret_cast<uint64_t*>(static_cast<char*>(slot_buf) + slot_area_bytes(sg.regions));
     const uint32_t cpl = slot_cpl(), tile = cpl * kThreads;
     if (info) info->width = cpl;
-    // the grid's bound: blob 0 decodes to at most one element per byte
-    const uint64_t ntiles = (blob_off_host[1] - blob_off_host[0] + tile - 1) / tile;
+    // the grid's bound: blob 0 decodes to at most one element per byte; a continued job's dimension is known
+    const bool continued = job && job->continued;
+    const uint64_t bound = continued ? job->prior_dim : blob_off_host[1] - blob_off_host[0];
+    const uint64_t ntiles = (bound + tile - 1) / tile;
     if (ntiles > 0x7FFFFFFFull || R * kSlotCap >= (1ull << 39)) return hipErrorInvalidValue;
     hipError_t e;
     if ((e = upload_plan(w, blob_off_host, n_blobs, plan, false, true, s)) != hipSuccess) return e;
-    const SlotCombine comb = {(unsigned)ntiles, slots, tplan, w.blob_count, w.wide, out_cap,
+    // the job's words behind the flag word (its 256-byte block): [1] a continued job's dimension, [2] the payload's bytes
+    uint64_t* jobw = reinterpret_cast<uint64_t*>(w.wide);
+    if (job && (e = hipMemsetAsync(jobw + 2, 0, 8, s)) != hipSuccess) return e;
+    if (continued && (e = hipMemcpyAsync(jobw + 1, &job->prior_dim, 8, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+    const uint64_t* dim_p = continued ? jobw + 1 : w.blob_count;
+    const uint64_t* expect = continued ? jobw + 1 : nullptr;
+    const int64_t* state = continued ? out : nullptr;             // the recurrence continues in place
+    const SlotCombine comb = {(unsigned)ntiles, slots, tplan, dim_p, w.wide, out_cap,
                               make_mod64(modulus > 0 ? modulus : 1), modulus <= ((int64_t)1 << 62), s};
+    // the payload, queued blind behind the combine: the same dimension word and flag word gate it
+    auto encode_and_read = [&]() -> hipError_t {
+        if (!job) return read_back(w, n_blobs, counts_host, w.wide, 1, flags_host, s);
+        if (job->payload && ntiles && modulus > 0) {
+            if ((e = launch_varint_encode_devlen(out, out_cap, dim_p, w.wide, bound, job->payload, job->payload_cap,
+                                                 job->enc_work, jobw + 2, s, &job->enc_chunks)) != hipSuccess)
+                return e;
+            job->encoded = true;
+        }
+        // counts, flags and the payload's bytes in one copy: blob_count's block is followed by the flag block
+        const size_t words = (reinterpret_cast<const char*>(w.wide) - reinterpret_cast<const char*>(w.blob_count)) / 8;
+        std::vector<uint64_t> back(words + 3);
+        if ((e = hipMemcpyAsync(back.data(), w.blob_count, back.size() * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+        for (uint64_t b = 0; b < n_blobs; ++b) counts_host[b] = back[b];
+        *flags_host = (uint32_t)back[words];
+        job->payload_bytes = back[words + 2];
+        return hipSuccess;
+    };
     const bool combine = ntiles && modulus > 0;  // modulus 0: invalid -- no combine (an error if the dimension is > 0)
     const unsigned plan_gx = (unsigned)((plan.max_regions + kThreads - 1) / kThreads);   // slot_plan_kernel: one lane per region
     if (sg.G) {
@@ -1119,26 +1151,27 @@ hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64
             }
             if ((e = launch_scan(w, g0, ng, s)) != hipSuccess) return e;
             hipLaunchKernelGGL(slot_dims_kernel, dim3(1), dim3(kThreads), 0, s, (const uint64_t*)w.blob_count, g1,
-                               w.wide, g0);
+                               w.wide, g0, expect);
             if ((e = hipGetLastError()) != hipSuccess) return e;
             if (combine) {
                 hipLaunchKernelGGL(slot_plan_kernel, dim3(plan_gx, (unsigned)ng), dim3(kThreads), 0, s,
                                    w.blob_region, w.region_base, w.region_count, 0u, ng, ntiles, tile,
                                    (const uint32_t*)w.wide, tplan, g0, R0);
                 if ((e = hipGetLastError()) != hipSuccess) return e;
-                if ((e = launch_slot_combine(comb, cpl, ng, acc, g0 ? acc : nullptr)) != hipSuccess) return e;
+                if ((e = launch_slot_combine(comb, cpl, ng, acc, g0 ? acc : state)) != hipSuccess) return e;
             }
         }
         if (combine) {
             hipLaunchKernelGGL(slot_commit_kernel, dim3(2048), dim3(kThreads), 0, s, (const int64_t*)acc,
-                               (const uint64_t*)w.blob_count, (const uint32_t*)w.wide, out_cap, out);
+                               dim_p, (const uint32_t*)w.wide, out_cap, out);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
-        return read_back(w, n_blobs, counts_host, w.wide, 1, flags_host, s);
+        return encode_and_read();
     }
     if ((e = enqueue_decode<int32_t, true>(bytes, n_blobs, plan, w, slots, 0, w.wide, nullptr, s, info)) != hipSuccess) return e;
     if ((e = launch_scan(w, 0, n_blobs, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(slot_dims_kernel, dim3(1), dim3(kThreads), 0, s, (const uint64_t*)w.blob_count, n_blobs, w.wide);
+    hipLaunchKernelGGL(slot_dims_kernel, dim3(1), dim3(kThreads), 0, s, (const uint64_t*)w.blob_count, n_blobs, w.wide,
+                       (uint64_t)0, expect);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (combine) {
         e = each_blob_slice(n_blobs, nullptr, [&](uint32_t y0, unsigned ny) {
@@ -1146,9 +1179,9 @@ hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64
                                w.region_base, w.region_count, y0, n_blobs, ntiles, tile, (const uint32_t*)w.wide, tplan);
         });
         if (e != hipSuccess) return e;
-        if ((e = launch_slot_combine(comb, cpl, n_blobs, out, nullptr)) != hipSuccess) return e;
+        if ((e = launch_slot_combine(comb, cpl, n_blobs, out, state)) != hipSuccess) return e;
     }
-    return read_back(w, n_blobs, counts_host, w.wide, 1, flags_host, s);
+    return encode_and_read();
 }
 
 template <int DEPTH, bool MULTI>

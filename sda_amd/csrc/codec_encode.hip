@@ -9,6 +9,8 @@
 // One size body and one write body serve both element types; a traits struct per type (Enc64, Enc32) holds what
 // differs.  From int32 an element takes at most 5 bytes, so the zigzag, the size and the byte image stay in 32-bit
 // registers, an element touches at most two LDS dwords, and the chunk's LDS image is 5 bytes per element, not 10.
+// The same bodies also run with the row's length read from a device word (the job_encode_* kernels): the clerk job's
+// payload is queued behind a combine whose dimension the host has not seen yet (sda_clerk_job_dev).
 #include "codec_common.h"
 
 namespace sda {
@@ -271,9 +273,8 @@ __global__ __launch_bounds__(kThreads) void varint_write32_kernel(const int32_t*
 // exclusive scan of chunk_bytes per row (one block per row) + row base; row_bytes = total
 // One workgroup: rows placed back to back -- row_base = exclusive scan of row_bytes; *too_big = the total
 // exceeds cap (the write pass then writes nothing and the host reports it).
-__global__ __launch_bounds__(kThreads) void varint_rows_kernel(const uint64_t* __restrict__ row_bytes, uint64_t rows,
-                                                               uint64_t cap, uint64_t* __restrict__ row_base,
-                                                               uint32_t* __restrict__ too_big) {
+__device__ __forceinline__ void varint_rows_body(const uint64_t* __restrict__ row_bytes, uint64_t rows, uint64_t cap,
+                                                 uint64_t* __restrict__ row_base, uint32_t* __restrict__ too_big) {
     __shared__ uint64_t part[kThreads];
     uint64_t carry = 0;
     for (uint64_t base = 0; base < rows; base += kThreads) {
@@ -294,10 +295,15 @@ __global__ __launch_bounds__(kThreads) void varint_rows_kernel(const uint64_t* _
     if (threadIdx.x == 0) *too_big = carry > cap ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(kThreads) void varint_offsets_kernel(const uint64_t* __restrict__ chunk_bytes,
-                                                                  uint32_t chunks, const uint64_t* __restrict__ row_base,
-                                                                  uint64_t* __restrict__ chunk_off,
-                                                                  uint64_t* __restrict__ row_bytes) {
+__global__ __launch_bounds__(kThreads) void varint_rows_kernel(const uint64_t* __restrict__ row_bytes, uint64_t rows,
+                                                               uint64_t cap, uint64_t* __restrict__ row_base,
+                                                               uint32_t* __restrict__ too_big) {
+    varint_rows_body(row_bytes, rows, cap, row_base, too_big);
+}
+
+__device__ __forceinline__ void varint_offsets_body(const uint64_t* __restrict__ chunk_bytes, uint32_t chunks,
+                                                    const uint64_t* __restrict__ row_base,
+                                                    uint64_t* __restrict__ chunk_off, uint64_t* __restrict__ row_bytes) {
     const uint32_t row = blockIdx.x;
     __shared__ uint64_t part[kThreads];
     uint64_t carry = row_base ? row_base[row] : 0, total = 0;
@@ -318,6 +324,63 @@ __global__ __launch_bounds__(kThreads) void varint_offsets_kernel(const uint64_t
         __syncthreads();
     }
     if (threadIdx.x == 0 && row_bytes) row_bytes[row] = total;
+}
+__global__ __launch_bounds__(kThreads) void varint_offsets_kernel(const uint64_t* __restrict__ chunk_bytes,
+                                                                  uint32_t chunks, const uint64_t* __restrict__ row_base,
+                                                                  uint64_t* __restrict__ chunk_off,
+                                                                  uint64_t* __restrict__ row_bytes) {
+    varint_offsets_body(chunk_bytes, chunks, row_base, chunk_off, row_bytes);
+}
+
+// ---- the length on the device (sda_clerk_job_dev: the encode queued behind a combine whose dimension the host has
+// not seen).  The row's length is a device word, valid only while the job's flag word is clear and the length fits
+// the row's capacity; otherwise every pass exits without a store.  The grids and the workspace follow the host's
+// bound on the length: a chunk at or past the real length reports 0 bytes and its write pass stores nothing.
+struct DevLen {
+    const uint64_t* len;       // the row's element count
+    const uint32_t* flags;     // the job's flag word: nonzero = no result
+    uint64_t cap;              // elements the row can hold
+    __device__ __forceinline__ bool get(uint64_t* n) const {
+        if (*flags) return false;
+        *n = *len;
+        return *n <= cap;
+    }
+};
+__global__ __launch_bounds__(kThreads) void job_encode_size_kernel(const int64_t* __restrict__ vals, DevLen dl,
+                                                                      uint32_t chunks,
+                                                                      uint64_t* __restrict__ chunk_bytes) {
+    uint64_t len;
+    if (!dl.get(&len)) return;
+    varint_size_body<Enc64>(vals, len, len, chunks, chunk_bytes);
+}
+__global__ __launch_bounds__(kThreads) void job_encode_offsets_kernel(const uint64_t* __restrict__ chunk_bytes,
+                                                                         DevLen dl, uint32_t chunks,
+                                                                         uint64_t* __restrict__ chunk_off,
+                                                                         uint64_t* __restrict__ row_bytes) {
+    uint64_t len;
+    if (!dl.get(&len)) return;
+    varint_offsets_body(chunk_bytes, chunks, nullptr, chunk_off, row_bytes);
+}
+// *total = the payload's bytes, next to the job's flag word for the call's one copy
+__global__ __launch_bounds__(kThreads) void job_encode_rows_kernel(const uint64_t* __restrict__ row_bytes, DevLen dl,
+                                                                      uint64_t cap, uint64_t* __restrict__ row_base,
+                                                                      uint32_t* __restrict__ too_big,
+                                                                      uint64_t* __restrict__ total) {
+    uint64_t len;
+    if (!dl.get(&len)) return;
+    varint_rows_body(row_bytes, 1, cap, row_base, too_big);
+    if (threadIdx.x == 0) *total = row_bytes[0];
+}
+template <bool NT>
+__global__ __launch_bounds__(kThreads) void job_encode_write_kernel(const int64_t* __restrict__ vals, DevLen dl,
+                                                                       uint32_t chunks,
+                                                                       const uint64_t* __restrict__ chunk_off,
+                                                                       const uint64_t* __restrict__ row_base,
+                                                                       const uint32_t* __restrict__ too_big,
+                                                                       uint8_t* __restrict__ dst) {
+    uint64_t len;
+    if (!dl.get(&len) || (uint64_t)blockIdx.x * Enc64::kChunk >= len) return;
+    varint_write_body<Enc64, NT>(vals, len, len, chunks, chunk_off, row_base, too_big, dst);
 }
 
 }  // namespace
@@ -393,5 +456,36 @@ hipError_t launch_varint_encode32(const int32_t* vals, uint64_t rows, uint64_t l
     return launch_encode<Enc32>(varint_size32_kernel, varint_write32_kernel<true>, varint_write32_kernel<false>, vals,
                                 rows, len, stride, dst, dst_cap, work, row_bytes_host, s);
 }
+
+// One i64 row whose length is the device word *len_dev (sda_clerk_job_dev): size -> offsets -> rows -> write, only
+// queued.  bound >= the length the word can hold when the job is clean (the grids and `work`,
+// varint_encode_work_bytes(1, bound) bytes); *total_dev gets the payload's bytes unless the job's flag word is set
+// or the length exceeds vals_cap, and nothing is written to dst when they exceed dst_cap.
+hipError_t launch_varint_encode_devlen(const int64_t* vals, uint64_t vals_cap, const uint64_t* len_dev,
+                                       const uint32_t* flags_dev, uint64_t bound, uint8_t* dst, uint64_t dst_cap,
+                                       void* work, uint64_t* total_dev, hipStream_t s, uint64_t* chunks_out) {
+    const uint64_t chunks = (bound + kEncChunk - 1) / kEncChunk;
+    if (chunks_out) *chunks_out = chunks;
+    if (chunks == 0) return hipSuccess;
+    if (chunks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const EncodeWork w = carve_encode(work, 1, chunks);
+    const DevLen dl = {len_dev, flags_dev, vals_cap};
+    const dim3 grid((unsigned)chunks), block(kThreads);
+    hipError_t e;
+    hipLaunchKernelGGL(job_encode_size_kernel, grid, block, 0, s, vals, dl, (uint32_t)chunks, w.chunk_bytes);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(job_encode_offsets_kernel, dim3(1), block, 0, s, (const uint64_t*)w.chunk_bytes, dl,
+                       (uint32_t)chunks, w.chunk_off, w.row_bytes);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(job_encode_rows_kernel, dim3(1), block, 0, s, (const uint64_t*)w.row_bytes, dl, dst_cap,
+                       w.row_base, w.too_big, total_dev);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const char* nt = getenv("SDA_ENC_NT");                          // as launch_encode
+    hipLaunchKernelGGL(nt && nt[0] == '0' ? job_encode_write_kernel<false> : job_encode_write_kernel<true>, grid,
+                       block, 0, s, vals, dl, (uint32_t)chunks, (const uint64_t*)w.chunk_off,
+                       (const uint64_t*)w.row_base, (const uint32_t*)w.too_big, dst);
+    return hipGetLastError();
+}
+uint64_t varint_encode_chunks(uint64_t len) { return (len + kEncChunk - 1) / kEncChunk; }
 
 }  // namespace sda

@@ -330,6 +330,7 @@ void sda_engine_destroy(sda_engine* h) {
     dev_free(h->keyed_draws);
     dev_free(h->codec_work);
     dev_free(h->codec_mat);
+    dev_free(h->job_work);
     dev_free(h->pipe);
     dev_free(h->snap);
     dev_free(h->stage);
@@ -753,6 +754,17 @@ sda_status sda_codec_last_launch(sda_engine* h, uint32_t* path, uint32_t* width,
     *width = h->codec_last.width;
     *fell_back = h->codec_last.fell_back;
     *passes = h->codec_last.passes;
+    return ok();
+}
+
+sda_status sda_clerk_job_last_launch(sda_engine* h, uint32_t* continued, uint32_t* encode_route,
+                                     uint64_t* encode_chunks) {
+    SDA_ENTRY;
+    if (!h || !continued || !encode_route || !encode_chunks) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    // a host-side record, final when the call that made it returned: nothing to wait for
+    *continued = h->clerk_job_last.continued;
+    *encode_route = h->clerk_job_last.encode_route;
+    *encode_chunks = h->clerk_job_last.encode_chunks;
     return ok();
 }
 

@@ -56,28 +56,92 @@ sda_status codec_count(sda_engine* h, const uint8_t* bytes, const uint64_t* blob
     return SDA_OK;
 }
 
-// decode + combiner.rs:16-28 over device-resident blobs; out (device) gets out_len = count of blob 0
+// What sda_clerk_job_dev adds to the decode -> combine (job == nullptr: sda_clerk_decode_combine_dev exactly).
+struct ClerkJob {
+    uint64_t first;            // participations folded by earlier calls; > 0: a continuing call
+    uint64_t prior_dim;        // the dimension they established (continuing calls)
+    uint8_t* payload;          // device; nullptr: no encode
+    uint64_t payload_cap;
+    uint64_t* payload_len;     // host; non-NULL when payload is
+};
+
+// decode + combiner.rs:16-28 over device-resident blobs; out (device) gets out_len = count of blob 0.  With a job:
+// out is the job's state, continued in place from prior_dim columns when job->first > 0, and the result is encoded
+// into job->payload -- behind the combine, before the call's one wait, on the slot path (route 1), else once the
+// counts are known (route 2).
 sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const uint64_t* blob_off, uint64_t n_blobs,
-                          int64_t* out, uint64_t out_cap, uint64_t* out_len, hipStream_t st) {
-    *out_len = 0;
+                          int64_t* out, uint64_t out_cap, uint64_t* out_len, hipStream_t st,
+                          const ClerkJob* job = nullptr) {
+    const bool cont = job && job->first > 0;
+    const uint64_t prior = cont ? job->prior_dim : 0, first = cont ? job->first : 0;
+    *out_len = prior;
+    if (job && job->payload_len) *job->payload_len = 0;
     // sda_codec_last_launch: NONE until this call returns SDA_OK; `info` collects each decision where it is taken
     h->codec_last = sda::CodecLaunchInfo();
     sda::CodecLaunchInfo info;
-    if (n_blobs == 0) return ok();                                  // combiner.rs:17: empty input
+    // sda_clerk_job_last_launch: written by conclude() when the call ends well after launching something
+    sda_engine::ClerkJobLaunchInfo rec;
+    rec.continued = cont;
+    // the result on the host-length encoder, or the record alone when no payload is asked for
+    auto conclude = [&](uint64_t dim, bool launched) -> sda_status {
+        if (!job) return SDA_OK;
+        if (job->payload && dim) {
+            uint64_t nbytes = 0;
+            const sda_status e = encode_rows(h, (const int64_t*)out, 1, dim, dim, job->payload, job->payload_cap, &nbytes,
+                                             st, "payload_cap");
+            *job->payload_len = nbytes;                             // the count needed when payload_cap is too small
+            if (e) return e;
+            rec.encode_route = 2;
+            rec.encode_chunks = sda::varint_encode_chunks(dim);
+            launched = true;
+        } else if (job->payload) {
+            rec.encode_route = 2;
+        }
+        if (launched) h->clerk_job_last = rec;
+        return SDA_OK;
+    };
+    if (cont) {
+        if (prior > out_cap) return fail(SDA_ERR_INVALID_ARGUMENT, "prior_dim %llu > state_cap %llu",
+                                         (unsigned long long)prior, (unsigned long long)out_cap);
+        int64_t mm;                                                 // row 0 was folded by an earlier call
+        if (prior)
+            if (sda_status e = modulus_abs(m, &mm)) return e;
+    }
+    if (n_blobs == 0) {                                             // combiner.rs:17: empty input; the finish call
+        if (sda_status e = conclude(prior, false)) return e;
+        return ok();
+    }
     // SDA_CODEC_PATH=fused (A/B and test knob) runs the column-tile decode+combine, which reads the payload
     // once instead of writing and re-reading an int32 matrix but measured slower (VALU-bound: 3.4 ms per
     // 1000 x 1M launch vs 2.2 + 0.7 ms, profiles/r02d/ab_codec_fused.txt); the default is the matrix path.
+    // The fused kernel has no accumulating form: a continuing call asked for it takes the matrix path.
     const char* path = getenv("SDA_CODEC_PATH");
-    const bool force_fused = path && strcmp(path, "fused") == 0, force_matrix = !force_fused;
+    const bool want_fused = path && strcmp(path, "fused") == 0;
+    const bool force_fused = want_fused && !cont, force_matrix = !force_fused;
     const char* env = getenv("SDA_CODEC_NARROW");                    // "0": A/B and test knob
     const bool narrow_ok = !(env && atoi(env) == 0);
     sda::VarintPlan plan;
     std::vector<uint64_t> counts(n_blobs);
+    // the reference's checks once the counts are known: `% 0` on row 0 before a later row's "Wrong dimension";
+    // a continuing call's blob 0 is an ordinary row of the established dimension
+    auto check = [&](uint64_t dim, int64_t* mm) -> sda_status {
+        if (!cont && dim && m == 0) return modulus_abs(m, mm);      // blob 0 is folded first (combiner.rs:20-25)
+        for (uint64_t i = cont ? 0 : 1; i < n_blobs; ++i)
+            if (counts[i] != dim)
+                return fail(SDA_ERR_WRONG_DIMENSION,
+                            "Wrong dimension (participation %llu decodes to %llu shares, expected %llu)",
+                            (unsigned long long)(first + i), (unsigned long long)counts[i], (unsigned long long)dim);
+        if (dim) {
+            if (sda_status e = modulus_abs(m, mm)) return e;
+        }
+        if (out_cap < dim) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+        return SDA_OK;
+    };
     // Default: decode once into int32 slots per 16 KiB region (no count pass), then the exact combine
     // over the slots.  SDA_CODEC_PATH=matrix (A/B and test knob) takes the count pass + dense int32
     // matrix path; any element longer than 5 bytes or outside int32 (malformed or raw i64 payloads)
     // falls back to it as well.
-    if (narrow_ok && !force_fused && !(path && strcmp(path, "matrix") == 0)) {
+    if (narrow_ok && !want_fused && !(path && strcmp(path, "matrix") == 0)) {
         if (((uintptr_t)bytes & 15) != 0) return fail(SDA_ERR_INVALID_ARGUMENT, "byte buffer must be 16-byte aligned");
         for (uint64_t b = 0; b < n_blobs; ++b)
             if (blob_off[b + 1] < blob_off[b]) return fail(SDA_ERR_INVALID_ARGUMENT, "blob offsets must be non-decreasing");
@@ -86,31 +150,45 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
                                   sda::varint_decode_work_bytes(plan.regions, n_blobs)))
             return e;
         // the slots are sized by the bytes, the tile plan by the dimension (<= the bytes of blob 0)
-        const uint64_t dim_max = blob_off[1] - blob_off[0];
+        const uint64_t dim_max = cont ? prior : blob_off[1] - blob_off[0];
         if (sda_status e = ensure(&h->codec_mat, &h->codec_mat_bytes, sda::varint_slot_bytes(plan, n_blobs, dim_max)))
             return e;
+        sda::SlotJob sj;
+        if (job) {
+            sj.continued = cont;
+            sj.prior_dim = prior;
+            if (job->payload) {                // its own workspace: codec_work holds the counts until the wait
+                if (sda_status e = ensure(&h->job_work, &h->job_work_bytes, sda::varint_encode_work_bytes(1, dim_max)))
+                    return e;
+                sj.payload = job->payload;
+                sj.payload_cap = job->payload_cap;
+                sj.enc_work = h->job_work;
+            }
+        }
         // everything is queued before the host sees a count: the combine itself exits when a flag is set
         // or blob 0's count exceeds out_cap, and the checks below then report it in the reference's order
         const bool m_ok = m != 0 && m != INT64_MIN;
         uint32_t flags = 0;
         HIP_TRY(sda::launch_varint_decode_slots_combine(bytes, blob_off, n_blobs, plan, h->codec_work, h->codec_mat,
                                                         out, out_cap, m_ok ? (m < 0 ? -m : m) : 0, counts.data(),
-                                                        &flags, st, &info));
+                                                        &flags, st, &info, job ? &sj : nullptr));
         if (!(flags & 1u)) {
-            const uint64_t dim = counts[0];
+            const uint64_t dim = cont ? prior : counts[0];
             int64_t mm = 1;
-            if (dim && m == 0) return modulus_abs(m, &mm);     // blob 0 is folded first (combiner.rs:20-25)
-            for (uint64_t i = 1; i < n_blobs; ++i)
-                if (counts[i] != dim)
-                    return fail(SDA_ERR_WRONG_DIMENSION,
-                                "Wrong dimension (participation %llu decodes to %llu shares, expected %llu)",
-                                (unsigned long long)i, (unsigned long long)counts[i], (unsigned long long)dim);
-            if (dim) {
-                if (sda_status e = modulus_abs(m, &mm)) return e;
-            }
-            if (out_cap < dim) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+            if (sda_status e = check(dim, &mm)) return e;
             *out_len = dim;
             h->codec_last = info;
+            if (!job) return SDA_OK;
+            if (job->payload && dim && !sj.encoded) return conclude(dim, true);      // not reached: dim > 0 queues it
+            if (job->payload) {
+                rec.encode_route = 1;
+                rec.encode_chunks = sj.enc_chunks;
+                *job->payload_len = dim ? sj.payload_bytes : 0;
+                if (dim && sj.payload_bytes > job->payload_cap)
+                    return fail(SDA_ERR_INVALID_ARGUMENT, "payload_cap too small (%llu bytes needed)",
+                                (unsigned long long)sj.payload_bytes);
+            }
+            h->clerk_job_last = rec;
             return SDA_OK;
         }
         info = sda::CodecLaunchInfo();                 // the slot attempt wrote nothing: the count pass takes over
@@ -120,19 +198,14 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
     if (sda_status e = codec_count(h, bytes, blob_off, n_blobs, &plan, counts.data(), &irregular, st, !force_matrix,
                                    &long_elems))
         return e;
-    const uint64_t dim = counts[0];
+    const uint64_t dim = cont ? prior : counts[0];
     int64_t mm;
-    if (dim && m == 0) return modulus_abs(m, &mm);             // blob 0 is folded first (combiner.rs:20-25)
-    for (uint64_t i = 1; i < n_blobs; ++i)
-        if (counts[i] != dim)
-            return fail(SDA_ERR_WRONG_DIMENSION, "Wrong dimension (participation %llu decodes to %llu shares, expected %llu)",
-                        (unsigned long long)i, (unsigned long long)counts[i], (unsigned long long)dim);
-    if (dim) {
-        if (sda_status e = modulus_abs(m, &mm)) return e;
-    }
-    if (out_cap < dim) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    if (sda_status e = check(dim, &mm)) return e;
     *out_len = dim;
-    if (dim == 0) return ok();
+    if (dim == 0) {
+        if (sda_status e = conclude(0, true)) return e;
+        return ok();
+    }
     if (force_fused && irregular) info.fell_back |= sda::kCodecFusedIrregular;
     if (!irregular && force_fused) {
         // one pass over the payload: no [N][dim] matrix (the matrix buffer holds the tile plan)
@@ -142,7 +215,7 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
                                                   static_cast<uint64_t*>(h->codec_mat), dim, out, mm, long_elems, st,
                                                   &info));
         h->codec_last = info;
-        return SDA_OK;
+        return conclude(dim, true);
     }
     if (sda_status e = ensure(&h->codec_mat, &h->codec_mat_bytes, n_blobs * dim * 8)) return e;
     // Decoded field shares fit in int32 (|share| < m <= 2^31 for every field the reference uses): the
@@ -154,19 +227,19 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
         HIP_TRY(sda::launch_varint_decode_narrow(bytes, n_blobs, plan, h->codec_work, mat32, dim, &wide, st,
                                                  &info));
         if (!wide) {
-            HIP_TRY(sda::launch_combine_exact32(mat32, n_blobs, dim, dim, out, mm, st, false, &h->combine_last));
+            HIP_TRY(sda::launch_combine_exact32(mat32, n_blobs, dim, dim, out, mm, st, cont, &h->combine_last));
             info.path = sda::kCodecMatrix32;
             h->codec_last = info;
-            return SDA_OK;
+            return conclude(dim, true);
         }
         info.fell_back |= sda::kCodecNarrowWide;
     }
     int64_t* mat = static_cast<int64_t*>(h->codec_mat);
     HIP_TRY(sda::launch_varint_decode(bytes, n_blobs, plan, h->codec_work, mat, dim, dim, irregular, st, &info));
-    HIP_TRY(sda::launch_combine_exact(mat, n_blobs, dim, dim, out, mm, st, false, &h->combine_last));
+    HIP_TRY(sda::launch_combine_exact(mat, n_blobs, dim, dim, out, mm, st, cont, &h->combine_last));
     info.path = sda::kCodecMatrix64;
     h->codec_last = info;
-    return SDA_OK;
+    return conclude(dim, true);
 }
 
 // concatenate host blobs into a 16-byte aligned, padded device buffer
@@ -289,6 +362,58 @@ sda_status sda_clerk_decode_combine_dev(sda_engine* h, int64_t modulus, const ui
     if (sda_status e = decode_combine(h, modulus, bytes, blob_off, n_blobs, out, out_cap, out_len, pick(h, stream)))
         return e;
     return ok();
+}
+
+// The clerk's arithmetic step (clerk.rs:63-107 between the sealed boxes): decode, combine -- continued from `state`
+// when first_participation > 0 -- and the recipient's payload, one call with one wait.
+sda_status sda_clerk_job_dev(sda_engine* h, int64_t modulus, const uint8_t* bytes, const uint64_t* blob_off,
+                             uint64_t n_blobs, uint64_t first_participation, uint64_t prior_dim, int64_t* state,
+                             uint64_t state_cap, uint64_t* dim_out, uint8_t* payload, uint64_t payload_cap,
+                             uint64_t* payload_len, void* stream) {
+    SDA_ENTRY;
+    if (!h || !dim_out || (payload && !payload_len) || (n_blobs && (!bytes || !blob_off)))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (first_participation && prior_dim && !state) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    const ClerkJob job = {first_participation, prior_dim, payload, payload_cap, payload_len};
+    if (sda_status e = decode_combine(h, modulus, bytes, blob_off, n_blobs, state, state_cap, dim_out,
+                                      pick(h, stream), &job))
+        return e;
+    return ok();
+}
+
+sda_status sda_clerk_job(sda_engine* h, const sda_sharing_scheme* s, const uint8_t* const* blobs,
+                         const uint64_t* blob_lens, uint64_t n_blobs, int64_t* out, uint64_t out_cap,
+                         uint64_t* out_len, uint8_t* payload, uint64_t payload_cap, uint64_t* payload_len) {
+    SDA_ENTRY;
+    if (!h || !s || !out_len || !payload_len || (n_blobs && (!blobs || !blob_lens)))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out_len = 0;
+    *payload_len = 0;
+    for (uint64_t i = 0; i < n_blobs; ++i)
+        if (blob_lens[i] && !blobs[i]) return fail(SDA_ERR_INVALID_ARGUMENT, "blob %llu is NULL", (unsigned long long)i);
+    HIP_TRY(hipSetDevice(h->device));
+    (void)pick(h, h->stream);
+    // the streamed decode -> combine of sda_clerk_decode_combine; its accumulator stays on the device
+    int64_t* acc = nullptr;
+    if (sda_status st = host_decode_combine(h, s->modulus, blobs, blob_lens, n_blobs, out, out_cap, out_len, &acc))
+        return st;
+    const uint64_t dim = *out_len;
+    if (dim == 0) return ok();
+    // the recipient's payload from the accumulator: about 4.9 bytes per field share cross PCIe instead of 8
+    DevArena a;
+    if (sda_status st = stage(h, rup(dim * 10 + 16), &a)) return st;
+    uint8_t* db = a.take<uint8_t>(dim * 10 + 16);
+    uint64_t nbytes = 0;
+    if (sda_status st = encode_rows(h, (const int64_t*)acc, 1, dim, dim, db, dim * 10 + 16, &nbytes, h->stream, "payload"))
+        return st;
+    *payload_len = nbytes;
+    if (!payload || nbytes > payload_cap)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "payload_cap too small (%llu bytes needed)", (unsigned long long)nbytes);
+    HIP_TRY(hipMemcpyAsync(payload, db, nbytes, hipMemcpyDeviceToHost, h->stream));
+    if (sda_status st = finish(h)) return st;
+    h->clerk_job_last = {0u, 2u, sda::varint_encode_chunks(dim)};
+    return SDA_OK;
 }
 
 sda_status sda_varint_encode_dev(sda_engine* h, const int64_t* vals, uint64_t rows, uint64_t len, uint64_t stride,

@@ -328,8 +328,10 @@ sda_status host_chacha_combine(sda_engine* h, int64_t m, uint64_t D, const std::
 // at the first participation whose length differs from participation 0's.  One device (ordinals[0] of a
 // multi-device handle): a participation's columns are not locatable in its bytes before it is decoded.
 sda_status host_decode_combine(sda_engine* h, int64_t m, const uint8_t* const* blobs, const uint64_t* lens, uint64_t n,
-                               int64_t* out, uint64_t out_cap, uint64_t* out_len) {
+                               int64_t* out, uint64_t out_cap, uint64_t* out_len, int64_t** acc_dev) {
     *out_len = 0;
+    if (acc_dev) *acc_dev = nullptr;
+    const bool to_host = out || !acc_dev;       // the accumulator alone is wanted: no copy, no capacity check
     h->codec_last = sda::CodecLaunchInfo();     // this path keeps no record: a stale one must not be read
     if (n == 0) return SDA_OK;                                        // combiner.rs:17: empty input
     const uint64_t stage = host_stage_bytes();
@@ -396,7 +398,7 @@ sda_status host_decode_combine(sda_engine* h, int64_t m, const uint8_t* const* b
             if (dim) {
                 if (sda_status e = modulus_abs(m, &mm)) return e;
             }
-            if (out_cap < dim) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+            if (to_host && out_cap < dim) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
             if (dim) {
                 if (sda_status e = ensure(&h->work, &h->work_bytes, dim * 8)) return e;
                 acc = static_cast<int64_t*>(h->work);
@@ -410,9 +412,10 @@ sda_status host_decode_combine(sda_engine* h, int64_t m, const uint8_t* const* b
             HIP_TRY(sda::launch_combine_exact(mat, g.nb, dim, stride, acc, mm, h->stream, gi > 0, &h->combine_last));
         if (gi == 0) stride = std::max<uint64_t>(dim, 1);            // later groups: rows of exactly dim values
     }
-    if (dim) HIP_TRY(hipMemcpyAsync(out, acc, dim * 8, hipMemcpyDeviceToHost, h->stream));
+    if (dim && to_host) HIP_TRY(hipMemcpyAsync(out, acc, dim * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     *out_len = dim;
+    if (acc_dev) *acc_dev = acc;
     return SDA_OK;
 }
 

@@ -52,6 +52,8 @@ struct sda_engine {
     size_t codec_work_bytes = 0;
     void* codec_mat = nullptr;    // decoded [N][len] matrix of the clerk decode+combine path
     size_t codec_mat_bytes = 0;
+    void* job_work = nullptr;     // sda_clerk_job_dev: the queued encode's workspace (codec_work still holds the decode's)
+    size_t job_work_bytes = 0;
     void* pipe = nullptr;         // recipient / participant pipeline scratch (mask, masked, compacted shares)
     size_t pipe_bytes = 0;
     sda::DeviceTable rev_tab;     // packed-Shamir Newton/Lagrange tables (per scheme + clerk set)
@@ -74,6 +76,11 @@ struct sda_engine {
     sda::CombineLaunchInfo combine_last;
     // sda_snapshot_last_launch: what the last successful, non-sizing sda_snapshot_transpose_dev planned and launched
     sda::SnapshotLaunchInfo snap_last;
+    // sda_clerk_job_last_launch: written when a clerk job call that launched something returns SDA_OK
+    struct ClerkJobLaunchInfo {
+        uint32_t continued = 0, encode_route = 0;
+        uint64_t encode_chunks = 0;
+    } clerk_job_last;
     // sda_recipient_last_launch / sda_participant_last_launch: the decisions the last role pipeline call on this
     // handle took (engine_pipelines.cpp), written when a call of dimension > 0 returns SDA_OK
     struct RecipientLaunchInfo {
@@ -233,8 +240,10 @@ void destroy_comms(sda_engine* h);
 sda_status chacha_combine_multi(sda_engine* h, int64_t m, uint64_t D, const std::vector<uint32_t>& seeds, uint32_t w,
                                 uint64_t n, int64_t* dst);
 sda_status host_stream_ensure(sda_engine* h, size_t tile_bytes, size_t acc_bytes);
+// out == nullptr (sda_clerk_job): no copy to the host and no capacity check; *acc_dev (optional) = the device
+// accumulator holding the *out_len results (handle scratch: valid until the handle's next call), nullptr for none
 sda_status host_decode_combine(sda_engine* h, int64_t m, const uint8_t* const* blobs, const uint64_t* lens, uint64_t n,
-                               int64_t* out, uint64_t out_cap, uint64_t* out_len);
+                               int64_t* out, uint64_t out_cap, uint64_t* out_len, int64_t** acc_dev = nullptr);
 // kd != nullptr (sda_share_generate_keyed): `draws` is NULL and every device makes its own slice of them
 struct KeyedDraws {
     const uint32_t* key;          // host, 8 words

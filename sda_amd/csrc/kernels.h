@@ -251,11 +251,30 @@ hipError_t launch_varint_decode_combine(const uint8_t* bytes, uint64_t n_blobs, 
 // (bit 0: an element longer than 5 bytes or not a field share: use the matrix path; bit 1: the blobs
 // decode to different lengths), or blob 0's count exceeds out_cap, or modulus (|m|) is 0: then out is
 // untouched.  counts_host[n_blobs] and *flags_host are read at the end of the call (its only wait).
+// *job (sda_clerk_job_dev; nullptr: the call above exactly): what a clerk job adds to the pass of launches.
+//   continued: `out` holds the state of earlier calls over prior_dim columns and the recurrence continues from it
+//     in place; every blob, blob 0 included, has to decode to prior_dim values (else flag bit 1, out untouched),
+//     and prior_dim replaces blob 0's bytes as the bound of the grids and of varint_slot_bytes' dim.
+//   payload != nullptr: the result is encoded behind the combine (launch_varint_encode_devlen: nothing is stored
+//     when a flag is set or the dimension exceeds out_cap); enc_work holds varint_encode_work_bytes(1, bound).
+//     Back on the host: encoded = the encode was queued (not for modulus 0 or a bound of 0), enc_chunks its
+//     grid, payload_bytes the payload's size (above payload_cap: nothing was written to payload).
+// Counts, flags and payload_bytes come back in the call's one copy.
+struct SlotJob {
+    bool continued = false;
+    uint64_t prior_dim = 0;
+    uint8_t* payload = nullptr;
+    uint64_t payload_cap = 0;
+    void* enc_work = nullptr;
+    bool encoded = false;
+    uint64_t enc_chunks = 0, payload_bytes = 0;
+};
 size_t varint_slot_bytes(const VarintPlan& plan, uint64_t n_blobs, uint64_t dim);
 hipError_t launch_varint_decode_slots_combine(const uint8_t* bytes, const uint64_t* blob_off_host, uint64_t n_blobs,
                                               const VarintPlan& plan, void* work, void* slot_buf, int64_t* out,
                                               uint64_t out_cap, int64_t modulus, uint64_t* counts_host,
-                                              uint32_t* flags_host, hipStream_t s, CodecLaunchInfo* info = nullptr);
+                                              uint32_t* flags_host, hipStream_t s, CodecLaunchInfo* info = nullptr,
+                                              SlotJob* job = nullptr);
 // ---- codec_encode.hip (the same codec's encoder: one size body and one write body over i64 or int32 rows) ----
 size_t varint_encode_work_bytes(uint64_t rows, uint64_t len);
 // encode rows [rows][stride] (first len elements) back to back into dst; row_bytes_host gets each
@@ -266,6 +285,15 @@ hipError_t launch_varint_encode(const int64_t* vals, uint64_t rows, uint64_t len
 size_t varint_encode32_work_bytes(uint64_t rows, uint64_t len);
 hipError_t launch_varint_encode32(const int32_t* vals, uint64_t rows, uint64_t len, uint64_t stride, uint8_t* dst,
                                   uint64_t dst_cap, void* work, uint64_t* row_bytes_host, hipStream_t s);
+// One i64 row whose length the host has not seen (sda_clerk_job_dev): the same four passes, only queued, reading
+// the length from *len_dev.  They store nothing when *flags_dev is nonzero or the length exceeds vals_cap; the
+// grids and `work` (varint_encode_work_bytes(1, bound) bytes, not the decode's workspace) follow `bound`, which
+// the length does not exceed in a clean job.  *total_dev (device) = the payload's bytes; above dst_cap, dst is
+// left alone.  *chunks_out (host, optional) = the grid's chunks.
+hipError_t launch_varint_encode_devlen(const int64_t* vals, uint64_t vals_cap, const uint64_t* len_dev,
+                                       const uint32_t* flags_dev, uint64_t bound, uint8_t* dst, uint64_t dst_cap,
+                                       void* work, uint64_t* total_dev, hipStream_t s, uint64_t* chunks_out = nullptr);
+uint64_t varint_encode_chunks(uint64_t len);       // chunks of the i64 encoder's grid for a row of len values
 
 // ---- chacha.hip ----
 // Combine of n_seeds ChaCha mask streams (chacha.rs:57-76), two implementations:

@@ -192,6 +192,11 @@ SIGNATURES = [
     ("sda_varint_decode_dev", _st, [_vp, _vp, _u64p, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
     ("sda_clerk_decode_combine_dev", _st, [_vp, C.c_int64, _vp, _u64p, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
     ("sda_varint_encode_dev", _st, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
+    ("sda_clerk_job_dev", _st, [_vp, C.c_int64, _vp, _u64p, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64,
+                                _u64p, _vp, C.c_uint64, _u64p, _vp]),
+    ("sda_clerk_job", _st, [_vp, C.POINTER(S.SharingSchemeC), C.POINTER(_u8p), _u64p, C.c_uint64, _i64p, C.c_uint64,
+                            _u64p, _u8p, C.c_uint64, _u64p]),
+    ("sda_clerk_job_last_launch", _st, [_vp, _u32p, _u32p, _u64p]),
     ("sda_varint_encode32_dev", _st, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
     ("sda_snapshot_transpose_dev", _st, [_vp, _vp, _u64p, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _u64p, _u64p,
                                          _u64p, _vp]),
@@ -236,6 +241,8 @@ def load_library(path: Optional[str] = None):
             raise RuntimeError(f"MI355X engine not built: {path} is missing (run `make` / __graft_entry__.build())")
         lib = C.CDLL(path)
         for name, res, args in SIGNATURES:
+            if path != LIB_PATH and not hasattr(lib, name):
+                continue                    # an older build in an A/B: it lacks the entry points added since
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -498,6 +505,28 @@ class Engine:
                                                  C.byref(olen)))
         return out[: olen.value]
 
+    def clerk_job(self, scheme, blobs: Sequence[bytes], want_out=True, payload_cap=None):
+        """clerk.rs:63-107 between the sealed boxes, from host memory: decode each participation, combine, and
+        encode the combined shares for the recipient.  Returns (out or None, payload bytes); payload_cap defaults
+        to 10 bytes per byte of the longest blob.  A too-small payload_cap raises SdaError with `.payload_len`."""
+        s = scheme.c()
+        bufs = [(C.c_uint8 * max(len(b), 1)).from_buffer_copy(b or b"\0") for b in blobs]
+        n = len(bufs)
+        ptrs = (_u8p * max(n, 1))(*[C.cast(b, _u8p) for b in bufs])
+        lens = (C.c_uint64 * max(n, 1))(*[len(b) for b in blobs])
+        cap = max([len(b) for b in blobs] + [1])
+        out = np.zeros(cap, np.int64) if want_out else None
+        pcap = 10 * cap if payload_cap is None else payload_cap
+        pay = np.zeros(max(pcap, 1), np.uint8)
+        olen, plen = C.c_uint64(0), C.c_uint64(0)
+        try:
+            _check(self.lib.sda_clerk_job(self.h, C.byref(s), ptrs, lens, n, _ptr(out) if want_out else None, cap,
+                                          C.byref(olen), _ptr(pay, _u8p), pcap, C.byref(plen)))
+        except SdaError as e:
+            e.payload_len = int(plen.value)
+            raise
+        return (out[: olen.value] if want_out else None), pay[: plen.value].tobytes()
+
     # ---------------- fused role pipelines ----------------
     def recipient_reveal(self, masking, mask_rows, sharing, dimension: int, indexed_shares, output_modulus: int,
                          mode=REVEAL_EXACT) -> np.ndarray:
@@ -589,6 +618,14 @@ class Engine:
         path, width, fb, passes = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
         _check(self.lib.sda_codec_last_launch(self.h, C.byref(path), C.byref(width), C.byref(fb), C.byref(passes)))
         return int(path.value), int(width.value), int(fb.value), int(passes.value)
+
+    def clerk_job_last_launch(self):
+        """(continued, encode_route, encode_chunks) of the handle's last clerk_job_dev / clerk_job that launched
+        something: encode_route 0 no payload, 1 the device-length encode queued before the call's wait, 2 the
+        host-length encode after the counts were read (sda_clerk_job_last_launch)."""
+        cont, route, chunks = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        _check(self.lib.sda_clerk_job_last_launch(self.h, C.byref(cont), C.byref(route), C.byref(chunks)))
+        return int(cont.value), int(route.value), int(chunks.value)
 
     def combine_last_launch(self):
         """CombineLaunch(kind, elem_bytes, vec, rows, variant, grid, wlo, nwide, per_cu) of the handle's last
@@ -749,6 +786,23 @@ class Engine:
         _check(self.lib.sda_clerk_decode_combine_dev(self.h, modulus, bytes_ptr, _ptr(off, _u64p), off.size - 1,
                                                      out_ptr, out_cap, C.byref(olen), stream))
         return olen.value
+
+    def clerk_job_dev(self, modulus, bytes_ptr, blob_off, state_ptr, state_cap, first_participation=0, prior_dim=0,
+                      payload_ptr=None, payload_cap=0, stream=None):
+        """The clerk's decode -> combine -> payload as one call, continued from the state of participations
+        [0, first_participation) over prior_dim columns when first_participation > 0; blob_off empty or [0] with a
+        payload is the finish call.  Returns (dim, payload_len); payload_ptr None: an intermediate tile, no encode.
+        A failing call raises SdaError carrying `.dim` and `.payload_len` as the call left them."""
+        off = _arr(blob_off if len(blob_off) else [0], np.uint64)
+        dim, plen = C.c_uint64(0), C.c_uint64(0)
+        try:
+            _check(self.lib.sda_clerk_job_dev(self.h, modulus, bytes_ptr, _ptr(off, _u64p), off.size - 1,
+                                              first_participation, prior_dim, state_ptr, state_cap, C.byref(dim),
+                                              payload_ptr, payload_cap, C.byref(plen), stream))
+        except SdaError as e:
+            e.dim, e.payload_len = int(dim.value), int(plen.value)
+            raise
+        return int(dim.value), int(plen.value)
 
     def varint_encode_dev(self, vals_ptr, rows, length, stride, dst_ptr, dst_cap, stream=None) -> np.ndarray:
         rb = np.zeros(max(rows, 1), np.uint64)
