@@ -6,9 +6,11 @@ rounds, each block one warm-up launch and 10 timed ones between HIP events on th
 placement, clocks and box state are shared by every leg.  The yardstick of an int32 leg is the i64 leg of the
 same round.
     python scripts/packed32_inproc.py [rounds] [out_file]
-Legs: share-gen {canonical, exact} x {i64, int32}; reveal {canonical, exact} x {i64, int32}.  With
-SDA_INPROC_QUAD=1, on a library built with EXTRA=-DSDA_GEN32_QUAD=1, a third share-gen leg runs the 16-byte quad
-store (SDA_GEN32_STORE=16) next to the shipped 8-byte pair store: the A/B of the two int32 store forms.
+Legs: share-gen {canonical, exact} x {i64, int32}; reveal {canonical, exact} x {i64, int32}.
+SDA_INPROC_ALT_LIB=<another build of libsda_engine.so> adds both share-gen legs from that library, loaded into the
+same process (the A/B of two builds, e.g. against the parent commit's), and prints per leg whether this build's
+median is within the other's median plus the other's own spread (max - min) in this run.  The two builds' legs trade
+places every other round: a leg's place in the round is worth up to 1 % (profiles/gen_launch/ab_parent.txt).
 Per leg: per-launch ms of every round, median, spread, algorithmic bytes, fraction of the 8 TB/s HBM peak, and for
 the int32 legs the ratio to the i64 median next to the byte ratio.  Checks the int32 outputs against the i64 ones
 (bit equality after widening).
@@ -57,12 +59,16 @@ rev = torch.empty((V, D), dtype=torch.int64, device="cuda")
 MODES = (("canonical", E.REVEAL_CANONICAL), ("exact", E.REVEAL_EXACT))
 
 
-def gen64(mode):
-    eng.packed_generate_mode_dev(sch, sec.data_ptr(), D, V, drw.data_ptr(), sh64.data_ptr(), mode, st)
+ALT = os.environ.get("SDA_INPROC_ALT_LIB")
+alt = Engine(0, lib_path=ALT) if ALT else None      # a second build of the library in this process
 
 
-def gen32(mode):
-    eng.packed_generate32_dev(sch, sec.data_ptr(), D, V, drw.data_ptr(), sh32.data_ptr(), mode, st)
+def gen64(mode, e=eng):
+    e.packed_generate_mode_dev(sch, sec.data_ptr(), D, V, drw.data_ptr(), sh64.data_ptr(), mode, st)
+
+
+def gen32(mode, e=eng):
+    e.packed_generate32_dev(sch, sec.data_ptr(), D, V, drw.data_ptr(), sh32.data_ptr(), mode, st)
 
 
 def rev64(mode):
@@ -76,26 +82,33 @@ def rev32(mode):
 gen_in = 8.0 * V * (D + B * t)
 bytes_of = {"gen64": gen_in + 8.0 * V * n * B, "gen32": gen_in + 4.0 * V * n * B,
             "rev64": 8.0 * V * (m * B + D), "rev32": 4.0 * V * m * B + 8.0 * V * D}
-# (name, launcher, byte key, twin, environment)
-QUAD = os.environ.get("SDA_INPROC_QUAD") == "1"
-LEGS = [("gen i64", gen64, "gen64", None, {}),
-        ("gen int32 8-byte store", gen32, "gen32", "gen i64", {})]
-if QUAD:
-    LEGS.append(("gen int32 16-byte store", gen32, "gen32", "gen i64", {"SDA_GEN32_STORE": "16"}))
-LEGS += [("reveal i64", rev64, "rev64", None, {}),
-         ("reveal int32", rev32, "rev32", "reveal i64", {})]
+# (name, launcher, byte key, twin)
+LEGS = [("gen i64", gen64, "gen64", None),
+        ("gen int32", gen32, "gen32", "gen i64")]
+if alt:
+    LEGS += [("gen i64 alt lib", lambda mode: gen64(mode, alt), "gen64", None),
+             ("gen int32 alt lib", lambda mode: gen32(mode, alt), "gen32", "gen i64 alt lib")]
+LEGS += [("reveal i64", rev64, "rev64", None),
+         ("reveal int32", rev32, "rev32", "reveal i64")]
+BY_NAME = {leg[0]: leg for leg in LEGS}
+
+
+def other_build(name):
+    """the same leg from the other library; the leg itself where there is none"""
+    o = name[:-len(" alt lib")] if name.endswith(" alt lib") else name + " alt lib"
+    return o if o in BY_NAME else name
+
 
 say(f"packed32_inproc: k={k} t={t} n={n} p={p}  V={V} D={D} B={B}  reveal from {m} clerks  rounds={rounds} "
-    f"(1 warm-up + 10 timed launches per block)")
+    f"(1 warm-up + 10 timed launches per block)"
+    + (f"  alt lib {os.path.basename(os.path.dirname(ALT))}/{os.path.basename(ALT)}" if alt else ""))
 for mname, mode in MODES:
-    # correctness first: the int32 outputs against the i64 ones, both store forms
+    # correctness first: the int32 outputs against the i64 ones (the other build's too, against this build's i64)
     gen64(mode)
     checks = []
-    for env in ({}, {"SDA_GEN32_STORE": "16"}):
-        os.environ.update(env)
+    for e in (alt, eng) if alt else (eng,):
         sh32.fill_(0x5A5A5A5A)
-        gen32(mode)
-        os.environ.pop("SDA_GEN32_STORE", None)
+        gen32(mode, e)
         torch.cuda.synchronize()
         checks.append(all(torch.equal(sh32[v0:v0 + 50].to(torch.int64), sh64[v0:v0 + 50]) for v0 in range(0, V, 50)))
     fix_gen = eng.packed_fixup_count()
@@ -110,14 +123,14 @@ for mname, mode in MODES:
     checks.append(torch.equal(rev, ref))
     checks.append(torch.equal(torch.remainder(rev, p), sec))
     del ref
-    say(f"[{mname}] int32 == i64: gen 8-byte store {checks[0]}, gen 16-byte store "
-        f"{checks[1] if QUAD else 'not built'}, reveal {checks[2]}, reveals the secrets {checks[3]}; "
-        f"fix-up batches gen32 {fix_gen} reveal32 {fix_rev}")
+    say(f"[{mname}] int32 == i64: gen {checks[-3]}, gen alt lib {checks[0] if alt else 'not given'}, "
+        f"reveal {checks[-2]}, reveals the secrets {checks[-1]}; fix-up batches gen32 {fix_gen} reveal32 {fix_rev}")
     assert all(checks)
     res = {leg[0]: [] for leg in LEGS}
     for r in range(rounds):
-        for name, fn, _, _, env in LEGS:
-            os.environ.update(env)
+        for leg in LEGS:
+            # the two builds' legs trade places every other round, so neither always follows the same leg
+            name, fn, _, _ = BY_NAME[other_build(leg[0])] if r % 2 else leg
             fn(mode)                                                                    # warm
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -125,10 +138,9 @@ for mname, mode in MODES:
                 fn(mode)
             e1.record()
             torch.cuda.synchronize()
-            os.environ.pop("SDA_GEN32_STORE", None)
             res[name].append(e0.elapsed_time(e1) / 10)
     med = {}
-    for name, _, key, twin, _ in LEGS:
+    for name, _, key, twin in LEGS:
         s = sorted(res[name])
         med[name] = s[len(s) // 2]
         nb = bytes_of[key]
@@ -140,7 +152,14 @@ for mname, mode in MODES:
                      f"{nb / bytes_of[key.replace('32', '64')]:.3f})")
         say(line)
         say(f"[{mname}] {name:<24} per-launch ms by round: " + " ".join(f"{x:.4f}" for x in res[name]))
+    for name in ("gen i64", "gen int32") if alt else ():
+        o = res[name + " alt lib"]
+        bound = med[name + " alt lib"] + max(o) - min(o)
+        say(f"[{mname}] {name:<24} median {med[name]:.4f} ms against the alt lib's {med[name + ' alt lib']:.4f} + "
+            f"spread {max(o) - min(o):.4f} = {bound:.4f}: {'PASS' if med[name] <= bound else 'FAIL'}")
 eng.close()
+if alt:
+    alt.close()
 if out_path:
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as f:

@@ -12,6 +12,9 @@ override), canonical and exact, i64 and int32 shares.  Per (mode, width):
 (a) and (b) are compared for equality (shares and fix-up count) before timing.  Reported: every median and spread,
 (b) / (a) against the gate 0.97 (the project's rule for keeping a tuning change: a gain larger than the box-to-box
 spread), and (b) / max((c), (d)) without a gate.  The exit status is 1 when a leg misses the gate.
+SDA_INPROC_ALT_LIB=<another build of libsda_engine.so> adds (b) and (c) from that library, loaded into the same process
+(the A/B of two builds, e.g. against the parent commit's), and prints per leg whether this build's median is within
+the other's median plus the other's own spread (max - min) in this run.
 """
 import os
 import sys
@@ -60,6 +63,8 @@ def report(tag, name, v, extra=""):
 
 torch.cuda.init()
 eng = Engine(0)
+ALT = os.environ.get("SDA_INPROC_ALT_LIB")
+alt = Engine(0, lib_path=ALT) if ALT else None      # a second build of the library in this process
 st = torch.cuda.current_stream().cuda_stream
 sch = S.CONFIG_PACKED
 p, k, t, n = sch.prime_modulus, sch.secret_count, sch.privacy_threshold(), sch.share_count
@@ -114,11 +119,20 @@ for wname, dtype, unkeyed, keyed in (("i64", torch.int64, eng.packed_generate_mo
         assert same and fix_a == fix_b and rec == (1, 0)
         legs = {"(a) draws_dev + unkeyed generate": staged, "(b) keyed generate": fused,
                 "(c) unkeyed generate, pre-made draws": gen_alone, "(d) draws_dev alone": draws_alone}
+        if alt:
+            a_unkeyed, a_keyed = getattr(alt, unkeyed.__name__), getattr(alt, keyed.__name__)
+            legs["(b) keyed generate, alt lib"] = lambda: a_keyed(sch, sec.data_ptr(), D, V, KEY, STREAM,
+                                                                  out.data_ptr(), mode, stream=st)
+            legs["(c) unkeyed generate, alt lib"] = lambda: a_unkeyed(sch, sec.data_ptr(), D, V, drw.data_ptr(),
+                                                                      out.data_ptr(), mode, st)
         res = {name: [] for name in legs}
+        # the two builds' legs trade places every other round, so neither always follows the same leg
+        twin = {name: next((o for o in legs if o != name and o[:3] == name[:3]), name) for name in legs}
         for r in range(rounds):
-            for name, fn in legs.items():
-                res[name].append(timed_dev(fn, REPS))
-        tm = {name[:3]: med(v) for name, v in res.items()}
+            for name in legs:
+                name = twin[name] if r % 2 else name
+                res[name].append(timed_dev(legs[name], REPS))
+        tm = {name[:3]: med(v) for name, v in res.items() if not name.endswith("alt lib")}
         width = out.element_size()
         model = {"(a)": 8.0 * V * (D + 2 * B * t) + width * V * n * B, "(b)": 8.0 * V * D + width * V * n * B,
                  "(c)": 8.0 * V * (D + B * t) + width * V * n * B, "(d)": 8.0 * nd}
@@ -132,9 +146,16 @@ for wname, dtype, unkeyed, keyed in (("i64", torch.int64, eng.packed_generate_mo
         say(f"[{tag}] (b)/(a) = {ratio:.3f} (gate {GATE}: {'PASS' if ok else 'FAIL'})  "
             f"(b)/max((c),(d)) = {tm['(b)'] / yard:.3f} ({'memory (c)' if tm['(c)'] > tm['(d)'] else 'VALU (d)'} "
             f"yardstick)  (c)+(d) = {tm['(c)'] + tm['(d)']:.4f} ms")
+        for name in [name for name in res if name.endswith("alt lib")]:
+            o = res[name]
+            bound = med(o) + max(o) - min(o)
+            say(f"[{tag}] {name[:3]} median {tm[name[:3]]:.4f} ms against the alt lib's {med(o):.4f} + spread "
+                f"{max(o) - min(o):.4f} = {bound:.4f}: {'PASS' if tm[name[:3]] <= bound else 'FAIL'}")
     del out
 say(f"gate (b) <= {GATE} (a) in all four legs: {'PASS' if all_ok else 'FAIL'}")
 eng.close()
+if alt:
+    alt.close()
 if out_path:
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as f:

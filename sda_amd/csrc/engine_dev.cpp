@@ -8,28 +8,22 @@ namespace sda_host __attribute__((visibility("hidden"))) {
 sda_status packed_generate(sda_engine* h, const sda_sharing_scheme* s, sda::PackedGenArgs ga, hipStream_t st) {
     const uint32_t k = (uint32_t)s->secret_count, t = (uint32_t)s->privacy_threshold, n = (uint32_t)s->share_count;
     if (sda_status e = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
-    if (ga.out32) {
-        if (const size_t tmp = sda::packed_gen32_scratch_bytes(ga, k, t, n, (uint32_t)s->modulus)) {
-            if (sda_status e = ensure(&h->gen32_tmp, &h->gen32_tmp_bytes, tmp + 64)) return e;
-            ga.scratch = static_cast<int64_t*>(h->gen32_tmp);
-            ga.flag = ga.scratch + tmp / sizeof(int64_t);      // launch_narrow32's overflow word: never set here
-        }
+    // the launcher plans the call with the same function: the scratch sized here is the scratch its kernels use
+    const sda::PackedGenPlan pl = sda::packed_gen_plan(ga, k, t, n, (uint32_t)s->modulus);
+    if (const size_t tmp = pl.narrow_bytes) {
+        if (sda_status e = ensure(&h->gen32_tmp, &h->gen32_tmp_bytes, tmp + 64)) return e;
+        ga.scratch = static_cast<int64_t*>(h->gen32_tmp);
+        ga.flag = ga.scratch + tmp / sizeof(int64_t);          // launch_narrow32's overflow word: never set here
     }
-    uint32_t keyed_path = 0;
-    size_t staged = 0;
-    if (ga.key) {             // keyed: draws made in the share kernels (path 1), or staged in handle-owned scratch (2)
-        keyed_path = sda::packed_gen_keyed_in_kernel(ga, k, t, n, (uint32_t)s->modulus) ? 1 : 2;
-        staged = sda::packed_gen_keyed_scratch_bytes(ga, k, t, n, (uint32_t)s->modulus);
-        if (staged) {
-            if (sda_status e = ensure(&h->keyed_draws, &h->keyed_draws_bytes, rup(staged + 8))) return e;
-            ga.draw_scratch = static_cast<int64_t*>(h->keyed_draws);
-        }
+    if (pl.draw_bytes) {      // keyed, staged in handle-owned scratch (path 2; path 1 makes them in the share kernels)
+        if (sda_status e = ensure(&h->keyed_draws, &h->keyed_draws_bytes, rup(pl.draw_bytes + 8))) return e;
+        ga.draw_scratch = static_cast<int64_t*>(h->keyed_draws);
     }
     HIP_TRY(sda::launch_packed_generate(ga, k, t, n, (uint32_t)s->modulus, (uint32_t)s->omega_secrets,
                                         (uint32_t)s->omega_shares, h->gen_tab, h->gen_log, st, &h->gen_log_used));
-    if (keyed_path && ga.dimension && ga.n_vectors) {           // sda_packed_keyed_last_launch
-        h->keyed_path = keyed_path;
-        h->keyed_staged_bytes = staged;
+    if (pl.keyed_path && ga.dimension && ga.n_vectors) {        // sda_packed_keyed_last_launch
+        h->keyed_path = pl.keyed_path;
+        h->keyed_staged_bytes = pl.draw_bytes;
     }
     return SDA_OK;
 }

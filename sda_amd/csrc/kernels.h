@@ -107,34 +107,39 @@ struct PackedGenArgs {
     const int64_t* secrets; uint64_t dimension; uint64_t n_vectors;
     const int64_t* draws; int64_t* out;
     bool canonical = false;       // shares as canonical residues in [0, p) instead of tss' signed values
-    uint32_t prime = 0;           // set by launch_packed_generate (selects the lazy-truncation kernel)
-    bool signbit = false;         // set by launch_packed_generate (sign-bit radix-2 half, packed_gen.hip)
-    bool xcd_order = true;        // set by launch_packed_generate: XCD-chunked tile order (xcd.h)
     // int32 shares (sda_packed_generate32_dev): out32 != nullptr replaces out, [n_vectors][n][B] int32.  Native
     // kernels up to n + 1 = 27 and on the workspace path; the n + 1 = 81 register kernels write i64 into
-    // `scratch` (packed_gen32_scratch_bytes() bytes) and launch_narrow32 narrows it (`flag`: its device word).
+    // `scratch` (PackedGenPlan::narrow_bytes bytes, 16-byte aligned) and launch_narrow32 narrows it (`flag`: its
+    // device word).
     int32_t* out32 = nullptr;
     int64_t* scratch = nullptr;
     int64_t* flag = nullptr;
-    const void* align_as = nullptr;   // set by launch_packed_generate: the buffer whose alignment picks the kernel
-    int store32 = 0;              // set by launch_packed_generate: 2 = the 16-byte quad store (A/B, SDA_GEN32_QUAD builds)
     // keyed (sda_packed_generate_keyed_dev): key != nullptr replaces `draws`.  Batch b of vector v takes draws
     // (first_batch + v B + b) t + j, j < t, of launch_draws' rule under (key, stream_id) at bound p - 1 (key: HOST,
     // 8 words; the caller has checked that (first_batch + n_vectors B) t does not wrap).  Schemes on the register
     // path with n + 1 <= 27 make them in the share kernels; the others get launch_draws into draw_scratch
-    // (packed_gen_keyed_scratch_bytes() bytes) ahead of the unkeyed kernels.  keyed_fuse = false stages every scheme.
+    // (PackedGenPlan::draw_bytes bytes) ahead of the unkeyed kernels.  keyed_fuse = false stages every scheme.
     const uint32_t* key = nullptr;
     uint32_t stream_id = 0;
     uint64_t first_batch = 0;
     int64_t* draw_scratch = nullptr;
     bool keyed_fuse = true;
 };
-// Scratch the int32 call needs (0: native int32 kernels serve it).
-size_t packed_gen32_scratch_bytes(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p);
-// Whether a keyed call's draws are made in the share kernels (else staged through draw_scratch).
-bool packed_gen_keyed_in_kernel(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p);
-// Draw scratch a keyed call needs: 0 when the share kernels make the draws (or t == 0), else n_vectors B t 8 bytes.
-size_t packed_gen_keyed_scratch_bytes(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p);
+// How one share-gen call runs.  packed_gen_plan decides it once: the engine sizes the call's scratch from it and
+// launch_packed_generate dispatches from it, so the two cannot disagree.
+struct PackedGenPlan {
+    uint64_t B;                   // batches per vector
+    bool pair;                    // pair store: even B and a 16-byte aligned caller buffer (out32, else out) -- also
+                                  // when the i64 kernels write `scratch` for an int32 caller (narrow_bytes)
+    bool lazy;                    // p >= kLazyTruncMinP: exact shares with pair stores take the lazy-truncation kernels
+    bool registers;               // the register kernels (gen_register_path), else packed_wide.hip's workspace kernels
+    uint32_t keyed_path;          // 0 unkeyed; 1 draws made in the share kernels; 2 staged through draw_scratch, after
+                                  // which the call runs as the unkeyed one it has become (sda_packed_keyed_last_launch)
+    size_t draw_bytes;            // draw_scratch the staged call needs: n_vectors B t 8 (0 on paths 0 and 1)
+    size_t narrow_bytes;          // nonzero: int32 shares from the n + 1 = 81 register kernels, i64 into this much
+                                  // `scratch`, then launch_narrow32
+};
+PackedGenPlan packed_gen_plan(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p);
 // A/B knob: SDA_XCD_ORDER=0 runs the streaming kernels in natural workgroup order (xcd.h).
 bool xcd_order_enabled();
 // Exact share-gen uses lazy truncation (packed_gen.hip: Trunc<true>) for primes at least this big.

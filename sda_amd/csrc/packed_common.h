@@ -77,45 +77,54 @@ struct GenTables {
     uint32_t big2, big3;
 };
 
+// The host twiddles of share generation for any L = k + t + 1 and N3 = n + 1, as i64 words in the layout of the
+// workspace kernels' device table (packed_wide.hip): tw2[L - 1] (radix-2 level len: entries [len/2 - 1, len - 1)),
+// linv = L^{-1} mod p, then tw3[W3] and sq3[W3] (radix-3 level len: x and x^2 % p at entries [(len-3)/2, (len-3)/2 +
+// len)), W3 = (3 N3 - 3) / 2.  GenTables is the same table under its size caps.
+inline std::vector<int64_t> make_gen_twiddles(uint32_t L, uint32_t N3, int64_t p, int64_t ws, int64_t wn) {
+    const uint64_t W3 = (3ull * N3 - 3) / 2;
+    std::vector<int64_t> h(L + 2 * W3, 0);
+    // omega per level of a radix-r recursion over `size` points, top level (len = size) first: the recursion raises
+    // omega to the r at each level (mod_pow(ω, r))
+    auto levels = [p](int64_t om, uint32_t size, uint32_t r) {
+        std::vector<int64_t> lv;
+        for (uint32_t len = size; len >= r; len /= r) { lv.push_back(om); om = h_powmod(om, r, p); }
+        return lv;
+    };
+    // fft2_inverse: fft2 over omega^-1
+    std::vector<int64_t> lv = levels(h_modinv(ws, p), L, 2);
+    int lvl = (int)lv.size() - 1;
+    for (uint32_t len = 2; len <= L; len *= 2, --lvl)
+        for (uint32_t i = 0; i < len / 2; ++i) h[len / 2 - 1 + i] = h_powmod(lv[lvl], i, p);
+    h[L - 1] = h_modinv((int64_t)L, p);
+    lv = levels(wn, N3, 3);
+    lvl = (int)lv.size() - 1;
+    for (uint32_t len = 3; len <= N3; len *= 3, --lvl)
+        for (uint32_t j = 0; j < len; ++j) {
+            const int64_t x = h_powmod(lv[lvl], j, p);
+            h[L + (len - 3) / 2 + j] = x;
+            h[L + W3 + (len - 3) / 2 + j] = h_rem(x * x, p);
+        }
+    return h;
+}
+
 inline GenTables make_gen_tables(uint32_t L, uint32_t N3, int64_t p, int64_t ws, int64_t wn) {
     GenTables T;
     memset(&T, 0, sizeof(T));
     T.M = make_mont((uint32_t)p);
-    // fft2_inverse: fft2 over omega^-1; recursion squares omega at each level (mod_pow(ω, 2))
-    const int64_t winv = h_modinv(ws, p);
-    T.linv = (uint32_t)h_modinv((int64_t)L, p);
+    const std::vector<int64_t> h = make_gen_twiddles(L, N3, p, ws, wn);
+    const uint32_t W3 = (3 * N3 - 3) / 2;
+    for (uint32_t e = 0; e < L - 1; ++e) { T.tw2[e] = (uint32_t)h[e]; T.tw2_m[e] = to_mont(h[e], p); }
+    T.linv = (uint32_t)h[L - 1];
     T.linv_m = to_mont(T.linv, p);
-    {
-        int64_t om = winv;                 // omega for the top level (len = L)
-        std::vector<int64_t> per_level;    // omega per level, top first
-        for (uint32_t len = L; len >= 2; len /= 2) { per_level.push_back(om); om = h_powmod(om, 2, p); }
-        int lvl = (int)per_level.size() - 1;
-        for (uint32_t len = 2; len <= L; len *= 2, --lvl) {
-            for (uint32_t i = 0; i < len / 2; ++i) {
-                const int64_t w = h_powmod(per_level[lvl], i, p);
-                T.tw2[len / 2 - 1 + i] = (uint32_t)w;
-                T.tw2_m[len / 2 - 1 + i] = to_mont(w, p);
-            }
-        }
+    for (uint32_t o = 0; o < W3; ++o) {
+        const int64_t x = h[L + o], x2 = h[L + W3 + o];
+        T.tw3[o] = (uint32_t)x; T.tw3_m[o] = to_mont(x, p);
+        T.sq3[o] = (uint32_t)x2; T.sq3_m[o] = to_mont(x2, p);
     }
     T.big2 = 1;
     for (uint32_t e = 1; e < L - 1; ++e)
         if (T.tw2[e] > 1) { const uint64_t b = ((uint64_t)p + T.tw2[e] - 1) / T.tw2[e]; if (b > T.big2) T.big2 = (uint32_t)b; }
-    {
-        int64_t om = wn;
-        std::vector<int64_t> per_level;
-        for (uint32_t len = N3; len >= 3; len /= 3) { per_level.push_back(om); om = h_powmod(om, 3, p); }
-        int lvl = (int)per_level.size() - 1;
-        for (uint32_t len = 3; len <= N3; len *= 3, --lvl) {
-            for (uint32_t j = 0; j < len; ++j) {
-                const int64_t x = h_powmod(per_level[lvl], j, p);
-                const int64_t x2 = h_rem(x * x, p);
-                const uint32_t o = (len - 3) / 2 + j;
-                T.tw3[o] = (uint32_t)x; T.tw3_m[o] = to_mont(x, p);
-                T.sq3[o] = (uint32_t)x2; T.sq3_m[o] = to_mont(x2, p);
-            }
-        }
-    }
     T.big3 = 1;
     for (uint32_t j = 1; j < 3 && j < N3; ++j) {          // first radix-3 level: entries 1, 2 (len 3)
         const uint64_t b = ((uint64_t)p + T.tw3[j] - 1) / T.tw3[j];

@@ -21,11 +21,11 @@ struct GenKeyed {
     uint64_t zone;
 };
 
-inline GenKeyed make_gen_keyed(const PackedGenArgs& a) {
+inline GenKeyed make_gen_keyed(const PackedGenArgs& a, uint32_t p) {
     GenKeyed kg{};
     if (!a.key) return kg;
     for (int q = 0; q < 8; ++q) kg.key.k[q] = a.key[q];
-    const int64_t bound = (int64_t)a.prime - 1;
+    const int64_t bound = (int64_t)p - 1;
     kg.stream_id = a.stream_id;
     kg.first_batch = a.first_batch;
     kg.M = make_mod64(bound);
@@ -35,11 +35,21 @@ inline GenKeyed make_gen_keyed(const PackedGenArgs& a) {
 
 }  // namespace
 
+// What launch_packed_generate settles after the plan and hands to the per-object launchers with it.
+struct GenLaunch {
+    uint32_t prime;
+    const GenTables* T;
+    GenFixupLog log;
+    bool signbit;          // the table admits the sign-bit radix-2 half (DeviceTable::flags) and SDA_GEN_SIGNBIT allows it
+    bool xcd_order;        // XCD-chunked tile order (xcd.h)
+};
+
 // One launcher per (L = k+t+1, N3 = n+1); each is compiled in its own object (Makefile:
-// -DSDA_GEN_PART=N3 -DSDA_GEN_L=L) so the instantiations build in parallel.
+// -DSDA_GEN_PART=N3 -DSDA_GEN_L=L) so the instantiations build in parallel.  `a` is the call as the kernels see it
+// (launch_packed_generate), pl its plan.
 template <int L, int N3>
-hipError_t gen_launch(const PackedGenArgs& a, uint32_t k, uint32_t t, uint64_t B, const GenTables* T,
-                      const GenFixupLog& log, hipStream_t s);
+hipError_t gen_launch(const PackedGenArgs& a, const PackedGenPlan& pl, const GenLaunch& g, uint32_t k, uint32_t t,
+                      hipStream_t s);
 
 // Which schemes the register kernels serve (the rest run packed_wide.hip's workspace kernels).  At n + 1 = 81
 // the exact kernel without lazy truncation (p < 2^24, or odd B) needs its 64-bit sign products on top of 81
@@ -148,10 +158,6 @@ __device__ __forceinline__ void gen_store(const V& v, V* a) {
     if constexpr (SDA_GEN_NT_STORE) __builtin_nontemporal_store(v, a);
     else *a = v;
 }
-
-#ifndef SDA_GEN32_QUAD
-#define SDA_GEN32_QUAD 0
-#endif
 
 // Workgroup size: 256 batches, fewer for the wide transforms so the LDS stage stays <= 32 KiB.
 template <int L>
@@ -281,14 +287,7 @@ __device__ __forceinline__ void transform_canon(const int64_t (&raw)[L], const G
 // OT is the share type of `out`, int64_t or int32_t (sda_packed_generate32_dev: the shares are `% p` results,
 // p < 2^31, so the narrowing loses nothing).  The transform is the same; only the store tail differs.  STORE:
 //   0  each lane stores its own batch (odd B, or out not 16-byte aligned);
-//   1  the pair store above: 16 bytes per lane of i64 shares, 8 bytes of int32 ones;
-//   2  int32 only, B % 4 == 0: after the swap lanes 2m and 2m + 1 hold batches 4m .. 4m + 3 of one row; two row
-//      pairs at a time they trade halves (one DPP quad_perm per word), so each lane ends with four consecutive
-//      batches of one row: 16 bytes per lane, half the store instructions of form 1.  Measured 0.6-2 % SLOWER
-//      than form 1 at configs[2] in every process (5.33 against 5.23 ms canonical, 6.44 against 6.35 ms exact:
-//      the tail is not store-issue-bound, and the trade costs 12 DPP moves and 24 selects per lane; DESIGN.md
-//      §4.2, profiles/packed32), so it is compiled only with -DSDA_GEN32_QUAD=1 (A/B knob; SDA_GEN32_STORE=16
-//      then selects it at run time).
+//   1  the pair store above: 16 bytes per lane of i64 shares, 8 bytes of int32 ones.
 //
 // KEYED (packed_gen_keyed_kernel, n + 1 <= 27): `draws` is not read.  The tile's draws are the contiguous element
 // range [E0, E0 + nb t) of the draw stream, E0 = (first_batch + vec B + b0) t, nb the tile's live batches, and they
@@ -303,7 +302,6 @@ __device__ __forceinline__ void packed_gen_body(const int64_t* __restrict__ secr
                                                 uint32_t t, uint64_t B, const GenTables* __restrict__ Tp,
                                                 unsigned int* __restrict__ log, int xcd,
                                                 [[maybe_unused]] const GenKeyed& kg = GenKeyed{}) {
-    static_assert(STORE <= 1 || sizeof(OT) == 4, "the quad store is an int32 form");
     constexpr int LB = ilog(L, 2);
     constexpr int ND = ilog(N3, 3);
     constexpr int BS = gen_block<L>();
@@ -656,29 +654,7 @@ __device__ __forceinline__ void packed_gen_body(const int64_t* __restrict__ secr
                 }
             }
         };
-        if constexpr (STORE == 2) {
-            // B % 4 == 0: the four batches of a quad are live together.  The quads are stored whether or not their
-            // pairs took the fast path: a pair that did not is in the log, and the fix-up kernel, next on the
-            // stream, rewrites every row of its batches.
-            const bool odd = lane & 1;
-            const bool stq = pb < B;
-            // rows 4 q + 2 odd + half, batches from the even lane's pb
-            OT* qrow = out + ((uint64_t)vec * NR + 2 * (odd ? 1u : 0u) + half) * B + (pb - 2 * (odd ? 1u : 0u));
-            static_for<0, NR / 4>([&](auto q) {
-                const auto ra = __builtin_amdgcn_permlane32_swap((uint32_t)ys[1 + 4 * q], (uint32_t)ys[2 + 4 * q],
-                                                                 false, false);
-                const auto rb = __builtin_amdgcn_permlane32_swap((uint32_t)ys[3 + 4 * q], (uint32_t)ys[4 + 4 * q],
-                                                                 false, false);
-                // the even lane keeps its rows 4q + half and takes the odd lane's; the odd lane keeps rows 4q + 2 + half
-                const int32_t s0 = (int32_t)(odd ? ra[0] : rb[0]), s1 = (int32_t)(odd ? ra[1] : rb[1]);
-                const int32_t g0 = __builtin_amdgcn_mov_dpp(s0, 0xB1, 0xF, 0xF, true);     // quad_perm [1, 0, 3, 2]
-                const int32_t g1 = __builtin_amdgcn_mov_dpp(s1, 0xB1, 0xF, 0xF, true);
-                const v4i val = odd ? v4i{g0, g1, (int32_t)rb[0], (int32_t)rb[1]}
-                                    : v4i{(int32_t)ra[0], (int32_t)ra[1], g0, g1};
-                if (stq) gen_store(val, reinterpret_cast<v4i*>(qrow + (uint64_t)(4 * q) * B));
-            });
-            if constexpr (NR % 4 != 0) store_pair(std::integral_constant<int, NR / 2 - 1>{}, stq);
-        } else if constexpr (STORE == 1) {
+        if constexpr (STORE == 1) {
             static_for<0, NR / 2>([&](auto q) { store_pair(q, st1); });
         } else {                           // odd B: each lane stores its own batch
             OT* own = out + (uint64_t)vec * NR * B + b;
@@ -730,106 +706,74 @@ void packed_gen32_keyed_kernel(const int64_t* __restrict__ secrets, uint64_t D, 
 
 }  // namespace
 
-// The non-lazy exact kernels (p < 2^24, or odd B / unaligned out) exist only where gen_register_path admits them.
-template <int L, int N3, bool CANON>
-static hipError_t gen_launch_mode(const PackedGenArgs& a, uint32_t k, uint32_t t, uint64_t B, const GenTables* T,
-                                  uint32_t p, const GenFixupLog& log, hipStream_t s) {
+// One share kernel launch: the wrapper for the share type OT (int64_t or int32_t) and for a.key.  The keyed twins and
+// the int32 kernels exist in the objects with n + 1 <= 27 only (gen_launch_t refuses the rest).
+template <int L, int N3, int STORE, bool CANON, bool LAZY, bool SIGNBIT, class OT>
+static void gen_launch_kernel(const PackedGenArgs& a, OT* out, const PackedGenPlan& pl, const GenLaunch& g, uint32_t k,
+                              uint32_t t, hipStream_t s) {
     constexpr int BS = gen_block<L>();
+    constexpr bool I32 = sizeof(OT) == 4;
+    const uint64_t B = pl.B;
     const dim3 grid((unsigned)((B + BS - 1) / BS), (unsigned)a.n_vectors);
-    // (align_as: the i64 kernels run into scratch for an int32 caller and choose as for that caller's buffer)
-    const bool wide = B % 2 == 0 && ((uintptr_t)a.out % 16) == 0 && ((uintptr_t)a.align_as % 16) == 0;
-    const int xcd = a.xcd_order && (uint64_t)grid.x * grid.y < (1ull << 32) ? 1 : 0;
-    constexpr bool NONLAZY = CANON || gen_register_path(L, N3, true);
-    // a.key (n + 1 <= 27: launch_packed_generate stages the draws of the other schemes): the keyed twin
-    [[maybe_unused]] const GenKeyed kg = make_gen_keyed(a);
-#define SDA_GEN64(WD, CN, LZ, SB)                                                                                 \
-    do {                                                                                                          \
-        if constexpr (N3 <= 27) {                                                                                 \
-            if (a.key) {                                                                                          \
-                hipLaunchKernelGGL((packed_gen_keyed_kernel<L, N3, WD, CN, LZ, SB>), grid, dim3(BS), 0, s,        \
-                                   a.secrets, a.dimension, kg, a.out, k, t, B, T, log.count, xcd);                \
-                break;                                                                                            \
-            }                                                                                                     \
-        }                                                                                                         \
-        hipLaunchKernelGGL((packed_gen_kernel<L, N3, WD, CN, LZ, SB>), grid, dim3(BS), 0, s, a.secrets,           \
-                           a.dimension, a.draws, a.out, k, t, B, T, log.count, xcd);                              \
-    } while (0)
-    if (a.key && N3 > 27) return hipErrorInvalidValue;
-    if (wide && !CANON && p >= kLazyTruncMinP && a.signbit)   // exact shares, sign-bit radix-2 half
-        SDA_GEN64(true, false, true, true);
-    else if (wide && !CANON && p >= kLazyTruncMinP)          // exact shares, lazy zero handling
-        SDA_GEN64(true, false, true, false);
-    else if constexpr (!NONLAZY)
-        return hipErrorInvalidValue;                          // the dispatcher sends these to packed_wide.hip
-    else if (wide)
-        SDA_GEN64(true, CANON, false, false);
+    const int xcd = g.xcd_order && (uint64_t)grid.x * grid.y < (1ull << 32) ? 1 : 0;
+    if constexpr (N3 <= 27) {
+        if (a.key) {
+            const GenKeyed kg = make_gen_keyed(a, g.prime);
+            if constexpr (I32)
+                hipLaunchKernelGGL((packed_gen32_keyed_kernel<L, N3, STORE, CANON, LAZY, SIGNBIT>), grid, dim3(BS), 0, s,
+                                   a.secrets, a.dimension, kg, out, k, t, B, g.T, g.log.count, xcd);
+            else
+                hipLaunchKernelGGL((packed_gen_keyed_kernel<L, N3, STORE == 1, CANON, LAZY, SIGNBIT>), grid, dim3(BS), 0,
+                                   s, a.secrets, a.dimension, kg, out, k, t, B, g.T, g.log.count, xcd);
+            return;
+        }
+    }
+    if constexpr (I32)
+        hipLaunchKernelGGL((packed_gen32_kernel<L, N3, STORE, CANON, LAZY, SIGNBIT>), grid, dim3(BS), 0, s, a.secrets,
+                           a.dimension, a.draws, out, k, t, B, g.T, g.log.count, xcd);
     else
-        SDA_GEN64(false, CANON, false, false);
-#undef SDA_GEN64
-    return hipSuccess;
+        hipLaunchKernelGGL((packed_gen_kernel<L, N3, STORE == 1, CANON, LAZY, SIGNBIT>), grid, dim3(BS), 0, s, a.secrets,
+                           a.dimension, a.draws, out, k, t, B, g.T, g.log.count, xcd);
 }
 
-// The same choice for int32 shares (a.out32).  Built with SDA_GEN32_QUAD, a.store32 == 2 (SDA_GEN32_STORE=16)
-// takes the 16-byte quad store when B % 4 == 0.
-template <int L, int N3, bool CANON>
-static hipError_t gen_launch_mode32(const PackedGenArgs& a, uint32_t k, uint32_t t, uint64_t B, const GenTables* T,
-                                    uint32_t p, const GenFixupLog& log, hipStream_t s) {
-    if constexpr (N3 > 27) {
-        return hipErrorInvalidValue;                          // launch_packed_generate narrows the i64 kernels' output
+// The variant (STORE, CANON, LAZY, SIGNBIT) of one launch, chosen once from the plan for either share type.  The
+// non-lazy exact kernels (p < 2^24, or odd B / unaligned out) exist only where gen_register_path admits them.
+template <int L, int N3, bool CANON, class OT>
+static hipError_t gen_launch_t(const PackedGenArgs& a, OT* out, const PackedGenPlan& pl, const GenLaunch& g, uint32_t k,
+                               uint32_t t, hipStream_t s) {
+    if constexpr (sizeof(OT) == 4 && N3 > 27) {
+        return hipErrorInvalidValue;                          // the plan narrows the i64 kernels' output (narrow_bytes)
     } else {
-        constexpr int BS = gen_block<L>();
-        const dim3 grid((unsigned)((B + BS - 1) / BS), (unsigned)a.n_vectors);
-        const bool wide = B % 2 == 0 && ((uintptr_t)a.out32 % 16) == 0;
-        constexpr bool QUAD = SDA_GEN32_QUAD;
-        const bool quad = QUAD && wide && B % 4 == 0 && a.store32 == 2;
-        const int xcd = a.xcd_order && (uint64_t)grid.x * grid.y < (1ull << 32) ? 1 : 0;
-        const GenKeyed kg = make_gen_keyed(a);                // a.key: the keyed twin
-#define SDA_GEN32(STORE, CN, LZ, SB)                                                                               \
-    do {                                                                                                           \
-        if (a.key)                                                                                                 \
-            hipLaunchKernelGGL((packed_gen32_keyed_kernel<L, N3, STORE, CN, LZ, SB>), grid, dim3(BS), 0, s,        \
-                               a.secrets, a.dimension, kg, a.out32, k, t, B, T, log.count, xcd);                   \
-        else                                                                                                       \
-            hipLaunchKernelGGL((packed_gen32_kernel<L, N3, STORE, CN, LZ, SB>), grid, dim3(BS), 0, s, a.secrets,   \
-                               a.dimension, a.draws, a.out32, k, t, B, T, log.count, xcd);                         \
-    } while (0)
-#define SDA_GEN32_WIDE(CN, LZ, SB)                                 \
-    do {                                                           \
-        if constexpr (QUAD) {                                      \
-            if (quad) SDA_GEN32(2, CN, LZ, SB);                    \
-        }                                                          \
-        if (!quad) SDA_GEN32(1, CN, LZ, SB);                       \
-    } while (0)
-        if (wide && !CANON && p >= kLazyTruncMinP && a.signbit) {
-            SDA_GEN32_WIDE(false, true, true);
-        } else if (wide && !CANON && p >= kLazyTruncMinP) {
-            SDA_GEN32_WIDE(false, true, false);
-        } else if (wide) {
-            SDA_GEN32_WIDE(CANON, false, false);
-        } else {
-            SDA_GEN32(0, CANON, false, false);
-        }
-#undef SDA_GEN32_WIDE
-#undef SDA_GEN32
+        if (a.key && N3 > 27) return hipErrorInvalidValue;    // the plan stages these draws (keyed_path 2)
+        const bool lazy = pl.pair && !CANON && pl.lazy;
+        if (lazy && g.signbit)                                // exact shares, sign-bit radix-2 half
+            gen_launch_kernel<L, N3, 1, false, true, true>(a, out, pl, g, k, t, s);
+        else if (lazy)                                        // exact shares, lazy zero handling
+            gen_launch_kernel<L, N3, 1, false, true, false>(a, out, pl, g, k, t, s);
+        else if constexpr (!(CANON || gen_register_path(L, N3, true)))
+            return hipErrorInvalidValue;                      // the plan sends these to packed_wide.hip
+        else if (pl.pair)
+            gen_launch_kernel<L, N3, 1, CANON, false, false>(a, out, pl, g, k, t, s);
+        else
+            gen_launch_kernel<L, N3, 0, CANON, false, false>(a, out, pl, g, k, t, s);
         return hipSuccess;
     }
 }
 
 template <int L, int N3>
-hipError_t gen_launch(const PackedGenArgs& a, uint32_t k, uint32_t t, uint64_t B, const GenTables* T,
-                      const GenFixupLog& log, hipStream_t s) {
+hipError_t gen_launch(const PackedGenArgs& a, const PackedGenPlan& pl, const GenLaunch& g, uint32_t k, uint32_t t,
+                      hipStream_t s) {
     constexpr int BS = gen_block<L>();
-    if ((B + BS - 1) / BS > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const uint32_t p = a.prime;
-    const hipError_t e = a.out32 ? (a.canonical ? gen_launch_mode32<L, N3, true>(a, k, t, B, T, p, log, s)
-                                                : gen_launch_mode32<L, N3, false>(a, k, t, B, T, p, log, s))
-                         : a.canonical ? gen_launch_mode<L, N3, true>(a, k, t, B, T, p, log, s)
-                                       : gen_launch_mode<L, N3, false>(a, k, t, B, T, p, log, s);
+    if ((pl.B + BS - 1) / BS > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const hipError_t e = a.out32 ? (a.canonical ? gen_launch_t<L, N3, true>(a, a.out32, pl, g, k, t, s)
+                                                : gen_launch_t<L, N3, false>(a, a.out32, pl, g, k, t, s))
+                         : a.canonical ? gen_launch_t<L, N3, true>(a, a.out, pl, g, k, t, s)
+                                       : gen_launch_t<L, N3, false>(a, a.out, pl, g, k, t, s);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }
-template hipError_t gen_launch<SDA_GEN_L, SDA_GEN_PART>(const PackedGenArgs&, uint32_t, uint32_t, uint64_t,
-                                                        const GenTables*, const GenFixupLog&, hipStream_t);
+template hipError_t gen_launch<SDA_GEN_L, SDA_GEN_PART>(const PackedGenArgs&, const PackedGenPlan&, const GenLaunch&,
+                                                        uint32_t, uint32_t, hipStream_t);
 
 #else  // dispatcher, tables, generic fix-up
 
@@ -975,69 +919,69 @@ bool xcd_order_enabled() {
 
 size_t packed_gen_log_bytes() { return 64 + (size_t)kGenLogCap * sizeof(uint64_t); }
 
-// the register kernels' variant: WIDE stores need even B and a 16-byte aligned output (the caller's int32 buffer,
-// when the i64 kernels run into scratch for it); lazy truncation p >= 2^24
-static bool gen_takes_register_path(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p) {
-    const uint64_t B = (a.dimension + k - 1) / k;
-    const void* o = a.out32 ? (const void*)a.out32 : a.align_as ? a.align_as : (const void*)a.out;
-    const bool exact_nonlazy = !a.canonical && !(B % 2 == 0 && ((uintptr_t)o % 16) == 0 && p >= kLazyTruncMinP);
-    return gen_register_path(k + t + 1, n + 1, exact_nonlazy);
+// Reads the caller's fields only (none of scratch, flag, draw_scratch), so the engine can plan a call before it has
+// sized those and the launcher arrives at the same plan after.
+PackedGenPlan packed_gen_plan(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p) {
+    PackedGenPlan pl{};
+    pl.B = (a.dimension + k - 1) / k;
+    const void* buf = a.out32 ? (const void*)a.out32 : (const void*)a.out;
+    pl.pair = pl.B % 2 == 0 && (uintptr_t)buf % 16 == 0;
+    pl.lazy = p >= kLazyTruncMinP;
+    pl.registers = gen_register_path(k + t + 1, n + 1, !a.canonical && !(pl.pair && pl.lazy));
+    // keyed: draws in the share kernels on the register path up to n + 1 = 27, else staged
+    if (a.key) pl.keyed_path = a.keyed_fuse && n + 1 <= 27 && pl.registers ? 1 : 2;
+    if (pl.keyed_path == 2) pl.draw_bytes = (size_t)(a.n_vectors * pl.B * t) * sizeof(int64_t);
+    // int32 shares at n + 1 = 81: the i64 register kernels into scratch, chosen as the i64 call with an output of
+    // a.out32's alignment would choose them, then one narrowing pass (no value is lost: every share is a `% p` result)
+    if (a.out32 && n + 1 > 27 && pl.registers) pl.narrow_bytes = (size_t)(a.n_vectors * n * pl.B) * sizeof(int64_t);
+    return pl;
 }
 
-// a keyed call whose draws are made in the share kernels: the register path up to n + 1 = 27
-bool packed_gen_keyed_in_kernel(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p) {
-    return a.key && a.keyed_fuse && n + 1 <= 27 && gen_takes_register_path(a, k, t, n, p);
-}
-
-size_t packed_gen_keyed_scratch_bytes(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p) {
-    if (!a.key || packed_gen_keyed_in_kernel(a, k, t, n, p)) return 0;
-    const uint64_t B = (a.dimension + k - 1) / k;
-    return (size_t)(a.n_vectors * B * t) * sizeof(int64_t);
-}
-
-size_t packed_gen32_scratch_bytes(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p) {
-    if (n + 1 <= 27 || !gen_takes_register_path(a, k, t, n, p)) return 0;
-    const uint64_t B = (a.dimension + k - 1) / k;
-    return (size_t)(a.n_vectors * n * B) * sizeof(int64_t);
+// the fix-up kernel for the share type OT and for a.key, after the share kernel on the stream
+template <class OT>
+static void gen_launch_fixup(const PackedGenArgs& a, OT* out, uint64_t B, const GenLaunch& g, uint32_t k, uint32_t t,
+                             uint32_t n, hipStream_t s) {
+    constexpr bool I32 = sizeof(OT) == 4;
+    // one argument list: `draws` is the draws pointer, or the keyed kernels' GenKeyed in its place
+    auto launch = [&](auto kernel, auto draws) {
+        hipLaunchKernelGGL(kernel, dim3(512), dim3(64), 0, s, a.secrets, a.dimension, draws, out, k, t, B, a.n_vectors,
+                           (int)(k + t + 1), (int)(n + 1), g.T, g.log, a.canonical ? 1 : 0);
+    };
+    if (a.key) {
+        if constexpr (I32) launch(packed_gen32_keyed_fixup_kernel, make_gen_keyed(a, g.prime));
+        else launch(packed_gen_keyed_fixup_kernel, make_gen_keyed(a, g.prime));
+    } else {
+        if constexpr (I32) launch(packed_gen32_fixup_kernel, a.draws);
+        else launch(packed_gen_fixup_kernel, a.draws);
+    }
 }
 
 hipError_t launch_packed_generate(const PackedGenArgs& args, uint32_t k, uint32_t t, uint32_t n, uint32_t p,
                                   uint32_t omega_secrets, uint32_t omega_shares, DeviceTable& tab, void* log_buf,
                                   hipStream_t s, bool* logged) {
     if (logged) *logged = false;
-    PackedGenArgs a = args;
-    a.prime = p;
+    const PackedGenPlan pl = packed_gen_plan(args, k, t, n, p);
     const uint32_t L = k + t + 1, N3 = n + 1;
-    const uint64_t B = (a.dimension + k - 1) / k;
-    if (a.key && !packed_gen_keyed_in_kernel(a, k, t, n, p)) {
-        // keyed, staged: the call's draws into the caller's scratch (packed_gen_keyed_scratch_bytes), then the
-        // unkeyed path below reads them back
-        const uint64_t count = a.n_vectors * B * t;
-        if (count) {
+    const uint64_t B = pl.B;
+    PackedGenArgs a = args;                                   // the call as the kernels see it
+    if (pl.keyed_path == 2) {
+        // staged: the call's draws into the caller's scratch, then the unkeyed kernels read them back
+        if (pl.draw_bytes) {
             if (!a.draw_scratch) return hipErrorInvalidValue;
-            const hipError_t e = launch_draws(a.key, a.stream_id, a.first_batch * t, count, (int64_t)p - 1,
-                                              a.draw_scratch, s);
+            const hipError_t e = launch_draws(a.key, a.stream_id, a.first_batch * t, pl.draw_bytes / sizeof(int64_t),
+                                              (int64_t)p - 1, a.draw_scratch, s);
             if (e != hipSuccess) return e;
         }
         a.draws = a.draw_scratch;
         a.key = nullptr;
     }
-    if (!gen_takes_register_path(a, k, t, n, p))             // past the register kernels: packed_wide.hip
+    if (!pl.registers)                                        // past the register kernels: packed_wide.hip
         return launch_packed_generate_wide(a, k, t, n, p, omega_secrets, omega_shares, tab, s);
     if (B == 0 || a.n_vectors == 0) return hipSuccess;
-    if (a.out32 && N3 > 27) {
-        // int32 shares at n + 1 = 81: the i64 register kernels into the caller's scratch, chosen as the i64 call
-        // with an output of a.out32's alignment would choose them, then one narrowing pass (no value is lost:
-        // every share is a `% p` result)
-        if (!a.scratch || !a.flag) return hipErrorInvalidValue;
-        PackedGenArgs b = a;
-        b.out = a.scratch;
-        b.align_as = a.out32;
-        b.out32 = nullptr;
-        const hipError_t e = launch_packed_generate(b, k, t, n, p, omega_secrets, omega_shares, tab, log_buf, s, logged);
-        if (e != hipSuccess) return e;
-        const uint64_t rows = a.n_vectors * n;
-        return launch_narrow32(a.scratch, rows, B, B, a.out32, B, a.flag, s);
+    if (pl.narrow_bytes) {                                    // i64 rows into scratch; narrowed at the end
+        if (!a.scratch || !a.flag || (uintptr_t)a.scratch % 16) return hipErrorInvalidValue;
+        a.out = a.scratch;
+        a.out32 = nullptr;
     }
     const uint32_t kv[5] = {L, N3, p, omega_secrets, omega_shares};
     std::vector<uint8_t> key((const uint8_t*)kv, (const uint8_t*)kv + sizeof(kv));
@@ -1050,20 +994,15 @@ hipError_t launch_packed_generate(const PackedGenArgs& args, uint32_t k, uint32_
         tab.flags = (T.big2 <= 4096 && T.big3 <= 4096) ? 1u : 0u;
     }
     const char* sb = getenv("SDA_GEN_SIGNBIT");                 // A/B knob: 0 = the mad_i64 sign kernel
-    a.signbit = (tab.flags & 1u) && !(sb && sb[0] == '0');
-    a.xcd_order = xcd_order_enabled();
-    if (a.out32) {
-        const char* st = getenv("SDA_GEN32_STORE");             // A/B knob, builds with SDA_GEN32_QUAD: 16 = quad store
-        a.store32 = st && st[0] == '1' && st[1] == '6' ? 2 : 0;
-    }
-    const GenTables* T = static_cast<const GenTables*>(tab.dev);
-    GenFixupLog log{static_cast<unsigned int*>(log_buf),
-                    reinterpret_cast<uint64_t*>(static_cast<unsigned int*>(log_buf) + 16), kGenLogCap};
-    hipError_t e = hipMemsetAsync(log.count, 0, sizeof(unsigned int), s);
+    const GenLaunch g{p, static_cast<const GenTables*>(tab.dev),
+                      GenFixupLog{static_cast<unsigned int*>(log_buf),
+                                  reinterpret_cast<uint64_t*>(static_cast<unsigned int*>(log_buf) + 16), kGenLogCap},
+                      (tab.flags & 1u) && !(sb && sb[0] == '0'), xcd_order_enabled()};
+    hipError_t e = hipMemsetAsync(g.log.count, 0, sizeof(unsigned int), s);
     if (e != hipSuccess) return e;
     if (logged) *logged = true;
     switch (N3 * 128 + L) {             // one object per (N3, L): Makefile GEN_PARTS
-#define SDA_GEN_CASE(N, LL) case N * 128 + LL: e = gen_launch<LL, N>(a, k, t, B, T, log, s); break;
+#define SDA_GEN_CASE(N, LL) case N * 128 + LL: e = gen_launch<LL, N>(a, pl, g, k, t, s); break;
         SDA_GEN_CASE(3, 2)
         SDA_GEN_CASE(9, 2) SDA_GEN_CASE(9, 4) SDA_GEN_CASE(9, 8)
         SDA_GEN_CASE(27, 2) SDA_GEN_CASE(27, 4) SDA_GEN_CASE(27, 8) SDA_GEN_CASE(27, 16)
@@ -1073,21 +1012,10 @@ hipError_t launch_packed_generate(const PackedGenArgs& args, uint32_t k, uint32_
         default: e = hipErrorInvalidValue;
     }
     if (e != hipSuccess) return e;
-    if (a.key && a.out32)
-        hipLaunchKernelGGL(packed_gen32_keyed_fixup_kernel, dim3(512), dim3(64), 0, s, a.secrets, a.dimension,
-                           make_gen_keyed(a), a.out32, k, t, B, a.n_vectors, (int)L, (int)N3, T, log,
-                           a.canonical ? 1 : 0);
-    else if (a.key)
-        hipLaunchKernelGGL(packed_gen_keyed_fixup_kernel, dim3(512), dim3(64), 0, s, a.secrets, a.dimension,
-                           make_gen_keyed(a), a.out, k, t, B, a.n_vectors, (int)L, (int)N3, T, log,
-                           a.canonical ? 1 : 0);
-    else if (a.out32)
-        hipLaunchKernelGGL(packed_gen32_fixup_kernel, dim3(512), dim3(64), 0, s, a.secrets, a.dimension, a.draws,
-                           a.out32, k, t, B, a.n_vectors, (int)L, (int)N3, T, log, a.canonical ? 1 : 0);
-    else
-        hipLaunchKernelGGL(packed_gen_fixup_kernel, dim3(512), dim3(64), 0, s, a.secrets, a.dimension, a.draws, a.out,
-                           k, t, B, a.n_vectors, (int)L, (int)N3, T, log, a.canonical ? 1 : 0);
-    return hipGetLastError();
+    a.out32 ? gen_launch_fixup(a, a.out32, B, g, k, t, n, s) : gen_launch_fixup(a, a.out, B, g, k, t, n, s);
+    e = hipGetLastError();
+    if (e != hipSuccess || !pl.narrow_bytes) return e;
+    return launch_narrow32(a.scratch, a.n_vectors * n, B, B, args.out32, B, a.flag, s);
 }
 
 hipError_t ensure_table(DeviceTable& t, const std::vector<uint8_t>& key, const void* host, size_t bytes) {

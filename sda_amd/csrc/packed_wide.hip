@@ -27,9 +27,8 @@ __device__ __forceinline__ uint32_t rev_trits_rt(uint32_t i, uint32_t ndig) {
     return r;
 }
 
-// Device table of the wide share-gen (i64 words): tw2[L-1] (radix-2 level len: entries
-// [len/2 - 1, len - 1)), linv, tw3[W3] and sq3[W3] (radix-3 level len: entries [(len-3)/2, (len-3)/2 +
-// len)), W3 = (3 (n+1) - 3) / 2 -- the layout of GenTables without its size caps.
+// Device table of the wide share-gen: make_gen_twiddles' i64 words (packed_common.h) -- tw2[L-1], linv, tw3[W3] and
+// sq3[W3], W3 = (3 (n+1) - 3) / 2.
 // (OT: the share type of out, i64 or int32 -- every share is a `% p` result, p < 2^31.)
 template <class OT>
 __device__ __forceinline__ void gen_wide_body(const int64_t* __restrict__ secrets, uint64_t D,
@@ -206,31 +205,10 @@ hipError_t launch_packed_generate_wide(const PackedGenArgs& a, uint32_t k, uint3
     const uint32_t L = k + t + 1, N3 = n + 1;
     const uint64_t B = (a.dimension + k - 1) / k;
     if (B == 0 || a.n_vectors == 0) return hipSuccess;
-    const uint64_t W3 = (3ull * N3 - 3) / 2;
     const uint32_t kv[6] = {0x57494445u /* wide */, L, N3, p, omega_secrets, omega_shares};
     std::vector<uint8_t> key((const uint8_t*)kv, (const uint8_t*)kv + sizeof(kv));
     if (tab.key != key) {
-        // the twiddles of make_gen_tables, any L / N3
-        std::vector<int64_t> h(L + 2 * W3, 0);
-        const int64_t P = p;
-        const int64_t winv = h_modinv(omega_secrets, P);
-        h[L - 1] = h_modinv((int64_t)L, P);
-        std::vector<int64_t> lv;
-        int64_t om = winv;
-        for (uint32_t len = L; len >= 2; len /= 2) { lv.push_back(om); om = h_powmod(om, 2, P); }
-        int lvl = (int)lv.size() - 1;
-        for (uint32_t len = 2; len <= L; len *= 2, --lvl)
-            for (uint32_t i = 0; i < len / 2; ++i) h[len / 2 - 1 + i] = h_powmod(lv[lvl], i, P);
-        lv.clear();
-        om = omega_shares;
-        for (uint32_t len = N3; len >= 3; len /= 3) { lv.push_back(om); om = h_powmod(om, 3, P); }
-        lvl = (int)lv.size() - 1;
-        for (uint32_t len = 3; len <= N3; len *= 3, --lvl)
-            for (uint32_t j = 0; j < len; ++j) {
-                const int64_t x = h_powmod(lv[lvl], j, P);
-                h[L + (len - 3) / 2 + j] = x;
-                h[L + W3 + (len - 3) / 2 + j] = h_rem(x * x, P);
-            }
+        const std::vector<int64_t> h = make_gen_twiddles(L, N3, p, omega_secrets, omega_shares);
         hipError_t e = ensure_table(tab, key, h.data(), h.size() * sizeof(int64_t));
         if (e != hipSuccess) return e;
     }

@@ -7,8 +7,9 @@ scripts/code_objects.py demangles them, so tests/test_packed_matrix_plan.py can 
 tests/test_gpu_packed_matrix.py against the instantiations in the built library.
 
 Restated here, each next to the line of the product it mirrors:
-  gen_register_path, kLazyTruncMinP, make_gen_tables' big2 / big3 <= 4096 rule (the sign-bit flag), the WIDE
-  (even B, 16-byte aligned out) rule, the reveal's 8/16/32/64/96 point buckets, its FULL / KU / STAGED choices
+  gen_register_path, kLazyTruncMinP, make_gen_tables' big2 / big3 <= 4096 rule (the sign-bit flag), packed_gen_plan's
+  pair-store (even B, 16-byte aligned out) rule and register / workspace choice, gen_launch_t's variant choice,
+  the reveal's 8/16/32/64/96 point buckets, its FULL / KU / STAGED choices
   and its lazy-only-at-the-threshold rule,
   the canonical n_idx > 32 detour, wide_lanes, and which batches a launch logs for its fix-up kernel.
 """
@@ -74,14 +75,14 @@ def gen_kernel(sch, B, out_mod16, mode, signbit_env=None):
     p = sch.prime_modulus
     L, N3 = sch.secret_count + sch.privacy_threshold() + 1, sch.share_count + 1
     canon = mode == CANONICAL
-    wide_store = B % 2 == 0 and out_mod16 % 16 == 0
-    lazy_ok = p >= LAZY_TRUNC_MIN_P
+    wide_store = B % 2 == 0 and out_mod16 % 16 == 0                 # packed_gen_plan: pair
+    lazy_ok = p >= LAZY_TRUNC_MIN_P                                 # packed_gen_plan: lazy
     exact_nonlazy = not canon and not (wide_store and lazy_ok)
-    if not gen_register_path(L, N3, exact_nonlazy):
+    if not gen_register_path(L, N3, exact_nonlazy):                 # packed_gen_plan: registers
         return "wide"
     assert L in GEN_PARTS.get(N3, ()), (L, N3)
-    signbit = gen_signbit_flag(sch) and not (signbit_env is not None and str(signbit_env)[:1] == "0")
-    if wide_store and not canon and lazy_ok:
+    signbit = gen_signbit_flag(sch) and not (signbit_env is not None and str(signbit_env)[:1] == "0")   # GenLaunch::signbit
+    if wide_store and not canon and lazy_ok:                        # gen_launch_t, from here on
         args = (True, False, True, signbit)
     elif wide_store:
         args = (True, canon, False, False)

@@ -5,8 +5,7 @@ The cases are those of tests/test_gpu_packed_matrix.py (plan: tests/packed_matri
 tests/packed_dispatch.py, input builders: that module's gen_inputs): ONE launch of V = 3 vectors of B = 550 / 549
 batches with an odd dimension, raw i64 secrets planted in a few batches.  Added here: outputs 4 and 12 bytes off
 a 16-byte boundary (int32 rows need only 4-byte alignment), and B = 548 -- the matrix's even B is no multiple of
-4, so its int32 rows alternate between 16- and 8-byte alignment; at B = 548 every row is 16-byte aligned (and the
-16-bytes-per-lane store of an SDA_GEN32_QUAD build, packed_gen.hip STORE = 2, runs only from B % 4 == 0).
+4, so its int32 rows alternate between 16- and 8-byte alignment; at B = 548 every row is 16-byte aligned.
 
 Every share is a `% p` result with p < 2^31, so narrowing the oracle's i64 shares is lossless; each test asserts
 that on the oracle's array before it compares.  The fix-up counts are held between the number of planted batches

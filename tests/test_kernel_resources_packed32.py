@@ -57,7 +57,8 @@ def test_int32_packed_kernels_exist_and_use_no_agprs_scratch_or_spills(kernels):
 def test_share_gen32_instantiations_mirror_the_i64_set_up_to_27_points(kernels):
     """<L, N3, STORE, CANON, LAZY, SIGNBIT> for every Makefile GEN_PART with n + 1 <= 27: the lazy kernels with
     the pair store (1), the others with the pair store and the one-batch-per-lane store (0); nothing at
-    n + 1 = 81 (scratch + narrowing), and no quad store (2: measured slower, an SDA_GEN32_QUAD build only)."""
+    n + 1 = 81 (scratch + narrowing), and no other STORE value (a 16-byte quad store, 2, measured slower and was
+    removed: DESIGN.md §4.2)."""
     seen = {_gen32_args(k["pretty"]) for k in kernels}
     seen.discard(None)
     expect = set()
