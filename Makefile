@@ -18,7 +18,7 @@ HOST    := engine engine_dev hbm engine_codec engine_pipelines engine_host
 OBJS    := $(patsubst %,$(OBJDIR)/%.o,$(PLAIN)) $(patsubst %,$(OBJDIR)/%.o,$(HOST)) \
            $(OBJDIR)/packed_gen.o $(patsubst %,$(OBJDIR)/packed_gen_%.o,$(GEN_PARTS)) \
            $(OBJDIR)/packed_reveal.o $(patsubst %,$(OBJDIR)/packed_reveal_%.o,$(REVEAL_PARTS))
-HDRS    := $(CSRC)/packed_common.h $(CSRC)/kernels.h $(CSRC)/modarith.h $(CSRC)/xcd.h $(CSRC)/draws_common.h $(CSRC)/codec_common.h include/sda_engine.h
+HDRS    := $(CSRC)/packed_common.h $(CSRC)/kernels.h $(CSRC)/reveal_plan.h $(CSRC)/modarith.h $(CSRC)/xcd.h $(CSRC)/draws_common.h $(CSRC)/codec_common.h include/sda_engine.h
 
 all: $(LIB) oracle
 

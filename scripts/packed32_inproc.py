@@ -7,8 +7,8 @@ placement, clocks and box state are shared by every leg.  The yardstick of an in
 same round.
     python scripts/packed32_inproc.py [rounds] [out_file]
 Legs: share-gen {canonical, exact} x {i64, int32}; reveal {canonical, exact} x {i64, int32}.
-SDA_INPROC_ALT_LIB=<another build of libsda_engine.so> adds both share-gen legs from that library, loaded into the
-same process (the A/B of two builds, e.g. against the parent commit's), and prints per leg whether this build's
+SDA_INPROC_ALT_LIB=<another build of libsda_engine.so> adds the share-gen and reveal legs from that library, loaded into
+the same process (the A/B of two builds, e.g. against the parent commit's), and prints per leg whether this build's
 median is within the other's median plus the other's own spread (max - min) in this run.  The two builds' legs trade
 places every other round: a leg's place in the round is worth up to 1 % (profiles/gen_launch/ab_parent.txt).
 Per leg: per-launch ms of every round, median, spread, algorithmic bytes, fraction of the 8 TB/s HBM peak, and for
@@ -71,12 +71,12 @@ def gen32(mode, e=eng):
     e.packed_generate32_dev(sch, sec.data_ptr(), D, V, drw.data_ptr(), sh32.data_ptr(), mode, st)
 
 
-def rev64(mode):
-    eng.packed_reconstruct_dev(sch, D, idx, V, sub64.data_ptr(), rev.data_ptr(), mode, st)
+def rev64(mode, e=eng):
+    e.packed_reconstruct_dev(sch, D, idx, V, sub64.data_ptr(), rev.data_ptr(), mode, st)
 
 
-def rev32(mode):
-    eng.packed_reconstruct32_dev(sch, D, idx, V, sub32.data_ptr(), rev.data_ptr(), mode, st)
+def rev32(mode, e=eng):
+    e.packed_reconstruct32_dev(sch, D, idx, V, sub32.data_ptr(), rev.data_ptr(), mode, st)
 
 
 gen_in = 8.0 * V * (D + B * t)
@@ -90,6 +90,9 @@ if alt:
              ("gen int32 alt lib", lambda mode: gen32(mode, alt), "gen32", "gen i64 alt lib")]
 LEGS += [("reveal i64", rev64, "rev64", None),
          ("reveal int32", rev32, "rev32", "reveal i64")]
+if alt:
+    LEGS += [("reveal i64 alt lib", lambda mode: rev64(mode, alt), "rev64", None),
+             ("reveal int32 alt lib", lambda mode: rev32(mode, alt), "rev32", "reveal i64 alt lib")]
 BY_NAME = {leg[0]: leg for leg in LEGS}
 
 
@@ -116,6 +119,11 @@ for mname, mode in MODES:
     sub32.copy_(sh32[:, idx, :])
     rev64(mode)
     ref = rev.clone()
+    for fn, e in ((rev64, alt), (rev32, alt)) if alt else ():      # the other build's reveals, against this build's i64
+        rev.fill_(0x5A5A5A5A)
+        fn(mode, e)
+        torch.cuda.synchronize()
+        checks.append(torch.equal(rev, ref))
     rev.fill_(0x5A5A5A5A)
     rev32(mode)
     fix_rev = eng.packed_fixup_count()
@@ -123,8 +131,9 @@ for mname, mode in MODES:
     checks.append(torch.equal(rev, ref))
     checks.append(torch.equal(torch.remainder(rev, p), sec))
     del ref
-    say(f"[{mname}] int32 == i64: gen {checks[-3]}, gen alt lib {checks[0] if alt else 'not given'}, "
-        f"reveal {checks[-2]}, reveals the secrets {checks[-1]}; fix-up batches gen32 {fix_gen} reveal32 {fix_rev}")
+    say(f"[{mname}] int32 == i64: gen {checks[1 if alt else 0]}, gen alt lib {checks[0] if alt else 'not given'}, "
+        f"reveal {checks[-2]}, reveal alt lib (i64, int32) {tuple(checks[2:4]) if alt else 'not given'}, "
+        f"reveals the secrets {checks[-1]}; fix-up batches gen32 {fix_gen} reveal32 {fix_rev}")
     assert all(checks)
     res = {leg[0]: [] for leg in LEGS}
     for r in range(rounds):
@@ -152,7 +161,7 @@ for mname, mode in MODES:
                      f"{nb / bytes_of[key.replace('32', '64')]:.3f})")
         say(line)
         say(f"[{mname}] {name:<24} per-launch ms by round: " + " ".join(f"{x:.4f}" for x in res[name]))
-    for name in ("gen i64", "gen int32") if alt else ():
+    for name in ("gen i64", "gen int32", "reveal i64", "reveal int32") if alt else ():
         o = res[name + " alt lib"]
         bound = med[name + " alt lib"] + max(o) - min(o)
         say(f"[{mname}] {name:<24} median {med[name]:.4f} ms against the alt lib's {med[name + ' alt lib']:.4f} + "

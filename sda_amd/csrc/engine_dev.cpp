@@ -28,16 +28,18 @@ sda_status packed_generate(sda_engine* h, const sda_sharing_scheme* s, sda::Pack
     return SDA_OK;
 }
 
-hipError_t packed_reveal(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedRevealArgs& ra,
-                         const uint64_t* indices, uint64_t n_idx, int32_t mode, hipStream_t st) {
-    return sda::launch_packed_reveal(ra, indices, (uint32_t)n_idx, (uint32_t)s->secret_count,
-                                     (uint32_t)s->privacy_threshold, (uint32_t)s->modulus, (uint32_t)s->omega_secrets,
-                                     (uint32_t)s->omega_shares, mode, h->rev_tab, h->gen_log, st, &h->gen_log_used);
-}
-
-sda_status reveal_status(hipError_t e, int32_t mode) {
-    if (e == hipErrorInvalidValue && mode == SDA_REVEAL_CANONICAL)
+sda_status packed_reveal(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedRevealArgs& ra,
+                         const uint64_t* indices, uint64_t n_idx, int32_t mode, hipStream_t st, bool* refused) {
+    if (refused) *refused = false;
+    if (sda_status e = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
+    const hipError_t e = sda::launch_packed_reveal(ra, indices, (uint32_t)n_idx, (uint32_t)s->secret_count,
+                                                   (uint32_t)s->privacy_threshold, (uint32_t)s->modulus,
+                                                   (uint32_t)s->omega_secrets, (uint32_t)s->omega_shares, mode,
+                                                   h->rev_tab, h->gen_log, st, &h->gen_log_used);
+    if (e == hipErrorInvalidValue && mode == SDA_REVEAL_CANONICAL) {
+        if (refused) *refused = true;
         return fail(SDA_ERR_UNSUPPORTED, "canonical reveal needs distinct clerk indices");
+    }
     HIP_TRY(e);
     return SDA_OK;
 }
@@ -63,6 +65,28 @@ static sda_status combine_dev(sda_engine* h, int64_t modulus, const T* shares, u
     else
         HIP_TRY(sda::launch_combine_wide32(shares, n, dim, stride, out, m, pick(h, stream), accumulate,
                                            &h->combine_last));
+    return ok();
+}
+
+// Both reconstruct entry points, T the share type; the NULL-argument check is the int32 one's alone, as it has been.
+template <typename T>
+static sda_status packed_reconstruct(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                     const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors, const T* shares,
+                                     int64_t* out, int32_t mode, void* stream) {
+    if (!h || !s || s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "need a PackedShamir scheme");
+    if (sda_status st = check_packed(s)) return st;
+    if (mode != SDA_REVEAL_EXACT && mode != SDA_REVEAL_CANONICAL) return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
+    if (dimension == 0) return ok();                        // batched.rs:77-81: no batch, no check
+    if (n_idx < s->privacy_threshold + s->secret_count)
+        return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");
+    if (n_idx > sda::kRevealMaxShares)
+        return fail(SDA_ERR_UNSUPPORTED, "more than %u clerk shares per batch", sda::kRevealMaxShares);
+    if (n_vectors > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 vectors per launch");
+    if (sizeof(T) == 4 && n_vectors && (!out || !shares || !indices)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    sda::PackedRevealArgs ra{nullptr, dimension, n_vectors, out};
+    if constexpr (sizeof(T) == 4) ra.shares32 = shares; else ra.shares = shares;
+    if (sda_status e = packed_reveal(h, s, ra, indices, n_idx, mode, pick(h, stream))) return e;
     return ok();
 }
 
@@ -203,21 +227,7 @@ sda_status sda_packed_reconstruct_dev(sda_engine* h, const sda_sharing_scheme* s
                                       const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
                                       const int64_t* shares, int64_t* out, int32_t mode, void* stream) {
     SDA_ENTRY;
-    if (!h || !s || s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "need a PackedShamir scheme");
-    if (sda_status st = check_packed(s)) return st;
-    if (mode != SDA_REVEAL_EXACT && mode != SDA_REVEAL_CANONICAL) return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
-    if (dimension == 0) return ok();                        // batched.rs:77-81: no batch, no check
-    if (n_idx < s->privacy_threshold + s->secret_count)
-        return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");
-    if (n_idx > sda::kRevealMaxShares)
-        return fail(SDA_ERR_UNSUPPORTED, "more than %u clerk shares per batch", sda::kRevealMaxShares);
-    if (n_vectors > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 vectors per launch");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = pick(h, stream);
-    if (sda_status e = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
-    sda::PackedRevealArgs ra{shares, dimension, n_vectors, out};
-    if (sda_status e = reveal_status(packed_reveal(h, s, ra, indices, n_idx, mode, st), mode)) return e;
-    return ok();
+    return packed_reconstruct(h, s, dimension, indices, n_idx, n_vectors, shares, out, mode, stream);
 }
 
 // int32 shares (every share is a `% p` result, p < 2^31): native int32 kernels, or at n + 1 = 81 the i64 register
@@ -243,23 +253,7 @@ sda_status sda_packed_reconstruct32_dev(sda_engine* h, const sda_sharing_scheme*
                                         const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
                                         const int32_t* shares, int64_t* out, int32_t mode, void* stream) {
     SDA_ENTRY;
-    if (!h || !s || s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "need a PackedShamir scheme");
-    if (sda_status st = check_packed(s)) return st;
-    if (mode != SDA_REVEAL_EXACT && mode != SDA_REVEAL_CANONICAL) return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
-    if (dimension == 0) return ok();                        // batched.rs:77-81: no batch, no check
-    if (n_idx < s->privacy_threshold + s->secret_count)
-        return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");
-    if (n_idx > sda::kRevealMaxShares)
-        return fail(SDA_ERR_UNSUPPORTED, "more than %u clerk shares per batch", sda::kRevealMaxShares);
-    if (n_vectors > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 vectors per launch");
-    if (n_vectors && (!out || !shares || !indices)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = pick(h, stream);
-    if (sda_status e = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
-    sda::PackedRevealArgs ra{nullptr, dimension, n_vectors, out};
-    ra.shares32 = shares;
-    if (sda_status e = reveal_status(packed_reveal(h, s, ra, indices, n_idx, mode, st), mode)) return e;
-    return ok();
+    return packed_reconstruct(h, s, dimension, indices, n_idx, n_vectors, shares, out, mode, stream);
 }
 
 sda_status sda_additive_generate_dev(sda_engine* h, int64_t modulus, uint64_t share_count, const int64_t* secrets,

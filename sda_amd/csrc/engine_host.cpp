@@ -503,9 +503,8 @@ sda_status host_packed_reconstruct(sda_engine* h, const sda_sharing_scheme* s, u
         int64_t* dout = a.take<int64_t>(ds);
         for (uint64_t i = 0; i < n_rows; ++i)        // batched.rs:83-85: clerk i's batches [b0, b0 + nb)
             HIP_TRY(hipMemcpyAsync(din + i * nb, rows[i] + b0, nb * 8, hipMemcpyHostToDevice, d->stream));
-        if (sda_status e = ensure(&d->gen_log, &d->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
         sda::PackedRevealArgs ra{din, ds, 1, dout};
-        HIP_TRY(packed_reveal(d, s, ra, indices, n_rows, SDA_REVEAL_EXACT, d->stream));
+        if (sda_status e = packed_reveal(d, s, ra, indices, n_rows, SDA_REVEAL_EXACT, d->stream)) return e;
         HIP_TRY(hipMemcpyAsync(out + s0, dout, ds * 8, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(hipStreamSynchronize(d->stream));
         return SDA_OK;

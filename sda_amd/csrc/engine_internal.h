@@ -213,11 +213,12 @@ std::vector<uint32_t> pack_seeds(const int64_t* const* rows, const uint64_t* len
 // at n + 1 = 81 get the handle-owned scratch their narrowing pass needs, and a keyed call (ga.key) off the in-kernel
 // path the handle-owned draw scratch; a keyed call that launches records its path (sda_packed_keyed_last_launch).
 sda_status packed_generate(sda_engine* h, const sda_sharing_scheme* s, sda::PackedGenArgs ga, hipStream_t st);
-// Reveal of `ra` from n_idx clerk shares (h->gen_log is allocated); hipErrorInvalidValue: a CANONICAL reveal of
-// repeated clerk indices, which reveal_status turns into the call's failure.
-hipError_t packed_reveal(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedRevealArgs& ra,
-                         const uint64_t* indices, uint64_t n_idx, int32_t mode, hipStream_t st);
-sda_status reveal_status(hipError_t e, int32_t mode);
+// Reveal of `ra` from n_idx clerk shares with h's table and fix-up log (allocated here).  A CANONICAL reveal of
+// repeated clerk indices fails with SDA_ERR_UNSUPPORTED and sets *refused (optional), for a caller that can run
+// EXACT instead.
+sda_status packed_reveal(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedRevealArgs& ra,
+                         const uint64_t* indices, uint64_t n_idx, int32_t mode, hipStream_t st,
+                         bool* refused = nullptr);
 
 // ---------------- payload encoder (engine_codec.cpp) ----------------
 // rows x len values of [rows][stride] device rows (T: int64_t or int32_t) encoded back to back into dst;

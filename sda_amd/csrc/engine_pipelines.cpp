@@ -112,7 +112,6 @@ sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const
             HIP_TRY(hipMemcpy2DAsync(c, B * 8, shares, share_len * 8, B * 8, n_idx, hipMemcpyDeviceToDevice, st));
             src = c;
         }
-        if (sda_status e = ensure(&h->gen_log, &h->gen_log_bytes, sda::packed_gen_log_bytes())) return e;
         sda::PackedRevealArgs ra{src, dimension, 1, dmasked};
         // The output is positive(unmask(reveal)).  When the masking modulus (or no mask) and output_modulus are
         // both the sharing prime, that is the canonical residue of (reveal - mask) mod p, which depends only on
@@ -124,14 +123,15 @@ sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const
         const bool residue_only = output_modulus == p && (ms->kind == SDA_MASKING_NONE || q == p) &&
                                   !(keep && atoi(keep) == 1);
         const int32_t run_mode = (mode == SDA_REVEAL_EXACT && residue_only) ? SDA_REVEAL_CANONICAL : mode;
-        hipError_t e = packed_reveal(h, ss, ra, indices, n_idx, run_mode, st);
+        bool refused = false;
+        sda_status e = packed_reveal(h, ss, ra, indices, n_idx, run_mode, st, &refused);
         rec.reveal_mode = run_mode == SDA_REVEAL_CANONICAL ? 2 : 1;
-        if (e == hipErrorInvalidValue && run_mode != mode) {
+        if (refused && run_mode != mode) {
             e = packed_reveal(h, ss, ra, indices, n_idx, mode, st);
             rec.reveal_mode = 1;
             rec.fell_back = 1;
         }
-        if (sda_status r = reveal_status(e, mode)) return r;
+        if (e) return e;
     }
     // 3. unmask (receive.rs:149-152) + RecipientOutput::positive (:14-20), one pass
     HIP_TRY(sda::launch_unmask_positive(dmasked, ms->kind == SDA_MASKING_NONE ? nullptr : dmask, D, q,

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "modarith.h"
+#include "reveal_plan.h"
 
 namespace sda {
 
@@ -142,8 +143,6 @@ struct PackedGenPlan {
 PackedGenPlan packed_gen_plan(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p);
 // A/B knob: SDA_XCD_ORDER=0 runs the streaming kernels in natural workgroup order (xcd.h).
 bool xcd_order_enabled();
-// Exact share-gen uses lazy truncation (packed_gen.hip: Trunc<true>) for primes at least this big.
-constexpr uint32_t kLazyTruncMinP = 1u << 24;
 // Batches whose inputs fall outside (-p, p) are logged by the fast kernel and recomputed by a
 // generic exact fix-up kernel.  `log_buf` is device memory of packed_gen_log_bytes() bytes.
 constexpr uint32_t kGenLogCap = 1u << 16;
@@ -162,10 +161,7 @@ struct PackedRevealArgs {
     const int64_t* shares; uint64_t dimension; uint64_t n_vectors; int64_t* out;
     const int32_t* shares32 = nullptr;   // int32 shares (sda_packed_reconstruct32_dev): replaces `shares`
 };
-// The register reveal kernels take up to kRevealMaxPoints - 1 clerk shares per batch (n + 1 <= 81
-// gives n <= 80 clerks; they keep n_idx + 1 Newton points in registers).
-constexpr int kRevealMaxPoints = 96;
-// Past these sizes (k + t + 1 > 64, n + 1 > 81, more than kRevealMaxPoints - 1 shares) the packed
+// Past these sizes (k + t + 1 > 64, n + 1 > 81, more than kRevealMaxPoints - 1 shares: reveal_plan.h) the packed
 // calls take packed_wide.hip's workspace kernels, up to the engine's domain limits below.
 constexpr uint32_t kWideMaxL = 1024;       // k + t + 1
 constexpr uint32_t kWideMaxN3 = 729;       // n + 1
@@ -173,11 +169,9 @@ constexpr uint32_t kRevealMaxShares = 1023;
 hipError_t launch_packed_generate_wide(const PackedGenArgs& a, uint32_t k, uint32_t t, uint32_t n, uint32_t p,
                                        uint32_t omega_secrets, uint32_t omega_shares, DeviceTable& tab,
                                        hipStream_t s);
-// returns hipErrorInvalidValue for CANONICAL mode with duplicate clerk points.  `log_buf`: device
-// memory of packed_gen_log_bytes() bytes (batches the exact kernel hands to its generic fix-up).
-// t (the privacy threshold) picks the exact kernel: from exactly t + k shares every Newton coefficient is generic
-// and the lazily truncating sign-bit kernel runs; from more, the coefficients past degree t + k are 0 in every
-// batch, which is that kernel's trap, so the kernel with tss' truncation verbatim runs instead.
+// Runs the call as packed_reveal_plan (reveal_plan.h) decides it.  Returns hipErrorInvalidValue for CANONICAL mode
+// with duplicate clerk points: nothing is launched and `tab` keeps its key.  `log_buf`: device memory of
+// packed_gen_log_bytes() bytes (batches the exact kernel hands to its fix-up).
 hipError_t launch_packed_reveal(const PackedRevealArgs& a, const uint64_t* indices, uint32_t n_idx, uint32_t k,
                                 uint32_t t, uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, int mode,
                                 DeviceTable& tab, void* log_buf, hipStream_t s, bool* logged = nullptr);

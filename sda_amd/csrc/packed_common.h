@@ -133,6 +133,37 @@ inline GenTables make_gen_tables(uint32_t L, uint32_t N3, int64_t p, int64_t ws,
     return T;
 }
 
+// The host tables of a reveal from the clerk set `indices` (data independent; same ops as tss), as i64 words at stride
+// m = n_idx + 1: packed_wide.hip uploads `h` as is, packed_reveal.hip packs it into its u32 / Montgomery layout.
+//   pts[m]            the points: the inserted 1 first (points.insert(0, 1)), then omega_shares^(indices[i] + 1)
+//   h[j m + i]        inv[j][i] = mod_inverse(points[i] - points[i-j]), 1 <= j <= i < m (store[i] covers [i-j, i])
+//   h[m m + e m + i]  np[e][i], the signed Newton basis at omega_secrets^(e+1), e < k
+//   duplicate         two of the m points coincide: no Lagrange form, so a CANONICAL reveal is refused
+struct RevealTables { std::vector<int64_t> pts, h; bool duplicate = false; };
+inline RevealTables make_reveal_tables(const uint64_t* indices, uint32_t n_idx, uint32_t k, int64_t p, int64_t ws,
+                                       int64_t wn) {
+    const uint32_t m = n_idx + 1;
+    RevealTables T;
+    T.pts.resize(m);
+    T.h.assign((uint64_t)m * m + (uint64_t)k * m, 0);
+    T.pts[0] = 1;
+    for (uint32_t i = 0; i < n_idx; ++i) T.pts[i + 1] = h_powmod(wn, (uint32_t)(indices[i] + 1), p);
+    for (uint32_t j = 1; j < m; ++j)
+        for (uint32_t i = j; i < m; ++i) T.h[(uint64_t)j * m + i] = h_modinv(h_rem(T.pts[i] - T.pts[i - j], p), p);
+    for (uint32_t a = 0; a < m && !T.duplicate; ++a)
+        for (uint32_t c = a + 1; c < m; ++c)
+            if (T.pts[a] == T.pts[c]) { T.duplicate = true; break; }
+    int64_t* np = T.h.data() + (uint64_t)m * m;
+    for (uint32_t e = 0; e < k; ++e) {
+        const int64_t point = h_powmod(ws, e + 1, p);
+        int64_t v = 1;
+        for (uint32_t i = 0; i < m; ++i) {
+            np[(uint64_t)e * m + i] = v;
+            if (i + 1 < m) v = h_rem(v * h_rem(point - T.pts[i], p), p);
+        }
+    }
+    return T;
+}
 
 // Rust `v % p` from the canonical residue c and the sign word sw of the exact dividend v.
 //   exact (LAZY = false): trunc_rep, 5 VALU ops incl. the c == 0 case (v < 0, v = 0 mod p -> 0);
@@ -140,8 +171,9 @@ inline GenTables make_gen_tables(uint32_t L, uint32_t N3, int64_t p, int64_t ws,
 //   (a nonzero multiple of p: probability ~1/p per value; v == 0 itself is exact).  -p is the only
 //   value outside (-p, p), so a running signed min over the outputs finds it (one v_min3 per two
 //   values, as opaque asm so the compiler cannot reassociate the chain and stretch live ranges);
-//   the batch is then recomputed by the generic exact path (share-gen: logged for the fix-up
-//   kernel; reveal: the lane's generic branch).  LAZY is launched only for p >= kLazyTruncMinP.
+//   the batch is then logged and recomputed by the fix-up kernel launched behind it (share-gen: the generic
+//   exact path; reveal: ZeroTrap below plays this part, and packed_reveal_fixup_wave_kernel / packed_reveal_fixup_kernel
+//   rerun the batch with tss' truncation verbatim).  LAZY is launched only for p >= kLazyTruncMinP.
 #ifndef SDA_TRAP_ASM
 #define SDA_TRAP_ASM 1
 #endif

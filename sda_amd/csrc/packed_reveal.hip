@@ -1,6 +1,4 @@
 // packed_reveal.hip -- packed-Shamir reveal, EXACT (Newton) and CANONICAL (Lagrange).
-#include <algorithm>
-
 #include "packed_common.h"
 #include "xcd.h"
 
@@ -14,15 +12,15 @@ using namespace packed;
 //   [.. , +KMAX*TS)       np_m[e][i]   Montgomery form of canon(np)
 //   [.. , +KMAX*TS)       lam_m[e][i]  Montgomery Lagrange weight of clerk i      (CANONICAL)
 constexpr int TS = 128;
-constexpr int KMAX = 64;
+constexpr int KMAX = kRevealMaxK;
 [[maybe_unused]] constexpr size_t OFF_INV = 0, OFF_INVM = (size_t)TS * TS, OFF_NP = 2 * (size_t)TS * TS,
                  OFF_NPM = OFF_NP + (size_t)KMAX * TS, OFF_LAM = OFF_NPM + (size_t)KMAX * TS,
                  TAB_WORDS = OFF_LAM + (size_t)KMAX * TS;
 
-// One launcher per MM (the padded point count); each is compiled in its own object
-// (Makefile: -DSDA_REVEAL_PART=MM) so the wide instantiations build in parallel.
+// One launcher per MM (the padded point count), each compiled in its own object (Makefile: -DSDA_REVEAL_PART=MM) so the
+// wide instantiations build in parallel.  It launches what the plan names (pl.mm == MM) and re-decides nothing.
 template <int MM>
-hipError_t reveal_launch(int mode, const PackedRevealArgs& a, uint64_t B, uint32_t n_idx, uint32_t k, bool lazy,
+hipError_t reveal_launch(const PackedRevealPlan& pl, const PackedRevealArgs& a, uint32_t n_idx, uint32_t k,
                          const uint32_t* tab, const MontP& M, unsigned int* log, hipStream_t s);
 
 #ifdef SDA_REVEAL_PART
@@ -97,17 +95,37 @@ __device__ __forceinline__ bool load_points(const ST* __restrict__ sh, uint64_t 
     return in_range;
 }
 
+// The Newton triangle over m <= 16 points, unrolled: step(i, j) for j in 1..m, i from m - 1 down to j (tss' in-place
+// descending loop); every table word is a compile-time offset (merged s_loads).  FULL: m == MMAX, so every `i < m`
+// guard is a compile-time constant: no per-step uniform branches, and the table rows load as merged s_load_dwordx16.
+template <int MMAX, bool FULL, class Step>
+__device__ __forceinline__ void newton_triangle(uint32_t m, Step&& step) {
+    static_assert(MMAX <= 16, "unrolled: code size O(MMAX^2)");
+    static_for<1, MMAX>([&](auto j) {
+        if (FULL || (uint32_t)j < m) {
+            static_for<0, MMAX - j>([&](auto ii) {
+                constexpr int i = MMAX - 1 - ii;
+                if (FULL || (uint32_t)i < m) step(std::integral_constant<int, i>{}, (uint32_t)j);
+            });
+        }
+    });
+}
+
+// eval(e) for the secrets e < k <= KU, unrolled: compile-time table offsets (merged scalar loads), no loop overhead.
+template <int KU, class Eval>
+__device__ __forceinline__ void for_each_secret(uint32_t k, Eval&& eval) {
+    static_for<0, KU>([&](auto e) { if ((uint32_t)e < k) eval((uint32_t)e); });
+}
+
 // tss reconstruct of one batch from its m points (shares in (-p, p)): Newton divided differences,
 // then newton_evaluate at omega_secrets^(e+1), e < k; secrets e < lim go to dst[e].  With LAZY
 // (the sign-bit formulation below) returns whether a zero residue appeared, in which case dst may
 // hold garbage and the caller reruns the batch with LAZY = false (tss' `%` verbatim).
-// KU > 0: the evaluation loop over the k <= KU secrets is unrolled (table offsets become
-// compile-time constants: merged scalar loads, no per-secret loop overhead).
-// FULL: m == MMAX, so every `i < m` guard is a compile-time constant: no per-step uniform branches,
-// and the table rows load as merged s_load_dwordx16.
+// KU > 0: the evaluation over the k <= KU secrets is unrolled (for_each_secret); FULL: m == MMAX (newton_triangle).
 //
-// LAZY: the sign-bit formulation.  A value is kept as its canonical residue c and a word whose bit 31
-// is its sign n (value = c - p n; c = 0 implies n = 0).  Then both of tss' truncations are sign logic:
+// LAZY: the sign-bit formulation, launched for up to 16 points and 8 secrets only (packed_reveal_plan).  A value is
+// kept as its canonical residue c and a word whose bit 31 is its sign n (value = c - p n; c = 0 implies n = 0).  Then
+// both of tss' truncations are sign logic:
 //   Newton step  sgn(s_i - s_{i-1}) = MAJ(n_i, ~n_{i-1}, [c_i < c_{i-1}])
 //   fold step    x = acc + t with acc = (pc, n), t = (tc, sgn s xor sgn np):  y = pc + tc in [0, 2p),
 //                sgn(x) = MAJ(n, sgn t, [y < p]) and pc' = y mod p
@@ -133,23 +151,7 @@ __device__ __forceinline__ bool newton_reveal_signbit(FE (&s)[MMAX], uint32_t m,
         s[i] = FE{(int32_t)n, fc};
         zt.note1(fc);
     };
-    if constexpr (MMAX <= 16) {
-        static_for<1, MMAX>([&](auto j) {
-            if (FULL || (uint32_t)j < m) {
-                static_for<0, MMAX - j>([&](auto ii) {
-                    constexpr int i = MMAX - 1 - ii;
-                    if (FULL || (uint32_t)i < m) newton_step(std::integral_constant<int, i>{}, (uint32_t)j);
-                });
-            }
-        });
-    } else {
-        for (uint32_t j = 1; j < m; ++j) {
-            static_for<0, MMAX - 1>([&](auto ii) {
-                constexpr int i = MMAX - 1 - ii;
-                if ((uint32_t)i < m && (uint32_t)i >= j) newton_step(std::integral_constant<int, i>{}, j);
-            });
-        }
-    }
+    newton_triangle<MMAX, FULL>(m, newton_step);
     // newton_evaluate: coefficient 0 is the inserted point's value 0, so the fold starts at i = 1
     auto eval = [&](uint32_t e) {
         const uint32_t* np = tab + OFF_NP + e * TS;
@@ -174,11 +176,7 @@ __device__ __forceinline__ bool newton_reveal_signbit(FE (&s)[MMAX], uint32_t m,
         zt.flush();
         if (e < lim) dst[e] = (int32_t)(pc - (p & (uint32_t)((int32_t)n >> 31)));     // batched.rs:94
     };
-    if constexpr (KU > 0) {
-        static_for<0, KU>([&](auto e) { if ((uint32_t)e < k) eval((uint32_t)e); });
-    } else {
-        for (uint32_t e = 0; e < k; ++e) eval(e);
-    }
+    for_each_secret<KU>(k, eval);
     return zt.bad();
 }
 
@@ -187,7 +185,6 @@ __device__ __forceinline__ bool newton_reveal(FE (&s)[MMAX], uint32_t m, uint32_
                                               const MontP& M, int64_t* dst, uint32_t lim) {
     if constexpr (LAZY) return newton_reveal_signbit<MMAX, KU, FULL>(s, m, k, tab, M, dst, lim);
     const uint32_t p = M.p;
-    Trunc<false> tr;
     // numtheory::compute_newton_coefficients: for j in 1..m { for i in (j..m).rev() {
     //   s[i] = (((s[i] - s[i-1]) % p) * inv(points[i] - points[i-j])) % p } }
     // inv >= 0, so the product has the sign of the exact difference (or is 0).
@@ -195,19 +192,10 @@ __device__ __forceinline__ bool newton_reveal(FE (&s)[MMAX], uint32_t m, uint32_
         const uint32_t dc = s[i].c - s[i - 1].c + p;      // lazy: (0, 2p), REDC input < 2p^2 < pR
         const int32_t sg = __builtin_elementwise_sub_sat(s[i].s, s[i - 1].s);
         const uint32_t fc = montu<false>(tab[OFF_INVM + j * TS + i], dc, M);
-        s[i] = FE{tr(fc, (uint32_t)sg, p), fc};
-        tr.note1(s[i].s);
+        s[i] = FE{trunc_rep(fc, (uint32_t)sg, p), fc};
     };
     if constexpr (MMAX <= 16) {
-        // fully unrolled triangle: every table word is a compile-time offset (merged s_loads)
-        static_for<1, MMAX>([&](auto j) {
-            if (FULL || (uint32_t)j < m) {
-                static_for<0, MMAX - j>([&](auto ii) {
-                    constexpr int i = MMAX - 1 - ii;
-                    if (FULL || (uint32_t)i < m) newton_step(std::integral_constant<int, i>{}, (uint32_t)j);
-                });
-            }
-        });
+        newton_triangle<MMAX, FULL>(m, newton_step);
     } else {
         // wide index sets: runtime j, unrolled i (uniform branches); keeps code size O(MMAX)
         for (uint32_t j = 1; j < m; ++j) {
@@ -225,20 +213,16 @@ __device__ __forceinline__ bool newton_reveal(FE (&s)[MMAX], uint32_t m, uint32_
         static_for<0, MMAX>([&](auto i) {
             if (FULL || (uint32_t)i < m) {
                 const uint32_t tc = montu<false>(npm[i], s[i].c, M);
-                const int32_t ts = tr(tc, (uint32_t)s[i].s ^ np[i], p);     // sign of s * np (np != 0 mod p)
+                const int32_t ts = trunc_rep(tc, (uint32_t)s[i].s ^ np[i], p);     // sign of s * np (np != 0 mod p)
                 const uint32_t ac = addm(acc.c, tc, p);
-                acc = FE{tr(ac, (uint32_t)__builtin_elementwise_add_sat(acc.s, ts), p), ac};
-                tr.note2(ts, acc.s);
+                acc = FE{trunc_rep(ac, (uint32_t)__builtin_elementwise_add_sat(acc.s, ts), p), ac};
             }
         });
         if (e < lim) dst[e] = acc.s;                                                // batched.rs:94
     };
-    if constexpr (KU > 0) {
-        static_for<0, KU>([&](auto e) { if ((uint32_t)e < k) eval((uint32_t)e); });
-    } else {
-        for (uint32_t e = 0; e < k; ++e) eval(e);
-    }
-    return tr.bad(p);
+    if constexpr (KU > 0) for_each_secret<KU>(k, eval);
+    else for (uint32_t e = 0; e < k; ++e) eval(e);
+    return false;                                        // tss' truncation verbatim: nothing to redo
 }
 
 // One lane = one batch.  LAZY (p >= kLazyTruncMinP, exactly t + k shares): the sign-bit path with its zero
@@ -350,13 +334,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     }
 }
 
-// The same fix-up with one WAVE per logged batch (m <= 64 points): lane i holds Newton point i, so each
-// of the m - 1 levels of tss' divided differences is one parallel step (lane i needs only lane i - 1's
-// value of the previous level -- the in-place descending loop reads exactly that), and lane e < k folds
-// newton_evaluate at omega_secrets^(e+1) with the coefficients broadcast from their lanes.  Exact i64
-// arithmetic with truncated `%` throughout (the generic path's), so in-range and raw i64 shares are
-// handled alike.  A trapped batch is a serial latency chain for one lane on the register path (~40 us);
-// spread over the wave it is m + k short steps.
 // Rust `v % p` for |v| < 2^62 (a product of two values in (-p, p), p < 2^31): the quotient from a double
 // product (exact operands, relative error 2^-53, so |q - v/p| < 1) and one signed correction step.
 __device__ __forceinline__ int64_t trem_prod(int32_t a, int32_t b, uint32_t p, double pinv) {
@@ -551,205 +528,157 @@ __global__ __launch_bounds__(256) void packed_reveal32_canon_kernel(const int32_
 
 }  // namespace
 
-// The launches of one bucket for share type ST: the i64 kernels, or their int32 twins by the same rules.
-#define SDA_REVEAL_K(NAME, NAME32, LDS, ...)                                                                   \
-    do {                                                                                                       \
-        if constexpr (sizeof(ST) == 8)                                                                         \
-            hipLaunchKernelGGL((NAME<__VA_ARGS__>), grid, dim3(256), LDS, s, sh, B, a.dimension, a.out, n_idx, k, tab, M, \
-                               SDA_REVEAL_TAIL);                                                               \
-        else                                                                                                   \
-            hipLaunchKernelGGL((NAME32<__VA_ARGS__>), grid, dim3(256), LDS, s, sh, B, a.dimension, a.out, n_idx, k, tab, \
-                               M, SDA_REVEAL_TAIL);                                                            \
-    } while (0)
-#define SDA_REVEAL_EXACT(LDS, ...) SDA_REVEAL_K(packed_reveal_exact_kernel, packed_reveal32_exact_kernel, LDS, __VA_ARGS__)
-#define SDA_REVEAL_CANON(LDS, ...) SDA_REVEAL_K(packed_reveal_canon_kernel, packed_reveal32_canon_kernel, LDS, __VA_ARGS__)
+// The __global__ wrapper for the share type ST of a launch: the i64 kernel, or its int32 twin.
+template <class ST, class K64, class K32>
+static auto for_shares(K64 k64, K32 k32) {
+    if constexpr (sizeof(ST) == 8) return k64; else return k32;
+}
 
+// The launches of one bucket for share type ST.  A reveal takes at least k shares (n_idx >= t + k:
+// sda_packed_reconstruct_dev), so k < MM: the staged kernels without the unrolled evaluation (8 < k <= 16) exist from
+// MM = 16, the unstaged ones (k > 16) from MM = 32, the Lagrange kernels up to MM = 32 and the wave fix-up up to 64
+// points -- every instantiation in the library can be launched (tests/test_packed_matrix_plan.py).
 template <int MM, class ST>
-static hipError_t reveal_launch_t(int mode, const PackedRevealArgs& a, const ST* sh, uint64_t B, uint32_t n_idx,
-                                  uint32_t k, bool lazy, const uint32_t* tab, const MontP& M, unsigned int* log,
-                                  hipStream_t s) {
-    dim3 grid((unsigned)((B + 255) / 256), (unsigned)a.n_vectors);
-    const bool staged = k <= 16;                      // LDS stage: 256 * k * 8 B <= 32 KiB
-    const size_t lds = staged ? (size_t)256 * k * sizeof(int64_t) : 0;
+static hipError_t reveal_launch_t(const PackedRevealPlan& pl, const PackedRevealArgs& a, const ST* sh, uint32_t n_idx,
+                                  uint32_t k, const uint32_t* tab, const MontP& M, unsigned int* log, hipStream_t s) {
+    const uint64_t B = (a.dimension + k - 1) / k;
+    const dim3 grid((unsigned)((B + 255) / 256), (unsigned)a.n_vectors);
+    const size_t lds = pl.staged ? (size_t)256 * k * sizeof(int64_t) : 0;
     const int xcd = xcd_order_enabled() && (uint64_t)grid.x * grid.y < (1ull << 32) ? 1 : 0;
-    if (mode == 0) {
-#define SDA_REVEAL_TAIL log, xcd
-        bool done = false;
-        if constexpr (MM <= 16) {
-            // lazy (launch_packed_reveal): p >= kLazyTruncMinP and exactly t + k shares, so n_idx + 1 = k + t + 1 is a
-            // power of 2: 16 points are this bucket's FULL kernel, 2 or 4 the 8-point bucket's partial one
-            done = staged && k <= 8;
-            if (done && lazy && n_idx + 1 == MM)
-                SDA_REVEAL_EXACT(lds, MM, true, 8, true, true);
-            else if (done && lazy && MM == 8) {
-                if constexpr (MM == 8) SDA_REVEAL_EXACT(lds, MM, true, 8, true);
-            } else if (done)
-                SDA_REVEAL_EXACT(lds, MM, true, 8, false);
-        }
-        // A reveal takes at least k shares (n_idx >= t + k: sda_packed_reconstruct_dev), so k < MM: the staged
-        // kernel without the unrolled evaluation (8 < k <= 16) exists from MM = 16, the unstaged one (k > 16)
-        // from MM = 32 -- every instantiation in the library can be launched (tests/test_packed_matrix_plan.py).
-        if (done) {
-        } else if (staged) {
-            if constexpr (MM > 8)
-                SDA_REVEAL_EXACT(lds, MM, true, 0, false);
-            else
-                return hipErrorInvalidValue;
-        } else {
-            if constexpr (MM > 16)
-                SDA_REVEAL_EXACT(0, MM, false, 0, false);
-            else
-                return hipErrorInvalidValue;
-        }
-#undef SDA_REVEAL_TAIL
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        bool wave = false;
-        if constexpr (MM <= 64) {
-            wave = k <= 64;
-            if (wave) {
-                if constexpr (sizeof(ST) == 8)
-                    hipLaunchKernelGGL((packed_reveal_fixup_wave_kernel<MM>), dim3(1024), dim3(64), 0, s, sh, B,
-                                       a.dimension, a.n_vectors, a.out, n_idx, k, tab, M.p, log);
-                else
-                    hipLaunchKernelGGL((packed_reveal32_fixup_wave_kernel<MM>), dim3(1024), dim3(64), 0, s, sh, B,
-                                       a.dimension, a.n_vectors, a.out, n_idx, k, tab, M.p, log);
-            }
-        }
-        if (!wave)
-            hipLaunchKernelGGL((packed_reveal_fixup_kernel<MM, 0, ST>), dim3(64), dim3(64), 0, s, sh, B,
-                               a.dimension, a.n_vectors, a.out, n_idx, k, tab, M, log);
+    // launches `kernel` when it is the instantiation the plan names; `tail`: (log, xcd), the Lagrange kernels' (xcd)
+    auto run = [&](bool named, auto kernel, auto... tail) {
+        if (named) hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, sh, B, a.dimension, a.out, n_idx, k, tab, M, tail...);
+        return named;
+    };
+    auto exact = [&](auto staged, auto ku, auto lazy, auto full) {
+        return run(pl.staged == staged && pl.ku == ku && pl.lazy == lazy && pl.full == full,
+                   for_shares<ST>(packed_reveal_exact_kernel<MM, staged, ku, lazy, full>,
+                                  packed_reveal32_exact_kernel<MM, staged, ku, lazy, full>), log, xcd);
+    };
+    auto canon = [&](auto staged) {
+        return run(pl.staged == staged,
+                   for_shares<ST>(packed_reveal_canon_kernel<MM, staged>, packed_reveal32_canon_kernel<MM, staged>), xcd);
+    };
+    using T = std::true_type;
+    using F = std::false_type;
+    using K8 = std::integral_constant<int, 8>;
+    using K0 = std::integral_constant<int, 0>;
+    bool found = false;
+    if (pl.mm != MM || (pl.fixup == kRevealFixupWave && MM > 64)) {
+    } else if (pl.mode == 0) {
+        if constexpr (MM <= 16) found = exact(T{}, K8{}, T{}, T{}) || exact(T{}, K8{}, F{}, F{});
+        if constexpr (MM == 8) found = found || exact(T{}, K8{}, T{}, F{});
+        if constexpr (MM > 8) found = found || exact(T{}, K0{}, F{}, F{});
+        if constexpr (MM > 16) found = found || exact(F{}, K0{}, F{}, F{});
     } else if constexpr (MM <= 32) {
-#define SDA_REVEAL_TAIL xcd
-        if (staged)
-            SDA_REVEAL_CANON(lds, MM, true);
-        else if constexpr (MM > 16)                   // k <= n_idx <= MM: unstaged (k > 16) only at MM = 32
-            SDA_REVEAL_CANON(0, MM, false);
-        else
-            return hipErrorInvalidValue;
-#undef SDA_REVEAL_TAIL
-    } else {
-        return hipErrorInvalidValue;                  // launch_packed_reveal runs these as exact + canonical
+        found = canon(T{});
+        if constexpr (MM > 16) found = found || canon(F{});
     }
+    if (!found) return hipErrorInvalidValue;          // not compiled in this bucket: packed_reveal_plan never names it
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || pl.fixup == kRevealFixupNone) return e;
+    if constexpr (MM <= 64) {
+        if (pl.fixup == kRevealFixupWave)
+            hipLaunchKernelGGL((for_shares<ST>(packed_reveal_fixup_wave_kernel<MM>, packed_reveal32_fixup_wave_kernel<MM>)),
+                               dim3(1024), dim3(64), 0, s, sh, B, a.dimension, a.n_vectors, a.out, n_idx, k, tab, M.p, log);
+    }
+    if (pl.fixup == kRevealFixupLane)
+        hipLaunchKernelGGL((packed_reveal_fixup_kernel<MM, 0, ST>), dim3(64), dim3(64), 0, s, sh, B, a.dimension,
+                           a.n_vectors, a.out, n_idx, k, tab, M, log);
     return hipGetLastError();
 }
-#undef SDA_REVEAL_EXACT
-#undef SDA_REVEAL_CANON
-#undef SDA_REVEAL_K
 
 template <int MM>
-hipError_t reveal_launch(int mode, const PackedRevealArgs& a, uint64_t B, uint32_t n_idx, uint32_t k, bool lazy,
+hipError_t reveal_launch(const PackedRevealPlan& pl, const PackedRevealArgs& a, uint32_t n_idx, uint32_t k,
                          const uint32_t* tab, const MontP& M, unsigned int* log, hipStream_t s) {
-    return a.shares32 ? reveal_launch_t<MM>(mode, a, a.shares32, B, n_idx, k, lazy, tab, M, log, s)
-                      : reveal_launch_t<MM>(mode, a, a.shares, B, n_idx, k, lazy, tab, M, log, s);
+    return a.shares32 ? reveal_launch_t<MM>(pl, a, a.shares32, n_idx, k, tab, M, log, s)
+                      : reveal_launch_t<MM>(pl, a, a.shares, n_idx, k, tab, M, log, s);
 }
-template hipError_t reveal_launch<SDA_REVEAL_PART>(int, const PackedRevealArgs&, uint64_t, uint32_t, uint32_t, bool,
-                                                   const uint32_t*, const MontP&, unsigned int*, hipStream_t);
+template hipError_t reveal_launch<SDA_REVEAL_PART>(const PackedRevealPlan&, const PackedRevealArgs&, uint32_t,
+                                                   uint32_t, const uint32_t*, const MontP&, unsigned int*,
+                                                   hipStream_t);
 
 #else  // dispatcher + host tables
 
-// Host precompute of the per-index-set tables (data independent; same ops as tss).
-static void build_reveal_tables(std::vector<uint32_t>& tab, const uint64_t* indices, uint32_t n_idx, uint32_t k,
-                                int64_t p, int64_t ws, int64_t wn, bool want_lagrange, bool* duplicate) {
-    tab.assign(TAB_WORDS, 0);
+// make_reveal_tables' words (packed_common.h) in the register kernels' device layout (u32 / Montgomery, stride TS),
+// with the Lagrange weights of the CANONICAL kernels when asked (distinct points only).
+static std::vector<uint32_t> pack_reveal_tables(const RevealTables& T, uint32_t n_idx, uint32_t k, int64_t p,
+                                                int64_t ws, bool want_lagrange) {
+    std::vector<uint32_t> tab(TAB_WORDS, 0);
     const uint32_t m = n_idx + 1;
-    std::vector<int64_t> pts(m);
-    pts[0] = 1;                                                    // points.insert(0, 1)
-    for (uint32_t i = 0; i < n_idx; ++i) pts[i + 1] = h_powmod(wn, (uint32_t)(indices[i] + 1), p);
     for (uint32_t j = 1; j < m; ++j)
         for (uint32_t i = j; i < m; ++i) {
-            const int64_t diff = h_rem(pts[i] - pts[i - j], p);    // store[i] covers [i-j, i]
-            const int64_t inv = h_modinv(diff, p);
+            const int64_t inv = T.h[(uint64_t)j * m + i];
             tab[OFF_INV + j * TS + i] = (uint32_t)inv;
             tab[OFF_INVM + j * TS + i] = to_mont(inv, p);
         }
-    *duplicate = false;
-    for (uint32_t a = 0; a < m; ++a)
-        for (uint32_t c = a + 1; c < m; ++c)
-            if (pts[a] == pts[c]) *duplicate = true;
     for (uint32_t e = 0; e < k; ++e) {
-        const int64_t point = h_powmod(ws, e + 1, p);
-        int64_t np = 1;
         for (uint32_t i = 0; i < m; ++i) {
+            const int64_t np = T.h[(uint64_t)m * m + (uint64_t)e * m + i];
             tab[OFF_NP + e * TS + i] = (uint32_t)(int32_t)np;
             tab[OFF_NPM + e * TS + i] = to_mont(np, p);
-            if (i + 1 < m) np = h_rem(np * h_rem(point - pts[i], p), p);
         }
-        if (want_lagrange && !*duplicate) {
-            // lambda_i = prod_{j != i+1} (X - x_j) / (x_{i+1} - x_j), over all m points
-            for (uint32_t i = 0; i < n_idx; ++i) {
-                int64_t num = 1, den = 1;
-                for (uint32_t j = 0; j < m; ++j) {
-                    if (j == i + 1) continue;
-                    int64_t a = (point - pts[j]) % p; if (a < 0) a += p;
-                    int64_t d = (pts[i + 1] - pts[j]) % p; if (d < 0) d += p;
-                    num = num * a % p; den = den * d % p;
-                }
-                const int64_t lam = num * h_modinv(den, p) % p;
-                tab[OFF_LAM + e * TS + i] = to_mont(lam, p);
+        if (!want_lagrange) continue;
+        // lambda_i = prod_{j != i+1} (X - x_j) / (x_{i+1} - x_j), over all m points
+        const int64_t point = h_powmod(ws, e + 1, p);
+        for (uint32_t i = 0; i < n_idx; ++i) {
+            int64_t num = 1, den = 1;
+            for (uint32_t j = 0; j < m; ++j) {
+                if (j == i + 1) continue;
+                int64_t a = (point - T.pts[j]) % p; if (a < 0) a += p;
+                int64_t d = (T.pts[i + 1] - T.pts[j]) % p; if (d < 0) d += p;
+                num = num * a % p; den = den * d % p;
             }
+            const int64_t lam = num * h_modinv(den, p) % p;
+            tab[OFF_LAM + e * TS + i] = to_mont(lam, p);
         }
     }
+    return tab;
 }
 
+// The call as packed_reveal_plan decides it: workspace path or table, log reset, kernel and fix-up, canonicalising pass.
 hipError_t launch_packed_reveal(const PackedRevealArgs& a, const uint64_t* indices, uint32_t n_idx, uint32_t k,
                                 uint32_t t, uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, int mode,
                                 DeviceTable& tab, void* log_buf, hipStream_t s, bool* logged) {
     if (logged) *logged = false;
     const uint64_t B = (a.dimension + k - 1) / k;
     if (B == 0 || a.n_vectors == 0) return hipSuccess;
-    if ((mode == 0 ? n_idx + 1 : n_idx) > (uint32_t)kRevealMaxPoints || k > (uint32_t)KMAX)   // packed_wide.hip
+    const PackedRevealPlan pl = packed_reveal_plan(n_idx, k, t, p, mode);
+    if (pl.path == kRevealWorkspace)                      // packed_wide.hip
         return launch_packed_reveal_wide(a, indices, n_idx, k, p, omega_secrets, omega_shares, mode, tab, s);
-    if (mode == 1 && n_idx > 32) {
-        // CANONICAL from more than 32 shares: the exact Newton kernels, then one canonicalising pass -- the same
-        // values by definition (CANONICAL = positive() of the exact reveal, as on the workspace path).  The
-        // Lagrange kernel's 64- and 96-point instantiations needed AGPRs standing in for VGPRs, or scratch
-        // (tests/test_kernel_resources.py; DESIGN.md §4.2 "Register budget at n + 1 = 81").
-        std::vector<int64_t> pts(n_idx);
-        for (uint32_t i = 0; i < n_idx; ++i) pts[i] = h_powmod(omega_shares, (uint32_t)(indices[i] + 1), p);
-        std::sort(pts.begin(), pts.end());
-        if (std::adjacent_find(pts.begin(), pts.end()) != pts.end() || pts[0] == 1)
-            return hipErrorInvalidValue;              // repeated points: no Lagrange form (as the canonical tables)
-        const uint32_t m = n_idx + 1;
-        hipError_t e = m > (uint32_t)kRevealMaxPoints
-                           ? launch_packed_reveal_wide(a, indices, n_idx, k, p, omega_secrets, omega_shares, 1, tab, s)
-                           : launch_packed_reveal(a, indices, n_idx, k, t, p, omega_secrets, omega_shares, 0, tab,
-                                                  log_buf, s, logged);
-        if (e != hipSuccess || m > (uint32_t)kRevealMaxPoints) return e;
-        return launch_mod_canonical(a.out, a.dimension * a.n_vectors, a.out, p, s);
-    }
+    // the table of the mode the kernels run: the detour shares the EXACT call's
     std::vector<uint8_t> key(sizeof(uint32_t) * 6 + sizeof(uint64_t) * n_idx);
-    const uint32_t kv[6] = {n_idx, k, p, omega_secrets, omega_shares, (uint32_t)mode};
+    const uint32_t kv[6] = {n_idx, k, p, omega_secrets, omega_shares, (uint32_t)pl.mode};
     memcpy(key.data(), kv, sizeof(kv));
     memcpy(key.data() + sizeof(kv), indices, sizeof(uint64_t) * n_idx);
+    // Repeated points have no Lagrange form: a CANONICAL call of them is refused, on the detour too.  tab.flags bit 0
+    // keeps make_reveal_tables' verdict with the table, so a CANONICAL call that finds an EXACT call's table sees it.
     if (tab.key != key) {
-        std::vector<uint32_t> host;
-        bool dup = false;
-        build_reveal_tables(host, indices, n_idx, k, p, omega_secrets, omega_shares, mode == 1, &dup);
-        if (mode == 1 && dup) return hipErrorInvalidValue;
+        const RevealTables T = make_reveal_tables(indices, n_idx, k, p, omega_secrets, omega_shares);
+        if (mode == 1 && T.duplicate) return hipErrorInvalidValue;
+        const std::vector<uint32_t> host = pack_reveal_tables(T, n_idx, k, p, omega_secrets, pl.mode == 1);
         hipError_t e = ensure_table(tab, key, host.data(), host.size() * sizeof(uint32_t));
         if (e != hipSuccess) return e;
+        tab.flags = T.duplicate ? 1u : 0u;
+    } else if (mode == 1 && (tab.flags & 1u)) {
+        return hipErrorInvalidValue;
     }
     const MontP M = make_mont(p);
     const uint32_t* dtab = static_cast<const uint32_t*>(tab.dev);
-    const uint32_t m = n_idx + 1;
-    const uint32_t need = mode == 0 ? m : n_idx;
     unsigned int* log = static_cast<unsigned int*>(log_buf);
-    hipError_t e = hipSuccess;
-    if (mode == 0 && (e = hipMemsetAsync(log, 0, sizeof(unsigned int), s)) != hipSuccess) return e;
-    if (logged) *logged = mode == 0;
-    // The sign-bit kernels are exact unless a residue on the way is 0 (ZeroTrap).  From more than t + k shares the
-    // divided differences past the polynomial's degree are 0 in EVERY batch: such a launch would log all of its
-    // batches and the fix-up would recompute them (right, and slower than never taking the lazy kernel).
-    const bool lazy = p >= kLazyTruncMinP && n_idx == k + t;
-    if (need <= 8) e = reveal_launch<8>(mode, a, B, n_idx, k, lazy, dtab, M, log, s);
-    else if (need <= 16) e = reveal_launch<16>(mode, a, B, n_idx, k, lazy, dtab, M, log, s);
-    else if (need <= 32) e = reveal_launch<32>(mode, a, B, n_idx, k, lazy, dtab, M, log, s);
-    else if (need <= 64) e = reveal_launch<64>(mode, a, B, n_idx, k, lazy, dtab, M, log, s);
-    else if (need <= kRevealMaxPoints)
-        e = reveal_launch<kRevealMaxPoints>(mode, a, B, n_idx, k, lazy, dtab, M, log, s);
-    else return hipErrorInvalidValue;
-    return e;
+    hipError_t e = pl.logged ? hipMemsetAsync(log, 0, sizeof(unsigned int), s) : hipSuccess;
+    if (e != hipSuccess) return e;
+    if (logged) *logged = pl.logged;
+    switch (pl.mm) {                                      // one object per bucket: Makefile REVEAL_PARTS
+        case 8: e = reveal_launch<8>(pl, a, n_idx, k, dtab, M, log, s); break;
+        case 16: e = reveal_launch<16>(pl, a, n_idx, k, dtab, M, log, s); break;
+        case 32: e = reveal_launch<32>(pl, a, n_idx, k, dtab, M, log, s); break;
+        case 64: e = reveal_launch<64>(pl, a, n_idx, k, dtab, M, log, s); break;
+        case kRevealMaxPoints: e = reveal_launch<kRevealMaxPoints>(pl, a, n_idx, k, dtab, M, log, s); break;
+        default: e = hipErrorInvalidValue;
+    }
+    if (e != hipSuccess || pl.path != kRevealDetour) return e;
+    return launch_mod_canonical(a.out, a.dimension * a.n_vectors, a.out, p, s);
 }
 
 #endif  // SDA_REVEAL_PART

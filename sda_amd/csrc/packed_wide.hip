@@ -118,8 +118,8 @@ __global__ __launch_bounds__(256) void packed_gen32_wide_kernel(const int64_t* _
 
 // Wide reveal: tss' Newton divided differences over the m = n_idx + 1 points (the inserted (1, 0)
 // first), then newton_evaluate at omega_secrets^(e+1).  inv[j m + i] = mod_inverse(points[i] -
-// points[i-j]); np[e m + i] = the signed Newton basis at omega_secrets^(e+1) (as packed_reveal.hip's
-// host tables, stride m).  CANONICAL: the exact value's canonical residue (= positive()).
+// points[i-j]); np[e m + i] = the signed Newton basis at omega_secrets^(e+1) (make_reveal_tables'
+// words, packed_common.h).  CANONICAL: the exact value's canonical residue (= positive()).
 // (ST: the share type, i64 or int32 sign-extended as it is read.)
 template <class ST>
 __device__ __forceinline__ void reveal_wide_body(const ST* __restrict__ shares, uint64_t B, uint64_t D, uint64_t n_vec,
@@ -242,28 +242,10 @@ hipError_t launch_packed_reveal_wide(const PackedRevealArgs& a, const uint64_t* 
     memcpy(key.data(), kv, sizeof(kv));
     memcpy(key.data() + sizeof(kv), indices, sizeof(uint64_t) * n_idx);
     if (tab.key != key) {
-        // packed_reveal.hip's host tables (same ops as tss), stride m: inv [m][m], np [k][m]
-        std::vector<int64_t> h((uint64_t)m * m + (uint64_t)k * m, 0);
-        std::vector<int64_t> pts(m);
-        pts[0] = 1;                                                    // points.insert(0, 1)
-        for (uint32_t i = 0; i < n_idx; ++i) pts[i + 1] = h_powmod(omega_shares, (uint32_t)(indices[i] + 1), P);
-        bool dup = false;
-        for (uint32_t j = 1; j < m; ++j)
-            for (uint32_t i = j; i < m; ++i) h[(uint64_t)j * m + i] = h_modinv(h_rem(pts[i] - pts[i - j], P), P);
-        for (uint32_t x = 0; x < m && !dup; ++x)
-            for (uint32_t y = x + 1; y < m; ++y)
-                if (pts[x] == pts[y]) { dup = true; break; }
-        if (mode == 1 && dup) return hipErrorInvalidValue;            // as the Lagrange table refuses them
-        int64_t* np = h.data() + (uint64_t)m * m;
-        for (uint32_t e = 0; e < k; ++e) {
-            const int64_t point = h_powmod(omega_secrets, e + 1, P);
-            int64_t v = 1;
-            for (uint32_t i = 0; i < m; ++i) {
-                np[(uint64_t)e * m + i] = v;
-                if (i + 1 < m) v = h_rem(v * h_rem(point - pts[i], P), P);
-            }
-        }
-        hipError_t e = ensure_table(tab, key, h.data(), h.size() * sizeof(int64_t));
+        // inv [m][m], np [k][m] at stride m: make_reveal_tables' words as they are
+        const RevealTables T = make_reveal_tables(indices, n_idx, k, P, omega_secrets, omega_shares);
+        if (mode == 1 && T.duplicate) return hipErrorInvalidValue;    // as the Lagrange table refuses them
+        hipError_t e = ensure_table(tab, key, T.h.data(), T.h.size() * sizeof(int64_t));
         if (e != hipSuccess) return e;
     }
     const uint64_t lanes = wide_lanes(B * a.n_vectors, m);

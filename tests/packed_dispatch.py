@@ -9,18 +9,18 @@ tests/test_gpu_packed_matrix.py against the instantiations in the built library.
 Restated here, each next to the line of the product it mirrors:
   gen_register_path, kLazyTruncMinP, make_gen_tables' big2 / big3 <= 4096 rule (the sign-bit flag), packed_gen_plan's
   pair-store (even B, 16-byte aligned out) rule and register / workspace choice, gen_launch_t's variant choice,
-  the reveal's 8/16/32/64/96 point buckets, its FULL / KU / STAGED choices
-  and its lazy-only-at-the-threshold rule,
-  the canonical n_idx > 32 detour, wide_lanes, and which batches a launch logs for its fix-up kernel.
+  packed_reveal_plan (reveal_plan.h): the reveal's workspace / register / detour paths, its 8/16/32/64/96 point
+  buckets, its FULL / KU / STAGED choices and its lazy-only-at-the-threshold rule,
+  wide_lanes, and which batches a launch logs for its fix-up kernel.
 """
 import math
 
 EXACT, CANONICAL = 0, 1                    # SDA_REVEAL_EXACT / SDA_REVEAL_CANONICAL
 
-LAZY_TRUNC_MIN_P = 1 << 24                 # kernels.h: kLazyTruncMinP
+LAZY_TRUNC_MIN_P = 1 << 24                 # reveal_plan.h: kLazyTruncMinP
 GEN_LOG_CAP = 1 << 16                      # kernels.h: kGenLogCap
-REVEAL_MAX_POINTS = 96                     # kernels.h: kRevealMaxPoints
-REVEAL_KMAX = 64                           # packed_reveal.hip: KMAX
+REVEAL_MAX_POINTS = 96                     # reveal_plan.h: kRevealMaxPoints
+REVEAL_KMAX = 64                           # reveal_plan.h: kRevealMaxK
 SIGNBIT_MAX_BIG = 4096                     # packed_gen.hip: tab.flags
 GEN_PARTS = {3: (2,), 9: (2, 4, 8), 27: (2, 4, 8, 16), 81: (2, 4, 8, 16, 32, 64)}    # Makefile: GEN_PARTS
 REVEAL_PARTS = (8, 16, 32, 64, 96)         # Makefile: REVEAL_PARTS
@@ -100,19 +100,19 @@ def reveal_bucket(need):
 
 
 def reveal_kernel(sch, n_idx, k, mode):
-    """The reveal kernel of one launch from n_idx shares.  CANONICAL from more than 32 shares runs the exact
-    kernel named here followed by launch_mod_canonical (reveal_takes_detour)."""
+    """The reveal kernel of one launch from n_idx shares: packed_reveal_plan (sda_amd/csrc/reveal_plan.h), restated;
+    tests/test_reveal_plan.py holds the two against each other on the CPU.  CANONICAL from more than 32 shares runs
+    the exact kernel named here followed by launch_mod_canonical (reveal_takes_detour)."""
     p = sch.prime_modulus
-    need = n_idx + 1 if mode == EXACT else n_idx
-    if need > REVEAL_MAX_POINTS or k > REVEAL_KMAX:
+    if n_idx + 1 > REVEAL_MAX_POINTS or k > REVEAL_KMAX:            # kRevealWorkspace
         return "wide"
-    if mode == CANONICAL and n_idx > 32:
-        return "wide" if n_idx + 1 > REVEAL_MAX_POINTS else reveal_kernel(sch, n_idx, k, EXACT)
-    mm = reveal_bucket(need)
+    if reveal_takes_detour(n_idx, k, mode):                         # kRevealDetour: the plan's mode becomes EXACT
+        mode = EXACT
+    mm = reveal_bucket(n_idx + 1 if mode == EXACT else n_idx)       # the Lagrange kernels keep the shares only
     staged = k <= 16
     if mode == CANONICAL:
         return f"packed_reveal_canon_kernel<{mm}, {_b(staged)}>"
-    if mm <= 16 and k <= 8:
+    if mm <= 16 and k <= 8:                                         # ku = 8
         # lazy only from exactly t + k shares (from more, the top Newton coefficients are 0 in every batch: the
         # lazy kernel's trap); then n_idx + 1 = k + t + 1 is a power of 2: 16 is FULL, 2 and 4 sit in the 8 bucket
         lazy = p >= LAZY_TRUNC_MIN_P and n_idx == k + sch.privacy_threshold()
@@ -122,8 +122,9 @@ def reveal_kernel(sch, n_idx, k, mode):
     return f"packed_reveal_exact_kernel<{mm}, {_b(staged)}, 0, false, false>"
 
 
-def reveal_takes_detour(n_idx, mode):
-    return mode == CANONICAL and 32 < n_idx < REVEAL_MAX_POINTS
+def reveal_takes_detour(n_idx, k, mode):
+    """packed_reveal_plan: kRevealDetour -- the exact register kernels, then launch_mod_canonical."""
+    return mode == CANONICAL and 32 < n_idx < REVEAL_MAX_POINTS and k <= REVEAL_KMAX
 
 
 def reveal_kernel_is_lazy(name):
@@ -155,7 +156,7 @@ def gen_fixup_count(kernel, planted, B):
 
 
 def reveal_fixup_count(kernel, planted):
-    """Batches a reveal launch logs: the exact kernels log exactly the out-of-range batches; the canonical
+    """Batches a reveal launch logs (PackedRevealPlan::logged): the exact kernels log exactly the out-of-range batches; the canonical
     Lagrange kernels reduce raw shares in the lane and the workspace kernel takes any i64 -- neither logs."""
     return len(set(planted)) if kernel.startswith("packed_reveal_exact_kernel<") else 0
 

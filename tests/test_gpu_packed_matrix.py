@@ -303,6 +303,48 @@ def test_workspace_reveal_second_pass(engine):
         assert (host[-2:] == SENTINEL).all()
 
 
+@pytest.mark.parametrize("width", [64, 32], ids=["i64", "int32"])
+def test_cached_table_keeps_the_duplicate_refusal(engine, width):
+    """A CANONICAL reveal of repeated clerk indices is refused even when an EXACT reveal of the same indices has
+    just built and cached the table it would use -- from 40 shares (the detour shares the EXACT call's table, and
+    takes the verdict kept with it) and from 7 (the Lagrange kernels' own table).  The refused call launches
+    nothing, and the CANONICAL reveal of distinct indices that follows is the oracle's."""
+    import torch
+    from sda_amd import engine as E
+    O = _O()
+    sch = PM.scheme_for(3, 4, 80)                           # n + 1 = 81, k + t + 1 = 8
+    p, k, n = sch.prime_modulus, sch.secret_count, sch.share_count
+    D, nv = 8, 2                                            # B = 3 with a padded tail batch
+    B = (D + k - 1) // k
+    assert B == 3 and D % k
+    rng = np.random.default_rng(_seed(sch, D, width))
+    reveal = engine.packed_reconstruct_dev if width == 64 else engine.packed_reconstruct32_dev
+    for n_idx in (40, 7):
+        assert PD.reveal_takes_detour(n_idx, k, PD.CANONICAL) == (n_idx == 40)
+        idx = rng.permutation(n)[:n_idx]
+        dup = idx.copy()
+        dup[n_idx - 2] = dup[1]
+        shares = rng.integers(-(p - 1), p, size=(nv, n_idx, B), dtype=np.int64)
+        dsh = _dev(torch, shares if width == 64 else shares.astype(np.int32))
+        buf = torch.full((nv * D + 2,), SENTINEL, dtype=torch.int64, device="cuda")
+        reveal(sch, D, dup.tolist(), nv, dsh.data_ptr(), buf.data_ptr(), mode=PD.EXACT)        # SDA_OK
+        buf.fill_(SENTINEL)
+        with pytest.raises(E.SdaError) as err:
+            reveal(sch, D, dup.tolist(), nv, dsh.data_ptr(), buf.data_ptr(), mode=PD.CANONICAL)
+        assert err.value.status == E.ERR_UNSUPPORTED
+        assert "canonical reveal needs distinct clerk indices" in str(err.value)
+        torch.cuda.synchronize()
+        assert (buf.cpu().numpy() == SENTINEL).all(), "the refused call wrote"
+        reveal(sch, D, idx.tolist(), nv, dsh.data_ptr(), buf.data_ptr(), mode=PD.CANONICAL)
+        torch.cuda.synchronize()
+        host = buf.cpu().numpy()
+        for v in range(nv):
+            rc, exp = O.packed_reconstruct(_pp(O, sch), D, idx, shares[v])
+            assert rc == 0
+            assert_same(host[v * D:(v + 1) * D], np.mod(exp, p), f"from {n_idx}, vector {v}")
+        assert (host[nv * D:] == SENTINEL).all(), "wrote outside the output"
+
+
 def test_fixup_count_before_any_packed_launch():
     """A fresh handle reports 0."""
     from sda_amd import Engine
