@@ -260,6 +260,21 @@ extern "C" {
                                              mode: i32, shares_out: *mut i32, payload: *mut u8, payload_cap: u64,
                                              payload_row_bytes: *mut u64, stream: *mut c_void) -> SdaStatus;
 
+    // ---- recipient job: the recipient pipeline from the opened payloads ----
+    pub fn sda_recipient_job(h: *mut SdaEngine, ms: *const SdaMaskingScheme, mask_blobs: *const *const u8,
+                             mask_lens: *const u64, n_masks: u64, ss: *const SdaSharingScheme, dimension: u64,
+                             indices: *const u64, clerk_blobs: *const *const u8, clerk_lens: *const u64, n_idx: u64,
+                             output_modulus: i64, mode: i32, out: *mut i64, out_cap: u64, out_len: *mut u64)
+        -> SdaStatus;
+    pub fn sda_recipient_job_dev(h: *mut SdaEngine, ms: *const SdaMaskingScheme, mask: *const i64, mask_len: u64,
+                                 seed_bytes: *const u8, seed_off: *const u64, n_seeds: u64,
+                                 ss: *const SdaSharingScheme, dimension: u64, indices: *const u64,
+                                 clerk_bytes: *const u8, clerk_off: *const u64, n_idx: u64, output_modulus: i64,
+                                 mode: i32, out: *mut i64, out_cap: u64, out_len: *mut u64, stream: *mut c_void)
+        -> SdaStatus;
+    pub fn sda_recipient_job_last_launch(h: *mut SdaEngine, mask_route: *mut u32, share_route: *mut u32,
+                                         seeds_decoded: *mut u32) -> SdaStatus;
+
     // ---- synthetic benchmark input ----
     pub fn sda_synth_fill_dev(h: *mut SdaEngine, dst: *mut i64, rows: u64, cols: u64, seed: u64, lo: i64, hi: i64,
                               stream: *mut c_void) -> SdaStatus;

@@ -753,6 +753,78 @@ sda_status sda_participant_share32_keyed_dev(sda_engine* h, const sda_masking_sc
                                              int32_t mode, int32_t* shares_out, uint8_t* payload,
                                              uint64_t payload_cap, uint64_t* payload_row_bytes, void* stream);
 
+/* ---------------- recipient job: the recipient pipeline from the opened payloads ----------------
+ * receive.rs:98-157 + positive() with the decode of every mask blob and clerk result (Decryptor::decrypt,
+ * sodium.rs:82-90, receive.rs:101-146) done by the engine as well: the recipient hands over the opened payload
+ * bytes, as the clerk does to sda_clerk_job.
+ *
+ * CONTRACT.  For any input, sda_recipient_job returns what sda_recipient_reveal returns when it is called with each
+ * blob's sda_varint_decode output as the corresponding row: the status, the reference's message, *out_len and every
+ * output value.  Blobs of different lengths are the normal case, and sda_recipient_reveal's rules for ragged rows
+ * apply as they stand: Full mask blobs that decode to different lengths fail with full.rs:43's assertion
+ * (SDA_ERR_PRECONDITION; row 0's `% 0` panic comes first), Additive clerk results of different lengths with
+ * "Mismatching dimension" (4), PackedShamir clerk results are read over [0, B), a ChaCha seed is its first 8
+ * values `as u32`, zero padded, and with no masking every blob must be empty.  A failing call writes nothing to
+ * out and leaves every *_last_launch record of the handle as it was. */
+
+/* Host form.  mask_blobs[i] (mask_lens[i] bytes) is participation i's opened mask payload -- a Full mask or a
+ * ChaCha seed --, clerk_blobs[i] (clerk_lens[i] bytes) the opened result of clerk indices[i].
+ *   Full masks stream through the decode -> combine of sda_clerk_decode_combine (full.rs:38-51 is combiner.rs:16-28's
+ *   recurrence), a group of blobs in HBM at a time, so a mask set larger than HBM runs; seed blobs and clerk
+ *   results are uploaded once.  On a multi-device handle the ChaCha mask combine is split over the devices as
+ *   sda_recipient_reveal splits it (the decoded key words, 32 bytes a seed, are read back for that), and
+ *   sda_recipient_last_launch then reports mask_kind 4; the rest runs on ordinals[0]. */
+sda_status sda_recipient_job(sda_engine* h, const sda_masking_scheme* ms,
+                             const uint8_t* const* mask_blobs, const uint64_t* mask_lens, uint64_t n_masks,
+                             const sda_sharing_scheme* ss, uint64_t dimension, const uint64_t* indices,
+                             const uint8_t* const* clerk_blobs, const uint64_t* clerk_lens, uint64_t n_idx,
+                             int64_t output_modulus, int32_t mode,
+                             int64_t* out, uint64_t out_cap, uint64_t* out_len);
+
+/* Device form.  (seed_bytes, seed_off, n_seeds) and (clerk_bytes, clerk_off, n_idx) are laid out as
+ * sda_clerk_decode_combine_dev takes its (bytes, blob_off, n_blobs): device bytes, 16-byte aligned and readable 16
+ * bytes past the last blob, HOST offsets [n + 1], non-decreasing.
+ *   Full masking: mask (device) is the already combined mask of mask_len values, read as it is.  That is the state
+ *     sda_clerk_job_dev(h, ms->modulus, ..., payload = NULL) leaves after folding the mask payloads in any number
+ *     of tiles (full.rs:38-51 is the clerk's recurrence), so a mask set larger than HBM is folded tile by tile and
+ *     revealed with one call; SDA_ERR_WRONG_DIMENSION (3) from that fold stands for full.rs:43's assertion.
+ *     mask_len == 0 is the empty mask of zero participations.  The unmask asserts mask_len == the output length,
+ *     as sda_recipient_reveal_dev does.  The seed arguments are ignored.
+ *   ChaCha masking: the seeds arrive as n_seeds blobs and their key words are decoded on the device; mask and
+ *     mask_len are ignored.
+ *   No masking: every blob passed must be empty.
+ *   Additive clerk results are reconstructed by the clerk's decode -> combine straight into the pipeline's scratch
+ *   (no [n_idx][D] matrix of i64 rows exists); PackedShamir results are counted, decoded into i64 rows of the
+ *   longest result's length in handle scratch and revealed as sda_recipient_reveal_dev reveals them.
+ *   sda_codec_last_launch, sda_combine_last_launch, sda_chacha_last_launch and sda_recipient_last_launch report
+ *   what that reused code ran.
+ * The call reads mask and the byte buffers only, and a failing call leaves all caller memory untouched.  It makes
+ * one host wait before the reveal and the unmask are queued (the decode -> combine's, or the count pass's); with
+ * ChaCha masking it drains its stream before returning, as sda_recipient_reveal_dev does.  Runs on ordinals[0] of
+ * a multi-device handle; stream ordering on the handle is that of every _dev call. */
+sda_status sda_recipient_job_dev(sda_engine* h, const sda_masking_scheme* ms,
+                                 const int64_t* mask, uint64_t mask_len,
+                                 const uint8_t* seed_bytes, const uint64_t* seed_off, uint64_t n_seeds,
+                                 const sda_sharing_scheme* ss, uint64_t dimension, const uint64_t* indices,
+                                 const uint8_t* clerk_bytes, const uint64_t* clerk_off, uint64_t n_idx,
+                                 int64_t output_modulus, int32_t mode,
+                                 int64_t* out, uint64_t out_cap, uint64_t* out_len, void* stream);
+
+/* Diagnostic (read-only): where the handle's most recent sda_recipient_job / sda_recipient_job_dev took its inputs
+ * from.  Written when such a call returns SDA_OK with a non-empty output, as sda_recipient_last_launch is; before
+ * any such call every field is 0.
+ *   mask_route     0  no masking
+ *                  1  Full, the caller's combined mask (sda_recipient_job_dev)
+ *                  2  Full, the blobs streamed through decode -> combine (sda_recipient_job)
+ *                  3  ChaCha, the seeds decoded on the device
+ *                  4  as 3, then the mask combine split over the handle's devices
+ *   share_route    1  Additive: decode -> combine
+ *                  2  PackedShamir: count pass + i64 rows
+ *   seeds_decoded  the blobs the seed kernel handled
+ * A host-side record: nothing is waited for or copied.  No pointer may be NULL. */
+sda_status sda_recipient_job_last_launch(sda_engine* h, uint32_t* mask_route, uint32_t* share_route,
+                                         uint32_t* seeds_decoded);
+
 /* Synthetic benchmark input: dst[r*cols + c] = lo + splitmix64(seed, r, c) % (hi - lo). */
 sda_status sda_synth_fill_dev(sda_engine* h, int64_t* dst, uint64_t rows, uint64_t cols,
                               uint64_t seed, int64_t lo, int64_t hi, void* stream);

@@ -38,12 +38,13 @@ static sda_status encode_dev(sda_engine* h, const T* vals, uint64_t rows, uint64
     return ok();
 }
 
-namespace {
+// Shared with the recipient job (engine_pipelines.cpp): declared in engine_internal.h.
+namespace sda_host {
 
 // Plan + count N device-resident blobs; counts[n] on the host.
 sda_status codec_count(sda_engine* h, const uint8_t* bytes, const uint64_t* blob_off, uint64_t n_blobs,
                        sda::VarintPlan* plan, uint64_t* counts, bool* irregular, hipStream_t st,
-                       bool sub_counts = false, bool* long_any = nullptr) {
+                       bool sub_counts, bool* long_any) {
     if (((uintptr_t)bytes & 15) != 0) return fail(SDA_ERR_INVALID_ARGUMENT, "byte buffer must be 16-byte aligned");
     for (uint64_t b = 0; b < n_blobs; ++b)
         if (blob_off[b + 1] < blob_off[b]) return fail(SDA_ERR_INVALID_ARGUMENT, "blob offsets must be non-decreasing");
@@ -56,22 +57,13 @@ sda_status codec_count(sda_engine* h, const uint8_t* bytes, const uint64_t* blob
     return SDA_OK;
 }
 
-// What sda_clerk_job_dev adds to the decode -> combine (job == nullptr: sda_clerk_decode_combine_dev exactly).
-struct ClerkJob {
-    uint64_t first;            // participations folded by earlier calls; > 0: a continuing call
-    uint64_t prior_dim;        // the dimension they established (continuing calls)
-    uint8_t* payload;          // device; nullptr: no encode
-    uint64_t payload_cap;
-    uint64_t* payload_len;     // host; non-NULL when payload is
-};
-
 // decode + combiner.rs:16-28 over device-resident blobs; out (device) gets out_len = count of blob 0.  With a job:
 // out is the job's state, continued in place from prior_dim columns when job->first > 0, and the result is encoded
 // into job->payload -- behind the combine, before the call's one wait, on the slot path (route 1), else once the
 // counts are known (route 2).
 sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const uint64_t* blob_off, uint64_t n_blobs,
                           int64_t* out, uint64_t out_cap, uint64_t* out_len, hipStream_t st,
-                          const ClerkJob* job = nullptr) {
+                          const ClerkJob* job) {
     const bool cont = job && job->first > 0;
     const uint64_t prior = cont ? job->prior_dim : 0, first = cont ? job->first : 0;
     *out_len = prior;
@@ -260,7 +252,7 @@ sda_status upload_blobs(sda_engine* h, const uint8_t* const* blobs, const uint64
     return SDA_OK;
 }
 
-}  // namespace
+}  // namespace sda_host
 
 extern "C" {
 

@@ -52,7 +52,8 @@ struct sda_engine {
     size_t codec_work_bytes = 0;
     void* codec_mat = nullptr;    // decoded [N][len] matrix of the clerk decode+combine path
     size_t codec_mat_bytes = 0;
-    void* job_work = nullptr;     // sda_clerk_job_dev: the queued encode's workspace (codec_work still holds the decode's)
+    void* job_work = nullptr;     // sda_clerk_job_dev: the queued encode's workspace (codec_work still holds the decode's);
+                                  // a recipient job: the decoded ChaCha seed words and the seed blobs' offsets
     size_t job_work_bytes = 0;
     void* pipe = nullptr;         // recipient / participant pipeline scratch (mask, masked, compacted shares)
     size_t pipe_bytes = 0;
@@ -89,6 +90,11 @@ struct sda_engine {
     struct ParticipantLaunchInfo {
         uint32_t mask_route = 0, share_route = 0, passes = 0;
     } participant_last;
+    // sda_recipient_job_last_launch: where the last recipient job's mask and clerk results came from, written as
+    // recipient_last is
+    struct RecipientJobLaunchInfo {
+        uint32_t mask_route = 0, share_route = 0, seeds_decoded = 0;
+    } recipient_job_last;
     // streaming host path (host rows -> HBM in row tiles, engine_host.cpp): pinned staging and device
     // tiles, double buffered, and a copy stream so a tile's upload overlaps the previous tile's combine
     hipStream_t copy_stream = nullptr;
@@ -226,6 +232,30 @@ sda_status packed_reveal(sda_engine* h, const sda_sharing_scheme* s, const sda::
 template <typename T>
 sda_status encode_rows(sda_engine* h, const T* vals, uint64_t rows, uint64_t len, uint64_t stride, uint8_t* dst,
                        uint64_t dst_cap, uint64_t* row_bytes, hipStream_t st, const char* cap_name);
+
+// ---------------- payload decoder (engine_codec.cpp) ----------------
+// Plan + count n_blobs device-resident blobs (the argument checks of every `_dev` byte buffer, then one wait);
+// counts[n_blobs] on the host.
+sda_status codec_count(sda_engine* h, const uint8_t* bytes, const uint64_t* blob_off, uint64_t n_blobs,
+                       sda::VarintPlan* plan, uint64_t* counts, bool* irregular, hipStream_t st,
+                       bool sub_counts = false, bool* long_any = nullptr);
+// What sda_clerk_job_dev adds to the decode -> combine (job == nullptr: sda_clerk_decode_combine_dev exactly).
+struct ClerkJob {
+    uint64_t first;            // participations folded by earlier calls; > 0: a continuing call
+    uint64_t prior_dim;        // the dimension they established (continuing calls)
+    uint8_t* payload;          // device; nullptr: no encode
+    uint64_t payload_cap;
+    uint64_t* payload_len;     // host; non-NULL when payload is
+};
+// decode + combiner.rs:16-28 over device-resident blobs into out (device); *out_len = the count of blob 0.  One
+// host wait.  The recipient job reconstructs an Additive scheme's clerk results with it (additive.rs:56-72 is the
+// same recurrence).
+sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const uint64_t* blob_off, uint64_t n_blobs,
+                          int64_t* out, uint64_t out_cap, uint64_t* out_len, hipStream_t st,
+                          const ClerkJob* job = nullptr);
+// host blobs concatenated into a 16-byte aligned, padded device buffer taken from `a`; (*off)[n + 1]
+sda_status upload_blobs(sda_engine* h, const uint8_t* const* blobs, const uint64_t* lens, uint64_t n, DevArena* a,
+                        uint8_t** dev, std::vector<uint64_t>* off);
 
 // ---------------- HBM allocator (hbm.cpp) ----------------
 bool hbm_owned(void* p);              // p was returned by sda_hbm_alloc and not freed

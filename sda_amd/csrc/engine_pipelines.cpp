@@ -31,21 +31,117 @@ sda_status mask_combine_checks(const sda_masking_scheme* ms, uint64_t n_masks, u
     return SDA_OK;
 }
 
-// receive.rs:80-157 + :14-20 on device-resident inputs (see sda_recipient_reveal_dev).
+// The payload source of a recipient job (sda_recipient_job / sda_recipient_job_dev): opened payload bytes on the
+// device, laid out as sda_clerk_decode_combine_dev takes them, that recipient_pipeline reads in place of mask_in
+// and of shares.  Each part stands alone (the host form on a multi-device handle combines its ChaCha mask first and
+// passes the clerk results only).
+struct RecipientPayloads {
+    const int64_t* combined_mask = nullptr;   // Full: the folded mask, mask_width values as one row, used as it is
+    const uint8_t* seed_bytes = nullptr;      // ChaCha: the n_masks seed blobs (mask_width = sda::kSeedWords)
+    const uint64_t* seed_off = nullptr;
+    const uint8_t* clerk_bytes = nullptr;     // the n_idx clerk results; share_len is then what they decode to
+    const uint64_t* clerk_off = nullptr;
+    bool shares = false;                      // the clerk results come from clerk_bytes (n_idx may be 0)
+};
+
+// The checks every `_dev` call makes of a (bytes, blob_off) pair before anything reads it.
+sda_status check_blob_buffer(const uint8_t* bytes, const uint64_t* blob_off, uint64_t n_blobs) {
+    if (n_blobs == 0) return SDA_OK;
+    if (((uintptr_t)bytes & 15) != 0) return fail(SDA_ERR_INVALID_ARGUMENT, "byte buffer must be 16-byte aligned");
+    for (uint64_t b = 0; b < n_blobs; ++b)
+        if (blob_off[b + 1] < blob_off[b]) return fail(SDA_ERR_INVALID_ARGUMENT, "blob offsets must be non-decreasing");
+    return SDA_OK;
+}
+
+// Every *_last_launch record a recipient call can write, on every device of the handle: a call that fails after
+// the code it reuses has run puts them back.
+struct LaunchRecords {
+    struct One {
+        sda::ChachaLaunchInfo chacha;
+        bool chacha_split;
+        sda::CodecLaunchInfo codec;
+        sda::CombineLaunchInfo combine;
+        sda_engine::RecipientLaunchInfo recipient;
+        sda_engine::RecipientJobLaunchInfo job;
+    };
+    std::vector<One> saved;
+    explicit LaunchRecords(sda_engine* h) {
+        for (size_t g = 0; g < n_devices(h); ++g) {
+            const sda_engine* d = dev_of(h, g);
+            saved.push_back({d->chacha_last, d->chacha_split, d->codec_last, d->combine_last, d->recipient_last,
+                             d->recipient_job_last});
+        }
+    }
+    void restore(sda_engine* h) const {
+        for (size_t g = 0; g < saved.size(); ++g) {
+            sda_engine* d = dev_of(h, g);
+            d->chacha_last = saved[g].chacha;
+            d->chacha_split = saved[g].chacha_split;
+            d->codec_last = saved[g].codec;
+            d->combine_last = saved[g].combine;
+            d->recipient_last = saved[g].recipient;
+            d->recipient_job_last = saved[g].job;
+        }
+    }
+};
+
+// receive.rs:80-157 + :14-20 on device-resident inputs (see sda_recipient_reveal_dev); with `pay`, on the opened
+// payloads (see sda_recipient_job_dev).
 sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const void* mask_in, uint64_t n_masks,
                               uint64_t mask_width, const sda_sharing_scheme* ss, uint64_t dimension,
                               const uint64_t* indices, const int64_t* shares, uint64_t n_idx, uint64_t share_len,
                               int64_t output_modulus, int32_t mode, int64_t* out, uint64_t out_cap,
-                              uint64_t* out_len, hipStream_t st) {
+                              uint64_t* out_len, hipStream_t st, const RecipientPayloads* pay = nullptr) {
     *out_len = 0;
+    const bool pay_shares = pay && pay->shares, pay_seeds = pay && pay->seed_off && n_masks;
+    // Scratch in h->pipe: [mask | masked | compacted shares], carved once per call -- before the clerk payloads of
+    // an Additive scheme are decoded into `masked`, whose length is then bounded by blob 0's bytes only, else once
+    // the output length is known
+    int64_t *dmask = nullptr, *dmasked = nullptr, *dcompact = nullptr;
+    auto carve = [&](uint64_t masked_cap, uint64_t mask_cap, uint64_t compact_bytes) -> sda_status {
+        if (sda_status e = ensure(&h->pipe, &h->pipe_bytes,
+                                  rup(mask_cap * 8) + rup(masked_cap * 8) + rup(compact_bytes) + 256))
+            return e;
+        dmask = static_cast<int64_t*>(h->pipe);
+        dmasked = dmask + rup(mask_cap * 8) / 8;
+        dcompact = dmasked + rup(masked_cap * 8) / 8;
+        return SDA_OK;
+    };
     // Checks in the reference's order: mask combine (receive.rs:101-117), reconstruct (:120-146),
     // unmask (:149-152).
     // ---- 1. mask combine: its length and panics ----
     uint64_t mask_len = 0;
     if (sda_status e = mask_combine_checks(ms, n_masks, mask_width, &mask_len)) return e;
+    // ChaCha seed payloads: the key words of every seed, zero padded, decoded into handle scratch.  Queued here, in
+    // front of the wait the clerk results' lengths take, so that the offsets' copy and the kernel hide under it and
+    // the mask combine finds its seeds ready.
+    uint32_t* dseeds = nullptr;
+    if (pay_seeds && ms->kind == SDA_MASKING_CHACHA && mask_len) {
+        const size_t words = rup(n_masks * sda::kSeedWords * 4);
+        if (sda_status e = ensure(&h->job_work, &h->job_work_bytes, words + rup((n_masks + 1) * 8))) return e;
+        dseeds = static_cast<uint32_t*>(h->job_work);
+        HIP_TRY(sda::launch_recipient_seeds(pay->seed_bytes, pay->seed_off, n_masks,
+                                            reinterpret_cast<uint64_t*>(static_cast<char*>(h->job_work) + words),
+                                            dseeds, st));
+    }
     // ---- 2. reconstruct: masked output length and errors ----
     uint64_t D;
-    if (ss->kind == SDA_SHARING_ADDITIVE) {
+    uint64_t stride = share_len;                             // of the i64 clerk rows the packed reveal reads
+    sda::VarintPlan plan;                                    // PackedShamir clerk payloads: the count pass's plan
+    bool irregular = false;
+    if (ss->kind == SDA_SHARING_ADDITIVE && pay_shares) {
+        // additive.rs:56-72 is combiner.rs:16-28: the clerk's decode -> combine writes `masked`, and its one wait
+        // tells the length.  Row 0 is folded (`%= modulus`, additive.rs:66-67) before :64 reads a later row's length.
+        const uint64_t cap = n_idx ? pay->clerk_off[1] - pay->clerk_off[0] : 0;       // one value per byte at most
+        if (cap) {
+            int64_t m0;
+            if (sda_status e = modulus_abs(ss->modulus, &m0)) return e;
+        }
+        if (sda_status e = carve(cap, ms->kind == SDA_MASKING_NONE || pay->combined_mask ? 0 : std::min(mask_len, cap), 0))
+            return e;
+        if (sda_status e = decode_combine(h, ss->modulus, pay->clerk_bytes, pay->clerk_off, n_idx, dmasked, cap, &D, st))
+            return e == SDA_ERR_WRONG_DIMENSION ? fail(SDA_ERR_MISMATCHING_DIMENSION, "Mismatching dimension") : e;
+    } else if (ss->kind == SDA_SHARING_ADDITIVE) {
         D = n_idx ? share_len : 0;                           // additive.rs:56-60
         if (D) {                                             // additive.rs:67 `%= modulus`
             int64_t m0;
@@ -55,6 +151,19 @@ sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const
         if (sda_status e = check_packed(ss)) return e;
         if (mode != SDA_REVEAL_EXACT && mode != SDA_REVEAL_CANONICAL) return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
         const uint64_t B = (dimension + ss->secret_count - 1) / ss->secret_count;
+        if (pay_shares) {
+            // the count pass's one wait supplies the lengths of the reference's checks: ragged rows are read over
+            // [0, B) (batched.rs:83-85), so the shortest decides, and the longest is the rows' stride
+            share_len = stride = 0;
+            if (B && n_idx) {
+                std::vector<uint64_t> counts(n_idx);
+                if (sda_status e = codec_count(h, pay->clerk_bytes, pay->clerk_off, n_idx, &plan, counts.data(),
+                                               &irregular, st))
+                    return e;
+                share_len = *std::min_element(counts.begin(), counts.end());
+                stride = *std::max_element(counts.begin(), counts.end());
+            }
+        }
         if (B) {                                             // batched.rs:77-81: no batch => no check
             const bool enough = n_idx >= ss->privacy_threshold + ss->secret_count;
             if (n_idx && share_len < (enough ? B : 1))      // batched.rs:84 indexes [batch_index]
@@ -78,38 +187,46 @@ sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const
         if (sda_status e = modulus_abs(ms->modulus, &q)) return e;
     const bool packed = ss->kind == SDA_SHARING_PACKED_SHAMIR;
     const uint64_t B = packed ? (dimension + ss->secret_count - 1) / ss->secret_count : 0;
-    const bool compact = packed && share_len != B;
-    if (sda_status e = ensure(&h->pipe, &h->pipe_bytes, 2 * rup(D * 8) + (compact ? rup(n_idx * B * 8) : 0) + 256))
-        return e;
-    int64_t* dmask = static_cast<int64_t*>(h->pipe);
-    int64_t* dmasked = dmask + rup(D * 8) / 8;
+    const bool compact = packed && stride != B;
+    if (!dmasked)                                           // (a payload job's Additive reconstruction has run)
+        if (sda_status e = carve(D, D, compact ? n_idx * B * 8 : 0)) return e;
     // sda_recipient_last_launch: collected here, the handle's record only once this call returns SDA_OK
     sda_engine::RecipientLaunchInfo rec;
     rec.mask_kind = ms->kind == SDA_MASKING_NONE ? 1 : ms->kind == SDA_MASKING_FULL ? 2 : 3;
     rec.compact = compact;
     rec.unmask_launches = 1;
     // 1. masks (receive.rs:101-117)
-    if (ms->kind == SDA_MASKING_FULL) {
+    const int64_t* mask = dmask;
+    if (ms->kind == SDA_MASKING_FULL && pay && pay->combined_mask) {
+        mask = pay->combined_mask;                          // folded by the caller: (0 + c) % m = c
+    } else if (ms->kind == SDA_MASKING_FULL) {
         if (sda_status e = modulus_abs(ms->modulus, &q)) return e;
         HIP_TRY(sda::launch_combine_exact(static_cast<const int64_t*>(mask_in), n_masks, D, mask_width, dmask, q, st,
                                           false, &h->combine_last));
     }
     PendingChacha pc;                                       // ChaCha: its rejection count is checked at the end
     if (ms->kind == SDA_MASKING_CHACHA) {
-        if (sda_status e = chacha_combine_begin(h, ms->modulus, D, static_cast<const uint32_t*>(mask_in),
-                                                (uint32_t)mask_width, n_masks, dmask, st, &pc))
+        const uint32_t* seeds = dseeds ? dseeds : static_cast<const uint32_t*>(mask_in);
+        if (sda_status e = chacha_combine_begin(h, ms->modulus, D, seeds, (uint32_t)mask_width, n_masks, dmask, st, &pc))
             return e;
     }
     // 2. reconstruct (receive.rs:120-146)
-    if (!packed) {
+    if (!packed && !pay_shares) {
         int64_t m;
         if (sda_status e = modulus_abs(ss->modulus, &m)) return e;
         HIP_TRY(sda::launch_combine_exact(shares, n_idx, D, share_len, dmasked, m, st, false, &h->combine_last));
-    } else {
+    } else if (packed) {
+        if (pay_shares) {                                   // i64 rows of the longest blob's length in handle scratch
+            if (sda_status e = ensure(&h->codec_mat, &h->codec_mat_bytes, n_idx * stride * 8 + 8)) return e;
+            int64_t* rows = static_cast<int64_t*>(h->codec_mat);
+            HIP_TRY(sda::launch_varint_decode(pay->clerk_bytes, n_idx, plan, h->codec_work, rows, stride, stride,
+                                              irregular, st));
+            shares = rows;
+        }
         const int64_t* src = shares;
         if (compact) {                                      // batched.rs:83-85 reads [clerk][0..B)
-            int64_t* c = dmasked + rup(D * 8) / 8;
-            HIP_TRY(hipMemcpy2DAsync(c, B * 8, shares, share_len * 8, B * 8, n_idx, hipMemcpyDeviceToDevice, st));
+            int64_t* c = dcompact;
+            HIP_TRY(hipMemcpy2DAsync(c, B * 8, shares, stride * 8, B * 8, n_idx, hipMemcpyDeviceToDevice, st));
             src = c;
         }
         sda::PackedRevealArgs ra{src, dimension, 1, dmasked};
@@ -134,7 +251,7 @@ sda_status recipient_pipeline(sda_engine* h, const sda_masking_scheme* ms, const
         if (e) return e;
     }
     // 3. unmask (receive.rs:149-152) + RecipientOutput::positive (:14-20), one pass
-    HIP_TRY(sda::launch_unmask_positive(dmasked, ms->kind == SDA_MASKING_NONE ? nullptr : dmask, D, q,
+    HIP_TRY(sda::launch_unmask_positive(dmasked, ms->kind == SDA_MASKING_NONE ? nullptr : mask, D, q,
                                         output_modulus, out, st));
     if (pc.pending) {            // the mask's rejection count: fix the mask and unmask again if it had any
         HIP_TRY(hipStreamSynchronize(st));
@@ -263,6 +380,188 @@ sda_status sda_recipient_reveal(sda_engine* h, const sda_masking_scheme* ms, con
     if (len) HIP_TRY(hipMemcpyAsync(out, dout, len * 8, hipMemcpyDeviceToHost, h->stream));
     *out_len = len;
     return finish(h);
+}
+
+// ---------------- recipient job: the same pipeline from the opened payloads ----------------
+// receive.rs:98-157 + positive() with the decode of receive.rs:101-146 (Decryptor::decrypt, sodium.rs:82-90) on the
+// device too.
+sda_status sda_recipient_job_dev(sda_engine* h, const sda_masking_scheme* ms, const int64_t* mask, uint64_t mask_len,
+                                 const uint8_t* seed_bytes, const uint64_t* seed_off, uint64_t n_seeds,
+                                 const sda_sharing_scheme* ss, uint64_t dimension, const uint64_t* indices,
+                                 const uint8_t* clerk_bytes, const uint64_t* clerk_off, uint64_t n_idx,
+                                 int64_t output_modulus, int32_t mode, int64_t* out, uint64_t out_cap,
+                                 uint64_t* out_len, void* stream) {
+    SDA_ENTRY;
+    if (!h || !ms || !ss || !out_len) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    const bool full = ms->kind == SDA_MASKING_FULL;
+    if (full) n_seeds = 0;                                  // the seed arguments belong to ChaCha and None
+    if ((n_idx && (!clerk_bytes || !clerk_off || !indices)) || (n_seeds && (!seed_bytes || !seed_off)) ||
+        (full && mask_len && !mask))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = pick(h, stream);
+    if (sda_status e = check_blob_buffer(seed_bytes, seed_off, n_seeds)) return e;
+    if (sda_status e = check_blob_buffer(clerk_bytes, clerk_off, n_idx)) return e;
+    RecipientPayloads pay;
+    pay.clerk_bytes = clerk_bytes;
+    pay.clerk_off = clerk_off;
+    pay.shares = true;
+    uint64_t n_masks = n_seeds, width = 0;
+    if (full) {                                             // one row, already folded: full.rs:38-51 has run
+        n_masks = mask_len ? 1 : 0;
+        width = mask_len;
+        pay.combined_mask = mask;
+    } else if (ms->kind == SDA_MASKING_CHACHA) {
+        width = sda::kSeedWords;
+        pay.seed_bytes = seed_bytes;
+        pay.seed_off = seed_off;
+    } else {                                                // none.rs:23: a blob with a byte decodes to a value
+        for (uint64_t i = 0; i < n_seeds; ++i) width |= seed_off[i + 1] - seed_off[i];
+    }
+    const LaunchRecords before(h);
+    if (sda_status e = recipient_pipeline(h, ms, nullptr, n_masks, width, ss, dimension, indices, nullptr, n_idx, 0,
+                                          output_modulus, mode, out, out_cap, out_len, st, &pay)) {
+        before.restore(h);
+        return e;
+    }
+    if (*out_len)
+        h->recipient_job_last = {ms->kind == SDA_MASKING_NONE ? 0u : full ? 1u : 3u,
+                                 ss->kind == SDA_SHARING_ADDITIVE ? 1u : 2u,
+                                 ms->kind == SDA_MASKING_CHACHA ? (uint32_t)n_seeds : 0u};
+    return ok();
+}
+
+sda_status sda_recipient_job(sda_engine* h, const sda_masking_scheme* ms, const uint8_t* const* mask_blobs,
+                             const uint64_t* mask_lens, uint64_t n_masks, const sda_sharing_scheme* ss,
+                             uint64_t dimension, const uint64_t* indices, const uint8_t* const* clerk_blobs,
+                             const uint64_t* clerk_lens, uint64_t n_idx, int64_t output_modulus, int32_t mode,
+                             int64_t* out, uint64_t out_cap, uint64_t* out_len) {
+    SDA_ENTRY;
+    if (!h || !ms || !ss || !out_len || (n_masks && (!mask_blobs || !mask_lens)) ||
+        (n_idx && (!clerk_blobs || !clerk_lens || !indices)))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (uint64_t i = 0; i < n_masks; ++i)
+        if (mask_lens[i] && !mask_blobs[i])
+            return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument (mask blob %llu)", (unsigned long long)i);
+    for (uint64_t i = 0; i < n_idx; ++i)
+        if (clerk_lens[i] && !clerk_blobs[i])
+            return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument (clerk blob %llu)", (unsigned long long)i);
+    *out_len = 0;
+    HIP_TRY(hipSetDevice(h->device));
+    (void)pick(h, h->stream);
+    const LaunchRecords before(h);
+    auto failed = [&](sda_status e) {                       // the call fails: every record stays the previous call's
+        before.restore(h);
+        return e;
+    };
+    // 1. the mask combine's inputs and panics (receive.rs:101-117), before anything of the clerk results is looked at
+    RecipientPayloads pay;
+    uint64_t pipe_masks = n_masks, width = 0;
+    const void* mask_in = nullptr;
+    const sda_masking_scheme* pipe_ms = ms;
+    const sda_masking_scheme full_row = {SDA_MASKING_FULL, ms->modulus, 0, 0};
+    const bool chacha = ms->kind == SDA_MASKING_CHACHA;
+    uint32_t mask_route = 0;
+    if (ms->kind == SDA_MASKING_FULL) {
+        // full.rs:38-51 is combiner.rs:16-28: the blobs stream through the clerk's decode -> combine, a group of
+        // them in HBM at a time, and the folded mask stays on the device
+        int64_t* acc = nullptr;
+        uint64_t len = 0;
+        if (sda_status e = host_decode_combine(h, ms->modulus, mask_blobs, mask_lens, n_masks, nullptr, 0, &len, &acc)) {
+            before.restore(h);
+            return e == SDA_ERR_WRONG_DIMENSION ? fail(SDA_ERR_PRECONDITION, "assertion failed: mask.len() == dimension")
+                                                : e;
+        }
+        pay.combined_mask = acc;
+        pipe_masks = len ? 1 : 0;
+        width = len;
+        mask_route = 2;
+    } else if (chacha) {
+        width = sda::kSeedWords;
+        uint64_t mask_len;
+        if (sda_status e = mask_combine_checks(ms, n_masks, width, &mask_len)) return e;
+        mask_route = 3;
+    } else {
+        for (uint64_t i = 0; i < n_masks; ++i)
+            if (mask_lens[i]) return fail(SDA_ERR_PRECONDITION, "assertion failed: masks.iter().all(|mask| mask.len() == 0)");
+    }
+    uint64_t seed_total = 0, clerk_total = 0;
+    if (chacha)
+        for (uint64_t i = 0; i < n_masks; ++i) seed_total += mask_lens[i];
+    for (uint64_t i = 0; i < n_idx; ++i) clerk_total += clerk_lens[i];
+    std::vector<uint64_t> seed_off, clerk_off;
+    uint8_t* dseed_bytes = nullptr;
+    // A multi-device handle spreads the ChaCha mask combine over its devices exactly as sda_recipient_reveal does:
+    // the key words are decoded on the device, read back (32 bytes a seed), split, reduced onto device 0, and the
+    // pipeline sees the combined mask as one Full row.
+    const bool multi_mask = chacha && is_multi(h) && n_masks && ms->dimension && ms->modulus > 0;
+    if (multi_mask) {
+        DevArena a;
+        if (sda_status e = stage(h, rup(seed_total + 32) + rup(n_masks * sda::kSeedWords * 4) + rup((n_masks + 1) * 8), &a))
+            return e;
+        if (sda_status e = upload_blobs(h, mask_blobs, mask_lens, n_masks, &a, &dseed_bytes, &seed_off)) return e;
+        uint32_t* dwords = a.take<uint32_t>(n_masks * sda::kSeedWords);
+        uint64_t* doff = a.take<uint64_t>(n_masks + 1);
+        std::vector<uint32_t> seeds(n_masks * sda::kSeedWords);
+        HIP_TRY(sda::launch_recipient_seeds(dseed_bytes, seed_off.data(), n_masks, doff, dwords, h->stream));
+        HIP_TRY(hipMemcpyAsync(seeds.data(), dwords, seeds.size() * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (sda_status e = host_stream_ensure(h, 0, ms->dimension * 8)) return e;
+        if (sda_status e = chacha_combine_multi(h, ms->modulus, ms->dimension, seeds, sda::kSeedWords, n_masks,
+                                                static_cast<int64_t*>(h->hs_dev)))
+            return failed(e);
+        pipe_ms = &full_row;
+        mask_in = h->hs_dev;
+        pipe_masks = 1;
+        width = ms->dimension;
+        mask_route = 4;
+    }
+    // 2. one upload of the seed and clerk payloads
+    const uint64_t outn = ss->kind == SDA_SHARING_ADDITIVE ? (n_idx ? clerk_lens[0] : 0) : dimension;
+    const bool up_seeds = chacha && !multi_mask && n_masks;
+    DevArena a;
+    if (sda_status e = stage(h, (up_seeds ? rup(seed_total + 32) : 0) + rup(clerk_total + 32) + rup(outn * 8 + 8), &a))
+        return failed(e);
+    if (up_seeds) {
+        if (sda_status e = upload_blobs(h, mask_blobs, mask_lens, n_masks, &a, &dseed_bytes, &seed_off)) return failed(e);
+        pay.seed_bytes = dseed_bytes;
+        pay.seed_off = seed_off.data();
+    }
+    uint8_t* dclerk = nullptr;
+    if (sda_status e = upload_blobs(h, clerk_blobs, clerk_lens, n_idx, &a, &dclerk, &clerk_off)) return failed(e);
+    pay.clerk_bytes = dclerk;
+    pay.clerk_off = clerk_off.data();
+    pay.shares = true;
+    int64_t* dout = a.take<int64_t>(outn + 1);
+    // 3. the pipeline, the clerk results decoded where it reconstructs
+    uint64_t len = 0;
+    if (sda_status e = recipient_pipeline(h, pipe_ms, mask_in, pipe_masks, width, ss, dimension, indices, nullptr, n_idx,
+                                          0, output_modulus, mode, dout, (uint64_t)-1, &len, h->stream, &pay))
+        return failed(e);
+    if (out_cap < len) {
+        before.restore(h);
+        return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    }
+    if (len) {
+        if (multi_mask) h->recipient_last.mask_kind = 4;    // the pipeline saw the combined row as a Full mask
+        h->recipient_job_last = {mask_route, ss->kind == SDA_SHARING_ADDITIVE ? 1u : 2u,
+                                 chacha ? (uint32_t)n_masks : 0u};
+        HIP_TRY(hipMemcpyAsync(out, dout, len * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    *out_len = len;
+    return finish(h);
+}
+
+sda_status sda_recipient_job_last_launch(sda_engine* h, uint32_t* mask_route, uint32_t* share_route,
+                                         uint32_t* seeds_decoded) {
+    SDA_ENTRY;
+    if (!h || !mask_route || !share_route || !seeds_decoded) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    // a host-side record, final when the call that made it returned: nothing to wait for
+    const sda_engine::RecipientJobLaunchInfo& r = h->recipient_job_last;
+    *mask_route = r.mask_route;
+    *share_route = r.share_route;
+    *seeds_decoded = r.seeds_decoded;
+    return ok();
 }
 
 // The participant pipeline behind sda_participant_share_dev, sda_participant_share32_dev and their keyed forms.

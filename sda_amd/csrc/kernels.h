@@ -392,4 +392,13 @@ hipError_t launch_snapshot_transpose(const uint8_t* src, uint8_t* dst, const Sna
                                      const uint64_t* chunk_start, uint64_t n_blobs, uint64_t total_chunks,
                                      hipStream_t s, uint64_t* grid = nullptr);
 
+// ---- recipient_job.hip ----
+// The ChaCha seed payloads of a recipient job: blob b = bytes[blob_off[b], blob_off[b + 1]) is walked by the
+// codec's rules and its first kSeedWords values are stored `as u32`, zero padded, into words[b][kSeedWords]
+// (16-byte aligned) -- the seed matrix of the ChaCha mask combine at w = kSeedWords.  blob_off_dev: device scratch
+// of (n_seeds + 1) * 8 bytes the host offsets are uploaded to.  Queued on s; no wait.
+constexpr uint32_t kSeedWords = 8;     // ChaChaRng's key
+hipError_t launch_recipient_seeds(const uint8_t* bytes, const uint64_t* blob_off_host, uint64_t n_seeds,
+                                  uint64_t* blob_off_dev, uint32_t* words, hipStream_t s);
+
 }  // namespace sda

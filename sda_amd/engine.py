@@ -99,6 +99,16 @@ PARTICIPANT_SHARE_PACKED = 3
 PARTICIPANT_SHARE_PACKED_KEYED = 4
 ParticipantLaunch = collections.namedtuple("ParticipantLaunch", "mask_route share_route passes")
 
+# sda_recipient_job_last_launch's route codes
+RECIPIENT_JOB_MASK_NONE = 0
+RECIPIENT_JOB_MASK_FULL_COMBINED = 1
+RECIPIENT_JOB_MASK_FULL_STREAMED = 2
+RECIPIENT_JOB_MASK_CHACHA = 3
+RECIPIENT_JOB_MASK_CHACHA_SPLIT = 4
+RECIPIENT_JOB_SHARE_ADDITIVE = 1
+RECIPIENT_JOB_SHARE_PACKED = 2
+RecipientJobLaunch = collections.namedtuple("RecipientJobLaunch", "mask_route share_route seeds_decoded")
+
 # Elements one workgroup of the draws kernel produces (csrc/kernels.h kDrawsTile): the sizes at which
 # sda_draws_dev's grid gains a workgroup
 DRAWS_TILE = 2048
@@ -206,6 +216,13 @@ SIGNATURES = [
     ("sda_recipient_reveal", _st, [_vp, C.POINTER(S.MaskingSchemeC), C.POINTER(_i64p), _u64p, C.c_uint64,
                                    C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.POINTER(_i64p), _u64p,
                                    C.c_uint64, C.c_int64, C.c_int32, _i64p, C.c_uint64, _u64p]),
+    ("sda_recipient_job", _st, [_vp, C.POINTER(S.MaskingSchemeC), C.POINTER(_u8p), _u64p, C.c_uint64,
+                                C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.POINTER(_u8p), _u64p, C.c_uint64,
+                                C.c_int64, C.c_int32, _i64p, C.c_uint64, _u64p]),
+    ("sda_recipient_job_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _vp, C.c_uint64, _vp, _u64p, C.c_uint64,
+                                    C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, _vp, _u64p, C.c_uint64,
+                                    C.c_int64, C.c_int32, _vp, C.c_uint64, _u64p, _vp]),
+    ("sda_recipient_job_last_launch", _st, [_vp, _u32p, _u32p, _u32p]),
     ("sda_participant_share_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _u32p, C.c_uint64, _vp,
                                         C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, _vp, C.c_int32, _vp, _vp,
                                         C.c_uint64, _u64p, _vp]),
@@ -543,6 +560,30 @@ class Engine:
                                              out.size, C.byref(olen)))
         return out[: olen.value]
 
+    @staticmethod
+    def _blobs(blobs):
+        bufs = [(C.c_uint8 * max(len(b), 1)).from_buffer_copy(b or b"\0") for b in blobs]
+        n = len(bufs)
+        ptrs = (_u8p * max(n, 1))(*[C.cast(b, _u8p) for b in bufs])
+        lens = (C.c_uint64 * max(n, 1))(*[len(b) for b in blobs])
+        return bufs, ptrs, lens, n
+
+    def recipient_job(self, masking, mask_blobs: Sequence[bytes], sharing, dimension: int, indexed_blobs,
+                      output_modulus: int, mode=REVEAL_EXACT) -> np.ndarray:
+        """recipient_reveal from the opened payloads: mask_blobs are the participations' mask payloads (Full masks or
+        ChaCha seeds), indexed_blobs the (clerk index, opened clerk result) pairs; the engine decodes them."""
+        ms, ss = masking.c(), sharing.c()
+        mbufs, mptrs, mlens, nm = self._blobs(mask_blobs)
+        idx = _arr([i for i, _ in indexed_blobs], np.uint64)
+        sbufs, sptrs, slens, ns = self._blobs([b for _, b in indexed_blobs])
+        cap = max(dimension, len(indexed_blobs[0][1]) if indexed_blobs else 0, 1)
+        out = np.zeros(cap, np.int64)
+        olen = C.c_uint64(0)
+        _check(self.lib.sda_recipient_job(self.h, C.byref(ms), mptrs, mlens, nm, C.byref(ss), dimension,
+                                          _ptr(idx, _u64p), sptrs, slens, ns, output_modulus, mode, _ptr(out),
+                                          out.size, C.byref(olen)))
+        return out[: olen.value]
+
     def synchronize(self):
         _check(self.lib.sda_engine_synchronize(self.h))
 
@@ -661,6 +702,14 @@ class Engine:
         v = [C.c_uint32() for _ in range(3)]
         _check(self.lib.sda_participant_last_launch(self.h, *[C.byref(x) for x in v]))
         return ParticipantLaunch(*[int(x.value) for x in v])
+
+    def recipient_job_last_launch(self):
+        """RecipientJobLaunch(mask_route, share_route, seeds_decoded) of the handle's last recipient_job /
+        recipient_job_dev with a non-empty output: the RECIPIENT_JOB_MASK_* and RECIPIENT_JOB_SHARE_* codes and the
+        seed blobs the seed kernel decoded (sda_recipient_job_last_launch)."""
+        v = [C.c_uint32() for _ in range(3)]
+        _check(self.lib.sda_recipient_job_last_launch(self.h, *[C.byref(x) for x in v]))
+        return RecipientJobLaunch(*[int(x.value) for x in v])
 
     def packed_keyed_last_launch(self):
         """(path, staged_bytes) of the handle's last keyed packed-Shamir launch: path 0 none yet, 1 the draws were
@@ -842,6 +891,23 @@ class Engine:
         _check(self.lib.sda_recipient_reveal_dev(self.h, C.byref(ms), mask_ptr, n_masks, mask_width, C.byref(ss),
                                                  dimension, _ptr(idx, _u64p), shares_ptr, idx.size, share_len,
                                                  output_modulus, mode, out_ptr, out_cap, C.byref(olen), stream))
+        return olen.value
+
+    def recipient_job_dev(self, masking, sharing, dimension, indices, clerk_ptr, clerk_off, output_modulus, out_ptr,
+                          out_cap, mask_ptr=None, mask_len=0, seed_ptr=None, seed_off=(), mode=REVEAL_EXACT,
+                          stream=None) -> int:
+        """recipient_reveal_dev from the opened payloads on the device: (clerk_ptr, clerk_off) and, for ChaCha
+        masking, (seed_ptr, seed_off) are (bytes, offsets) pairs as clerk_decode_combine_dev takes them; for Full
+        masking (mask_ptr, mask_len) is the combined mask, e.g. the state clerk_job_dev left over the mask payloads."""
+        ms, ss = masking.c(), sharing.c()
+        idx = _arr(indices, np.uint64)
+        coff = _arr(clerk_off if len(clerk_off) else [0], np.uint64)
+        soff = _arr(seed_off if len(seed_off) else [0], np.uint64)
+        olen = C.c_uint64(0)
+        _check(self.lib.sda_recipient_job_dev(self.h, C.byref(ms), mask_ptr, mask_len, seed_ptr, _ptr(soff, _u64p),
+                                              soff.size - 1, C.byref(ss), dimension, _ptr(idx, _u64p), clerk_ptr,
+                                              _ptr(coff, _u64p), coff.size - 1, output_modulus, mode, out_ptr,
+                                              out_cap, C.byref(olen), stream))
         return olen.value
 
     def participant_share_dev(self, masking, sharing, secrets_ptr, dimension, draws_ptr, shares_ptr, seed=None,
