@@ -13,7 +13,7 @@ LIB     ?= sda_amd/libsda_engine.so
 # share-gen objects, one per (n+1, k+t+1): the n+1 = 81 instantiations dominate the build, so they compile in parallel
 GEN_PARTS    := 3_2 9_2 9_4 9_8 27_2 27_4 27_8 27_16 81_2 81_4 81_8 81_16 81_32 81_64
 REVEAL_PARTS := 8 16 32 64 96
-PLAIN   := combine elementwise chacha codec_decode codec_encode snapshot packed_wide draws additive_keyed recipient_job
+PLAIN   := combine elementwise chacha codec_decode codec_encode snapshot packed_wide draws additive_keyed mask_keyed recipient_job
 HOST    := engine engine_dev hbm engine_codec engine_pipelines engine_host
 OBJS    := $(patsubst %,$(OBJDIR)/%.o,$(PLAIN)) $(patsubst %,$(OBJDIR)/%.o,$(HOST)) \
            $(OBJDIR)/packed_gen.o $(patsubst %,$(OBJDIR)/packed_gen_%.o,$(GEN_PARTS)) \
@@ -35,7 +35,7 @@ $(OBJDIR)/packed_reveal_%.o: $(CSRC)/packed_reveal.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -DSDA_REVEAL_PART=$* -c $< -o $@
 
 # the host translation units of the C ABI: one object each
-$(OBJDIR)/%.o: $(CSRC)/%.cpp $(CSRC)/engine_internal.h $(CSRC)/host_pack.h $(HDRS)
+$(OBJDIR)/%.o: $(CSRC)/%.cpp $(CSRC)/engine_internal.h $(CSRC)/host_pack.h $(CSRC)/participant_job_plan.h $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -x hip -c $< -o $@
 

@@ -275,6 +275,30 @@ extern "C" {
     pub fn sda_recipient_job_last_launch(h: *mut SdaEngine, mask_route: *mut u32, share_route: *mut u32,
                                          seeds_decoded: *mut u32) -> SdaStatus;
 
+    // ---- participant job: mask, mask payload, shares and every clerk payload in one call ----
+    pub fn sda_full_mask_keyed_dev(h: *mut SdaEngine, modulus: i64, secrets: *const i64, dimension: u64,
+                                   key: *const u32, stream_id: u32, first: u64, masked_out: *mut i64,
+                                   mask_out: *mut i64, stream: *mut c_void) -> SdaStatus;
+    pub fn sda_full_mask_keyed32_dev(h: *mut SdaEngine, modulus: i64, secrets: *const i64, dimension: u64,
+                                     key: *const u32, stream_id: u32, first: u64, masked_out: *mut i64,
+                                     mask_out: *mut i32, stream: *mut c_void) -> SdaStatus;
+    pub fn sda_participant_job_payload_bound(ms: *const SdaMaskingScheme, ss: *const SdaSharingScheme,
+                                             dimension: u64, clerk_row_bound: *mut u64, mask_bound: *mut u64)
+        -> SdaStatus;
+    pub fn sda_participant_job_dev(h: *mut SdaEngine, ms: *const SdaMaskingScheme, seed: *const u32,
+                                   seed_words: u64, ss: *const SdaSharingScheme, secrets: *const i64,
+                                   dimension: u64, key: *const u32, mask_stream_id: u32, share_stream_id: u32,
+                                   mode: i32, payload: *mut u8, payload_cap: u64, payload_row_bytes: *mut u64,
+                                   mask_payload: *mut u8, mask_payload_cap: u64, mask_payload_len: *mut u64,
+                                   stream: *mut c_void) -> SdaStatus;
+    pub fn sda_participant_job(h: *mut SdaEngine, ms: *const SdaMaskingScheme, seed: *const u32, seed_words: u64,
+                               ss: *const SdaSharingScheme, secrets: *const i64, dimension: u64, key: *const u32,
+                               mask_stream_id: u32, share_stream_id: u32, mode: i32,
+                               clerk_payloads: *const *mut u8, clerk_caps: *const u64, clerk_lens: *mut u64,
+                               mask_payload: *mut u8, mask_cap: u64, mask_len: *mut u64) -> SdaStatus;
+    pub fn sda_participant_job_last_launch(h: *mut SdaEngine, mask_route: *mut u32, share_route: *mut u32,
+                                           share_bytes: *mut u32, tiles: *mut u64) -> SdaStatus;
+
     // ---- synthetic benchmark input ----
     pub fn sda_synth_fill_dev(h: *mut SdaEngine, dst: *mut i64, rows: u64, cols: u64, seed: u64, lo: i64, hi: i64,
                               stream: *mut c_void) -> SdaStatus;

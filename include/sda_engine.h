@@ -368,6 +368,7 @@ sda_status sda_recipient_last_launch(sda_engine* h, uint32_t* mask_kind, uint32_
  *                3  ChaCha, the fused single-stream mask add (sda_chacha_last_launch path 4)
  *                4  ChaCha, the mask expanded by the combine's dispatch (a modulus off the fast path, or
  *                   SDA_CHACHA_PATH=stream), then one add
+ *                5  Full, the mask drawn in the masking kernel (a participant job)
  *   share_route  1  Additive from the caller's draws
  *                2  Additive, draws made in the kernel (keyed)
  *                3  PackedShamir from the caller's draws
@@ -493,6 +494,28 @@ sda_status sda_draws_dev(sda_engine* h, const uint32_t* key, uint32_t stream_id,
  * -> SDA_ERR_INVALID_ARGUMENT. */
 sda_status sda_draws(sda_engine* h, const uint32_t* key, uint32_t stream_id, uint64_t first,
                      uint64_t count, int64_t bound, int64_t* out, uint64_t out_cap);
+
+/* Full masking (full.rs:22-35) with the mask drawn inside the masking kernel: for d < dimension,
+ *   mask_out[d]   = draw(first + d) of (key, stream_id) at bound = modulus, and
+ *   masked_out[d] = (secrets[d] + mask_out[d]) % modulus, a wrapping add and Rust's truncated `%` (full.rs:28-31),
+ * so mask_out is bit-identical to sda_draws_dev(key, stream_id, first, dimension, modulus) and masked_out to what
+ * sda_secret_mask returns with that mask, in one pass that reads the secrets once and writes each output once.
+ * `first` lets a caller split one job's secrets over calls, devices or streams: any split gives the same values.
+ * secrets, masked_out and mask_out are device buffers (8-byte aligned; the 32 form's mask_out 4-byte aligned) that
+ * do not overlap.  Only enqueues; runs on ordinals[0] of a multi-device handle.  sda_draws_dev's KEY CONTRACT
+ * applies verbatim.
+ * The 32 form writes the mask as int32 values, equal to (int32_t) of the i64 form's: with modulus <= 2^31 every
+ * mask value lies in [0, modulus) and fits.
+ * Checks, in this order: a NULL handle, key or needed buffer -> SDA_ERR_INVALID_ARGUMENT; modulus <= 0 ->
+ * SDA_ERR_PRECONDITION ("Rng.gen_range called with low >= high"); first + dimension wrapping past 2^64 ->
+ * SDA_ERR_INVALID_ARGUMENT; the 32 form with modulus > 2^31 -> SDA_ERR_UNSUPPORTED; dimension == 0 -> SDA_OK,
+ * nothing launched.  A refused call writes nothing. */
+sda_status sda_full_mask_keyed_dev(sda_engine* h, int64_t modulus, const int64_t* secrets, uint64_t dimension,
+                                   const uint32_t* key, uint32_t stream_id, uint64_t first, int64_t* masked_out,
+                                   int64_t* mask_out, void* stream);
+sda_status sda_full_mask_keyed32_dev(sda_engine* h, int64_t modulus, const int64_t* secrets, uint64_t dimension,
+                                     const uint32_t* key, uint32_t stream_id, uint64_t first, int64_t* masked_out,
+                                     int32_t* mask_out, void* stream);
 
 /* Additive share generation with the draws made inside the kernel: column d < dimension of
  * `secrets` (device) is absolute column c = first_column + d of the job and takes draws c (n - 1) + j, j < n - 1,
@@ -752,6 +775,77 @@ sda_status sda_participant_share32_keyed_dev(sda_engine* h, const sda_masking_sc
                                              uint64_t dimension, const uint32_t* key, uint32_t stream_id,
                                              int32_t mode, int32_t* shares_out, uint8_t* payload,
                                              uint64_t payload_cap, uint64_t* payload_row_bytes, void* stream);
+
+/* ---------------- participant job: mask, mask payload, shares and every clerk payload in one call ----------------
+ * participate.rs:53-98 between the secrets and the sealed boxes: SecretMasker::mask, the recipient's mask payload
+ * (:56-72), ShareGenerator::generate and one payload per clerk (:79-98), each payload being the bytes
+ * Encryptor::encrypt encodes before it seals (sodium.rs:36-41).  Sealing stays on the host.  Every random value comes
+ * from one key (sda_draws_dev's KEY CONTRACT applies verbatim): the Full mask is elements [0, D) of
+ * (key, mask_stream_id) at bound = the masking modulus, drawn inside the masking kernel (sda_full_mask_keyed_dev),
+ * and the share-generation draws are those of sda_participant_share_keyed_dev under (key, share_stream_id).
+ *
+ * CONTRACT.  The clerk payloads and their sizes are byte-identical to sda_participant_share_keyed_dev(ms, seed,
+ * seed_words, full_masks = sda_draws_dev(key, mask_stream_id, 0, D, ms->modulus), ss, secrets, D, key,
+ * share_stream_id, mode, ...)'s payload and payload_row_bytes; the mask payload is sda_varint_encode of the mask that
+ * full.rs / chacha.rs return (Full: those draws; ChaCha: the seed words `as i64`; None: empty).  The shares live in
+ * handle scratch as int32 rows wherever they fit by construction -- a PackedShamir scheme, or an Additive scheme with
+ * modulus <= 2^31 (sda_participant_share32_keyed_dev's rules) -- else as i64 rows, and a Full mask as int32 values
+ * when its modulus <= 2^31.  Masking, the ChaCha rejection check and its redo, the scheme checks and their statuses
+ * are those of sda_participant_share_dev; ChaCha masking also needs seed_words == (seed_bitsize + 31) / 32 when
+ * dimension is 0.  With Full masking mask_stream_id == share_stream_id -> SDA_ERR_INVALID_ARGUMENT (the key
+ * contract).  More than 65,535 clerks -> SDA_ERR_UNSUPPORTED.
+ *
+ * CAPACITIES.  sda_participant_job_payload_bound gives the worst case in bytes of one clerk's payload and of the mask
+ * payload, from the moduli alone: a share lies in (-m, m) and a mask value in [0, m), so a value takes at most the
+ * bytes of 2 (m - 1) -- 5 for every modulus up to 2^34 -- and a ChaCha seed word 5.  (One Additive clerk's share is
+ * the masked secret as it stands: the masking modulus bounds it, and without masking it takes up to 10 bytes.)  Both
+ * job forms require every capacity to be at least its bound, else they return SDA_ERR_INVALID_ARGUMENT before any
+ * work with every length set to its bound: nothing is ever half-written for want of space.  Needs no device. */
+sda_status sda_participant_job_payload_bound(const sda_masking_scheme* ms, const sda_sharing_scheme* ss,
+                                             uint64_t dimension, uint64_t* clerk_row_bound, uint64_t* mask_bound);
+
+/* Device form.  secrets [dimension]: device; seed (ChaCha) and key: HOST words.  payload (device, payload_cap >=
+ * share_count * clerk_row_bound bytes): the clerk payloads back to back, payload_row_bytes[share_count] (host) their
+ * sizes; mask_payload (device, mask_payload_cap >= mask_bound): the mask payload, *mask_payload_len (host) its size
+ * (0 without masking: nothing is drawn).  The ChaCha seed words are encoded on the host and copied.
+ * A failing call leaves caller memory and every *_last_launch record as they were.  The call drains its stream
+ * before returning, as sda_participant_share_dev with a payload does.  Runs on ordinals[0] of a multi-device handle. */
+sda_status sda_participant_job_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                   uint64_t seed_words, const sda_sharing_scheme* ss, const int64_t* secrets,
+                                   uint64_t dimension, const uint32_t* key, uint32_t mask_stream_id,
+                                   uint32_t share_stream_id, int32_t mode, uint8_t* payload, uint64_t payload_cap,
+                                   uint64_t* payload_row_bytes, uint8_t* mask_payload, uint64_t mask_payload_cap,
+                                   uint64_t* mask_payload_len, void* stream);
+
+/* Host form.  secrets [dimension], clerk_payloads[c] (clerk_caps[c] >= clerk_row_bound bytes) and mask_payload
+ * (mask_cap >= mask_bound) are host memory; clerk_lens[c] and *mask_len get the sizes.  Every output byte equals the
+ * device form's.  The job runs in tiles of whole batches (Additive: columns): a tile's secrets go up on the handle's
+ * copy stream while the previous tile computes and the one before it comes down, each clerk's bytes of a tile are
+ * appended to that clerk's blob, and device memory is bounded by the tile, not by share_count * B.  Tile [b0, b1)
+ * draws its mask from element b0 k on and its shares from first_batch (first_column) b0, so the bytes do not depend
+ * on the tiling.  The tile size follows SDA_HOST_STAGE_MB; SDA_PARTICIPANT_TILE_BATCHES (read per call; an A/B and
+ * test knob) sets it in batches.  With ChaCha masking the masked secrets are made over the whole vector first (8
+ * dimension bytes of handle scratch twice over) and its rejection count is read before the first tile.  Runs on
+ * ordinals[0] of a multi-device handle. */
+sda_status sda_participant_job(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed, uint64_t seed_words,
+                               const sda_sharing_scheme* ss, const int64_t* secrets, uint64_t dimension,
+                               const uint32_t* key, uint32_t mask_stream_id, uint32_t share_stream_id, int32_t mode,
+                               uint8_t* const* clerk_payloads, const uint64_t* clerk_caps, uint64_t* clerk_lens,
+                               uint8_t* mask_payload, uint64_t mask_cap, uint64_t* mask_len);
+
+/* Diagnostic (read-only): what the handle's most recent sda_participant_job / sda_participant_job_dev ran.  Written
+ * when such a call of dimension > 0 returns SDA_OK; before any such call every field is 0.
+ *   mask_route   0  no masking
+ *                1  Full, the mask drawn in the masking kernel as i64 values
+ *                2  Full, the same as int32 values (modulus <= 2^31)
+ *                3  ChaCha
+ *   share_route  as sda_participant_last_launch reports it (2 Additive keyed, 4 PackedShamir keyed)
+ *   share_bytes  4 or 8: the width of the share rows in handle scratch
+ *   tiles        the tiles of the host form; 1 for the device form
+ * sda_participant_last_launch describes the reused pipeline (its mask_route 5: a Full mask drawn in the masking
+ * kernel).  A host-side record: nothing is waited for or copied.  No pointer may be NULL. */
+sda_status sda_participant_job_last_launch(sda_engine* h, uint32_t* mask_route, uint32_t* share_route,
+                                           uint32_t* share_bytes, uint64_t* tiles);
 
 /* ---------------- recipient job: the recipient pipeline from the opened payloads ----------------
  * receive.rs:98-157 + positive() with the decode of every mask blob and clerk result (Decryptor::decrypt,

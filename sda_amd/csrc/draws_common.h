@@ -1,5 +1,5 @@
 // draws_common.h -- the draw rule's device code, shared by the kernels that expand it (draws.hip,
-// additive_keyed.hip, packed_gen.hip's keyed kernels): the ChaCha20 block with state words 14 = stream_id and 15 = retry round, and one lane's
+// additive_keyed.hip, mask_keyed.hip, packed_gen.hip's keyed kernels): the ChaCha20 block with state words 14 = stream_id and 15 = retry round, and one lane's
 // block of 8 draws with its per-element retry rounds.  draws.hip states the rule.
 #pragma once
 #include "kernels.h"

@@ -331,6 +331,7 @@ void sda_engine_destroy(sda_engine* h) {
     dev_free(h->codec_work);
     dev_free(h->codec_mat);
     dev_free(h->job_work);
+    dev_free(h->job_shares);
     dev_free(h->pipe);
     dev_free(h->snap);
     dev_free(h->stage);
@@ -342,6 +343,7 @@ void sda_engine_destroy(sda_engine* h) {
     for (int b = 0; b < 2; ++b) {
         if (h->h2d_done[b]) (void)hipEventDestroy(h->h2d_done[b]);
         if (h->tile_free[b]) (void)hipEventDestroy(h->tile_free[b]);
+        if (h->d2h_done[b]) (void)hipEventDestroy(h->d2h_done[b]);
     }
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->order_ev) (void)hipEventDestroy(h->order_ev);

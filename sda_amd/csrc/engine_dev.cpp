@@ -425,6 +425,45 @@ sda_status sda_draws(sda_engine* h, const uint32_t* key, uint32_t stream_id, uin
     return finish(h);
 }
 
+}  // extern "C"
+
+// sda_full_mask_keyed_dev and its 32 form: the checks in sda_draws_dev's order, then mask_keyed.hip's kernel.
+template <typename MaskOut>
+static sda_status full_mask_keyed(sda_engine* h, int64_t modulus, const int64_t* secrets, uint64_t D,
+                                  const uint32_t* key, uint32_t stream_id, uint64_t first, int64_t* masked_out,
+                                  MaskOut* mask_out, void* stream) {
+    if (!h || !key || (D && (!secrets || !masked_out || !mask_out)))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle, key or needed buffer");
+    if (modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
+    if (D && first + (D - 1) < first) return fail(SDA_ERR_INVALID_ARGUMENT, "first + count wraps past 2^64");
+    if (sizeof(MaskOut) == 4 && modulus > (int64_t)1 << 31)
+        return fail(SDA_ERR_UNSUPPORTED, "an int32 mask needs modulus <= 2^31: a mask value lies in [0, modulus)");
+    if (D == 0) return ok();
+    HIP_TRY(hipSetDevice(h->device));
+    int64_t* m64 = nullptr;
+    int32_t* m32 = nullptr;
+    if constexpr (sizeof(MaskOut) == 4) m32 = mask_out; else m64 = mask_out;
+    HIP_TRY(sda::launch_full_mask_keyed(key, stream_id, first, secrets, D, modulus, masked_out, m64, m32,
+                                        pick(h, stream)));
+    return ok();
+}
+
+extern "C" {
+
+sda_status sda_full_mask_keyed_dev(sda_engine* h, int64_t modulus, const int64_t* secrets, uint64_t dimension,
+                                   const uint32_t* key, uint32_t stream_id, uint64_t first, int64_t* masked_out,
+                                   int64_t* mask_out, void* stream) {
+    SDA_ENTRY;
+    return full_mask_keyed(h, modulus, secrets, dimension, key, stream_id, first, masked_out, mask_out, stream);
+}
+
+sda_status sda_full_mask_keyed32_dev(sda_engine* h, int64_t modulus, const int64_t* secrets, uint64_t dimension,
+                                     const uint32_t* key, uint32_t stream_id, uint64_t first, int64_t* masked_out,
+                                     int32_t* mask_out, void* stream) {
+    SDA_ENTRY;
+    return full_mask_keyed(h, modulus, secrets, dimension, key, stream_id, first, masked_out, mask_out, stream);
+}
+
 sda_status sda_synth_fill_dev(sda_engine* h, int64_t* dst, uint64_t rows, uint64_t cols, uint64_t seed, int64_t lo,
                               int64_t hi, void* stream) {
     SDA_ENTRY;

@@ -53,7 +53,7 @@ static int host_threads(size_t devices = 1) {
 }
 
 // bytes of one staging tile (SDA_HOST_STAGE_MB, default 256 MiB; at least 1 MiB)
-static uint64_t host_stage_bytes() {
+uint64_t host_stage_bytes() {
     const long long mb = env_ll("SDA_HOST_STAGE_MB", 256);
     return (uint64_t)std::max<long long>(mb, 1) << 20;
 }

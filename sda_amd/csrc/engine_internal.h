@@ -5,7 +5,7 @@
 //   engine_dev.cpp        the device-resident (`_dev`) entry points
 //   hbm.cpp               sda_hbm_*: HBM buffers built from fixed-size physical chunks
 //   engine_codec.cpp      the share payload codec's host side and the snapshot transposition
-//   engine_pipelines.cpp  the fused recipient and participant pipelines
+//   engine_pipelines.cpp  the fused recipient and participant pipelines, the participant job
 //   engine_host.cpp       the streaming, multi-device host path (RCCL loaded at run time)
 //
 // Host-side responsibilities only: argument validation with the reference's error behaviour
@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "participant_job_plan.h"
 
 struct sda_engine {
     int device = 0;
@@ -95,10 +96,20 @@ struct sda_engine {
     struct RecipientJobLaunchInfo {
         uint32_t mask_route = 0, share_route = 0, seeds_decoded = 0;
     } recipient_job_last;
+    // participant job (sda_participant_job, sda_participant_job_dev): the share rows [n][B] of a call (a tile of the
+    // host form) and the Full mask row behind them -- int32 where they fit by construction, else i64
+    void* job_shares = nullptr;
+    size_t job_shares_bytes = 0;
+    // sda_participant_job_last_launch: written when a participant job of dimension > 0 returns SDA_OK
+    struct ParticipantJobLaunchInfo {
+        uint32_t mask_route = 0, share_route = 0, share_bytes = 0;
+        uint64_t tiles = 0;
+    } participant_job_last;
     // streaming host path (host rows -> HBM in row tiles, engine_host.cpp): pinned staging and device
     // tiles, double buffered, and a copy stream so a tile's upload overlaps the previous tile's combine
     hipStream_t copy_stream = nullptr;
     hipEvent_t h2d_done[2] = {nullptr, nullptr}, tile_free[2] = {nullptr, nullptr};
+    hipEvent_t d2h_done[2] = {nullptr, nullptr};   // the host participant job: a tile's payloads have reached pinned memory
     void* hs_pin = nullptr;       // pinned host: 2 tiles
     size_t hs_pin_bytes = 0;
     void* hs_dev = nullptr;       // device: 2 tiles + the accumulator
@@ -271,6 +282,8 @@ void destroy_comms(sda_engine* h);
 sda_status chacha_combine_multi(sda_engine* h, int64_t m, uint64_t D, const std::vector<uint32_t>& seeds, uint32_t w,
                                 uint64_t n, int64_t* dst);
 sda_status host_stream_ensure(sda_engine* h, size_t tile_bytes, size_t acc_bytes);
+// bytes of one staging tile of the streamed host calls (SDA_HOST_STAGE_MB, read per call)
+uint64_t host_stage_bytes();
 // out == nullptr (sda_clerk_job): no copy to the host and no capacity check; *acc_dev (optional) = the device
 // accumulator holding the *out_len results (handle scratch: valid until the handle's next call), nullptr for none
 sda_status host_decode_combine(sda_engine* h, int64_t m, const uint8_t* const* blobs, const uint64_t* lens, uint64_t n,

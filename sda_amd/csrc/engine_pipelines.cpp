@@ -569,18 +569,37 @@ sda_status sda_recipient_job_last_launch(sda_engine* h, uint32_t* mask_route, ui
 // and keyed Additive up to modulus 2^31).  kd (the keyed forms): `draws` is NULL and the share-generation draws
 // come from (kd->key, kd->stream_id) -- Additive in the fused kernel, PackedShamir through the keyed launch
 // (packed_generate: in the share kernels, or staged in h->keyed_draws where those do not serve the scheme).
+// job (the participant job, keyed): where a Full mask comes from and where the call's secrets lie within the job.
+struct ParticipantJobArgs {
+    // Full masking: `full_masks` is NULL and the mask is drawn in the masking kernel (mask_keyed.hip) from
+    // (mask_key, mask_stream_id); its `dimension` values go to mask64, or to mask32 as int32 when that is given
+    const uint32_t* mask_key = nullptr;
+    uint32_t mask_stream_id = 0;
+    int64_t* mask64 = nullptr;
+    int32_t* mask32 = nullptr;
+    // the call's first batch (Additive: column) within the job: the first_batch / first_column of the keyed share
+    // generation, and times the batch size the first element of the mask
+    uint64_t first = 0;
+    // the masking step alone (the host job under ChaCha masking, whose tiles then share and encode): nothing is
+    // generated or encoded, and *masked_out = the D masked secrets in handle scratch (h->pipe), complete for work
+    // queued on the call's stream after it (the rejection check and its redo have run)
+    const int64_t** masked_out = nullptr;
+};
 static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
                                     uint64_t seed_words, const int64_t* full_masks, const sda_sharing_scheme* ss,
                                     const int64_t* secrets, uint64_t dimension, const int64_t* draws, int32_t mode,
                                     int64_t* shares64, int32_t* shares32, uint8_t* payload, uint64_t payload_cap,
-                                    uint64_t* payload_row_bytes, void* stream, const KeyedDraws* kd = nullptr) {
-    if (!h || !ms || !ss || (dimension && (!secrets || (!shares64 && !shares32))) || (payload && !payload_row_bytes) ||
-        (kd && !kd->key))
+                                    uint64_t* payload_row_bytes, void* stream, const KeyedDraws* kd = nullptr,
+                                    const ParticipantJobArgs* job = nullptr) {
+    const bool mask_only = job && job->masked_out;
+    if (!h || !ms || !ss || (dimension && (!secrets || (!shares64 && !shares32 && !mask_only))) ||
+        (payload && !payload_row_bytes) || (kd && !kd->key))
         return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = pick(h, stream);
     const uint64_t D = dimension;
     const bool packed = ss->kind == SDA_SHARING_PACKED_SHAMIR;
+    const uint64_t first = job ? job->first : 0;
     if (!packed && ss->kind != SDA_SHARING_ADDITIVE) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown sharing scheme kind");
     if (!packed && shares32 && !kd)
         return fail(SDA_ERR_UNSUPPORTED, "int32 shares need a PackedShamir scheme: an additive scheme's first n - 1 "
@@ -616,7 +635,13 @@ static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms,
         if (ms->modulus <= 0) return fail(SDA_ERR_PRECONDITION, "Rng.gen_range called with low >= high");
         if (sda_status e = ensure(&h->pipe, &h->pipe_bytes, 2 * rup(D * 8) + 256)) return e;
         int64_t* dm = static_cast<int64_t*>(h->pipe);
-        if (ms->kind == SDA_MASKING_FULL) {
+        if (ms->kind == SDA_MASKING_FULL && job && job->mask_key) {
+            // full.rs:25-31 in one kernel: element d of the call is element first k + d of the job's mask
+            HIP_TRY(sda::launch_full_mask_keyed(job->mask_key, job->mask_stream_id,
+                                                first * (packed ? ss->secret_count : 1), secrets, D, ms->modulus, dm,
+                                                job->mask64, job->mask32, st));
+            rec.mask_route = 5;
+        } else if (ms->kind == SDA_MASKING_FULL) {
             if (!full_masks) return fail(SDA_ERR_INVALID_ARGUMENT, "Full masking needs the drawn masks");
             HIP_TRY(sda::launch_addsub_trem(secrets, full_masks, +1, D, dm, ms->modulus, st));      // full.rs:28-31
             rec.mask_route = 2;
@@ -656,6 +681,7 @@ static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms,
     if (B && !draws && !kd) return fail(SDA_ERR_INVALID_ARGUMENT, "need the randomness draws");
     if (payload && n > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 clerks");
     auto share_and_encode = [&]() -> sda_status {
+        if (mask_only) return SDA_OK;
         if (B) {
             if (packed) {
                 sda::PackedGenArgs ga{masked, D, 1, draws, shares64, mode == SDA_REVEAL_CANONICAL};
@@ -663,10 +689,11 @@ static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms,
                 if (kd) {                        // batch b takes draws b t + j of (key, stream_id) at bound p - 1
                     ga.key = kd->key;
                     ga.stream_id = kd->stream_id;
+                    ga.first_batch = first;
                 }
                 if (sda_status e = packed_generate(h, ss, ga, st)) return e;
             } else if (kd) {
-                HIP_TRY(sda::launch_additive_generate_keyed(kd->key, kd->stream_id, 0, masked, D, n, ss->modulus,
+                HIP_TRY(sda::launch_additive_generate_keyed(kd->key, kd->stream_id, first, masked, D, n, ss->modulus,
                                                             shares64, shares32, B, st));
             } else {
                 HIP_TRY(sda::launch_additive_generate(masked, D, draws, n, shares64, ss->modulus, st));
@@ -698,6 +725,7 @@ static sda_status participant_share(sda_engine* h, const sda_masking_scheme* ms,
         }
     }
     if (D) h->participant_last = rec;
+    if (mask_only) *job->masked_out = masked;
     return ok();
 }
 
@@ -746,6 +774,374 @@ sda_status sda_participant_share32_keyed_dev(sda_engine* h, const sda_masking_sc
     const KeyedDraws kd{key, stream_id};
     return participant_share(h, ms, seed, seed_words, full_masks, ss, secrets, dimension, nullptr, mode, nullptr,
                              shares_out, payload, payload_cap, payload_row_bytes, stream, &kd);
+}
+
+// ---------------- participant job: mask, mask payload, shares and clerk payloads in one call ----------------
+// participate.rs:53-98 without the sealing: participant_share with the Full mask drawn in its masking kernel, the
+// shares in handle scratch and the recipient's mask payload encoded next to the clerks'.
+}  // extern "C"
+
+namespace {
+
+// Every *_last_launch record a participant job's reused code writes (on ordinals[0], where it runs): a call that
+// fails puts them back.
+struct ParticipantRecords {
+    sda::ChachaLaunchInfo chacha;
+    bool chacha_split;
+    sda_engine::ParticipantLaunchInfo participant;
+    sda_engine::ParticipantJobLaunchInfo job;
+    uint32_t keyed_path;
+    uint64_t keyed_staged_bytes;
+    explicit ParticipantRecords(const sda_engine* h)
+        : chacha(h->chacha_last), chacha_split(h->chacha_split), participant(h->participant_last),
+          job(h->participant_job_last), keyed_path(h->keyed_path), keyed_staged_bytes(h->keyed_staged_bytes) {}
+    void restore(sda_engine* h) const {
+        h->chacha_last = chacha;
+        h->chacha_split = chacha_split;
+        h->participant_last = participant;
+        h->participant_job_last = job;
+        h->keyed_path = keyed_path;
+        h->keyed_staged_bytes = keyed_staged_bytes;
+    }
+};
+
+// What both job forms settle before any work: the schemes' kinds, the payload bounds and the width of the rows.
+struct ParticipantJobSetup {
+    sda::ParticipantJobShape shape;
+    uint64_t row_bound = 0, mask_bound = 0;   // sda_participant_job_payload_bound
+    bool packed = false, full = false, chacha = false;
+    uint32_t share_bytes = 8, mask_bytes = 0; // of a share / a Full mask value in handle scratch
+    uint32_t mask_route = 0;                  // sda_participant_job_last_launch
+};
+
+sda_status participant_job_setup(const sda_masking_scheme* ms, const sda_sharing_scheme* ss, uint64_t D,
+                                 uint32_t mask_stream_id, uint32_t share_stream_id, ParticipantJobSetup* s) {
+    if (ms->kind != SDA_MASKING_NONE && ms->kind != SDA_MASKING_FULL && ms->kind != SDA_MASKING_CHACHA)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "unknown masking scheme kind");
+    if (ss->kind != SDA_SHARING_ADDITIVE && ss->kind != SDA_SHARING_PACKED_SHAMIR)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "unknown sharing scheme kind");
+    s->packed = ss->kind == SDA_SHARING_PACKED_SHAMIR;
+    s->full = ms->kind == SDA_MASKING_FULL;
+    s->chacha = ms->kind == SDA_MASKING_CHACHA;
+    if (ss->share_count > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 clerks");
+    // the key contract: one (key, stream_id) pair must not serve the mask and the shares
+    if (s->full && mask_stream_id == share_stream_id)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "mask_stream_id and share_stream_id must differ");
+    s->shape = {ms->kind, ms->modulus, (ms->seed_bitsize + 31) / 32, s->packed, ss->modulus,
+                s->packed ? ss->secret_count : 1, ss->share_count};
+    if (!sda::participant_job_bound(s->shape, D, &s->row_bound, &s->mask_bound))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "the payload bound does not fit 64 bits");
+    // int32 rows wherever they fit by construction (sda_participant_share32_keyed_dev's rule)
+    s->share_bytes = s->packed || ss->modulus <= (int64_t)1 << 31 ? 4 : 8;
+    s->mask_bytes = s->full ? (ms->modulus <= (int64_t)1 << 31 ? 4 : 8) : 0;
+    s->mask_route = s->full ? (s->mask_bytes == 8 ? 1u : 2u) : s->chacha ? 3u : 0u;
+    return SDA_OK;
+}
+
+// chacha.rs:48-50: the mask is the seed words `as i64`; their encoding (sodium.rs:36-41) made on the host
+std::vector<uint8_t> encode_seed_words(const uint32_t* seed, uint64_t words) {
+    std::vector<uint8_t> out;
+    out.reserve(words * sda::kSeedWordBytes);
+    for (uint64_t i = 0; i < words; ++i) {
+        uint64_t z = (uint64_t)seed[i] << 1;                // zigzag of a value >= 0
+        do {
+            const uint8_t b = (uint8_t)(z & 127);
+            z >>= 7;
+            out.push_back(z ? (uint8_t)(b | 128) : b);
+        } while (z);
+    }
+    return out;
+}
+
+// The call's (a tile's) share rows [n][B] and the Full mask row [D] behind them, in h->job_shares.
+struct JobRows {
+    int64_t* sh64 = nullptr;
+    int32_t* sh32 = nullptr;
+    int64_t* mask64 = nullptr;
+    int32_t* mask32 = nullptr;
+};
+sda_status job_rows(sda_engine* h, const ParticipantJobSetup& s, uint64_t n, uint64_t B, uint64_t D, JobRows* r) {
+    uint64_t shares, mask;
+    if (__builtin_mul_overflow(n, B, &shares) || __builtin_mul_overflow(shares, (uint64_t)s.share_bytes, &shares) ||
+        __builtin_mul_overflow(D, (uint64_t)s.mask_bytes, &mask) || shares > (uint64_t)1 << 62 || mask > (uint64_t)1 << 62)
+        return fail(SDA_ERR_OUT_OF_MEMORY, "the share rows do not fit the address space");
+    if (sda_status e = ensure(&h->job_shares, &h->job_shares_bytes, rup(shares) + rup(mask) + 256)) return e;
+    char* base = static_cast<char*>(h->job_shares);
+    (s.share_bytes == 4 ? (void)(r->sh32 = reinterpret_cast<int32_t*>(base))
+                        : (void)(r->sh64 = reinterpret_cast<int64_t*>(base)));
+    if (s.mask_bytes == 4) r->mask32 = reinterpret_cast<int32_t*>(base + rup(shares));
+    if (s.mask_bytes == 8) r->mask64 = reinterpret_cast<int64_t*>(base + rup(shares));
+    return SDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+sda_status sda_participant_job_payload_bound(const sda_masking_scheme* ms, const sda_sharing_scheme* ss,
+                                             uint64_t dimension, uint64_t* clerk_row_bound, uint64_t* mask_bound) {
+    SDA_ENTRY;
+    if (!ms || !ss || !clerk_row_bound || !mask_bound) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    ParticipantJobSetup s;
+    if (sda_status e = participant_job_setup(ms, ss, dimension, 0, 1, &s)) return e;
+    *clerk_row_bound = s.row_bound;
+    *mask_bound = s.mask_bound;
+    return ok();
+}
+
+sda_status sda_participant_job_dev(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed,
+                                   uint64_t seed_words, const sda_sharing_scheme* ss, const int64_t* secrets,
+                                   uint64_t dimension, const uint32_t* key, uint32_t mask_stream_id,
+                                   uint32_t share_stream_id, int32_t mode, uint8_t* payload, uint64_t payload_cap,
+                                   uint64_t* payload_row_bytes, uint8_t* mask_payload, uint64_t mask_payload_cap,
+                                   uint64_t* mask_payload_len, void* stream) {
+    SDA_ENTRY;
+    const uint64_t D = dimension;
+    if (!h || !ms || !ss || !key || !mask_payload_len || (ss->share_count && !payload_row_bytes) || (D && !secrets))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    ParticipantJobSetup s;
+    if (sda_status e = participant_job_setup(ms, ss, D, mask_stream_id, share_stream_id, &s)) return e;
+    const uint64_t n = ss->share_count;
+    uint64_t all_rows;
+    if (__builtin_mul_overflow(n, s.row_bound, &all_rows))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "the payload bound does not fit 64 bits");
+    if (payload_cap < all_rows || mask_payload_cap < s.mask_bound) {
+        for (uint64_t c = 0; c < n; ++c) payload_row_bytes[c] = s.row_bound;
+        *mask_payload_len = s.mask_bound;
+        return fail(SDA_ERR_INVALID_ARGUMENT, "payload_cap or mask_payload_cap is below the bound of "
+                                              "sda_participant_job_payload_bound");
+    }
+    if ((all_rows && !payload) || (s.mask_bound && !mask_payload) || (s.chacha && seed_words && !seed))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = pick(h, stream);
+    const uint64_t k = s.packed ? std::max<uint64_t>(ss->secret_count, 1) : 1;
+    const uint64_t B = D / k + (D % k ? 1 : 0);
+    JobRows rows;
+    if (sda_status e = job_rows(h, s, n, B, D, &rows)) return e;
+    const ParticipantRecords before(h);
+    const KeyedDraws kd{key, share_stream_id};
+    ParticipantJobArgs job;
+    if (s.full) {
+        job.mask_key = key;
+        job.mask_stream_id = mask_stream_id;
+        job.mask64 = rows.mask64;
+        job.mask32 = rows.mask32;
+    }
+    uint64_t mask_len = 0;
+    sda_status e = participant_share(h, ms, seed, seed_words, nullptr, ss, secrets, D, nullptr, mode, rows.sh64,
+                                     rows.sh32, payload, payload_cap, payload_row_bytes, stream, &kd, &job);
+    if (!e && s.chacha && seed_words != s.shape.seed_words)
+        e = fail(SDA_ERR_PRECONDITION, "expected %llu seed words", (unsigned long long)s.shape.seed_words);
+    // the recipient's mask payload (participate.rs:56-72)
+    if (!e && s.full && D)
+        e = rows.mask32 ? encode_rows(h, rows.mask32, 1, D, D, mask_payload, mask_payload_cap, &mask_len, st,
+                                      "mask_payload_cap")
+                        : encode_rows(h, rows.mask64, 1, D, D, mask_payload, mask_payload_cap, &mask_len, st,
+                                      "mask_payload_cap");
+    if (!e && s.chacha && seed_words) {
+        const std::vector<uint8_t> bytes = encode_seed_words(seed, seed_words);
+        mask_len = bytes.size();
+        hipError_t he = hipMemcpyAsync(mask_payload, bytes.data(), bytes.size(), hipMemcpyHostToDevice, st);
+        if (he == hipSuccess) he = hipStreamSynchronize(st);             // `bytes` goes out of scope
+        if (he != hipSuccess) {
+            (void)hipGetLastError();
+            e = fail(SDA_ERR_DEVICE, "the mask payload's copy failed: %s", hipGetErrorString(he));
+        }
+    }
+    if (e) {
+        before.restore(h);
+        return e;
+    }
+    *mask_payload_len = mask_len;
+    if (D) h->participant_job_last = {s.mask_route, h->participant_last.share_route, s.share_bytes, 1};
+    return ok();
+}
+
+sda_status sda_participant_job(sda_engine* h, const sda_masking_scheme* ms, const uint32_t* seed, uint64_t seed_words,
+                               const sda_sharing_scheme* ss, const int64_t* secrets, uint64_t dimension,
+                               const uint32_t* key, uint32_t mask_stream_id, uint32_t share_stream_id, int32_t mode,
+                               uint8_t* const* clerk_payloads, const uint64_t* clerk_caps, uint64_t* clerk_lens,
+                               uint8_t* mask_payload, uint64_t mask_cap, uint64_t* mask_len) {
+    SDA_ENTRY;
+    const uint64_t D = dimension;
+    if (!h || !ms || !ss || !key || !mask_len || (D && !secrets) ||
+        (ss->share_count && (!clerk_payloads || !clerk_caps || !clerk_lens)))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    ParticipantJobSetup s;
+    if (sda_status e = participant_job_setup(ms, ss, D, mask_stream_id, share_stream_id, &s)) return e;
+    const uint64_t n = ss->share_count;
+    bool small = mask_cap < s.mask_bound;
+    for (uint64_t c = 0; c < n; ++c) small = small || clerk_caps[c] < s.row_bound;
+    if (small) {
+        for (uint64_t c = 0; c < n; ++c) clerk_lens[c] = s.row_bound;
+        *mask_len = s.mask_bound;
+        return fail(SDA_ERR_INVALID_ARGUMENT, "a clerk_caps entry or mask_cap is below the bound of "
+                                              "sda_participant_job_payload_bound");
+    }
+    if ((s.mask_bound && !mask_payload) || (s.chacha && seed_words && !seed))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (uint64_t c = 0; c < n; ++c)
+        if (s.row_bound && !clerk_payloads[c])
+            return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument (clerk payload %llu)", (unsigned long long)c);
+    HIP_TRY(hipSetDevice(h->device));
+    (void)pick(h, h->stream);
+    const ParticipantRecords before(h);
+    auto failed = [&](sda_status e) {           // nothing of this call stays queued, every record stays the previous call's
+        if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
+        (void)hipStreamSynchronize(h->stream);
+        before.restore(h);
+        return e;
+    };
+    const KeyedDraws kd{key, share_stream_id};
+    std::vector<uint64_t> lens(n, 0);           // the clerks' running offsets; the caller's arrays are set at the end
+    uint64_t mlen = 0;
+    // ChaCha: the masked secrets over the whole vector first, by participant_share's masking step (the rejection
+    // count is read there, before the first tile); the tiles then share and encode them as an unmasked job
+    const int64_t* masked_all = nullptr;
+    const sda_masking_scheme no_mask = {SDA_MASKING_NONE, 0, 0, 0};
+    sda_engine::ParticipantLaunchInfo mask_rec;
+    if (s.chacha) {
+        DevArena a;
+        if (sda_status e = stage(h, rup(D * 8 + 8), &a)) return e;
+        int64_t* dsec = a.take<int64_t>(D + 1);
+        if (D) HIP_TRY(hipMemcpyAsync(dsec, secrets, D * 8, hipMemcpyHostToDevice, h->stream));
+        ParticipantJobArgs mj;
+        mj.masked_out = &masked_all;
+        if (sda_status e = participant_share(h, ms, seed, seed_words, nullptr, ss, dsec, D, nullptr, mode, nullptr,
+                                             nullptr, nullptr, 0, nullptr, h->stream, &kd, &mj))
+            return failed(e);
+        if (seed_words != s.shape.seed_words)
+            return failed(fail(SDA_ERR_PRECONDITION, "expected %llu seed words", (unsigned long long)s.shape.seed_words));
+        mask_rec = h->participant_last;
+        const std::vector<uint8_t> bytes = encode_seed_words(seed, seed_words);
+        if (!bytes.empty()) memcpy(mask_payload, bytes.data(), bytes.size());
+        mlen = bytes.size();
+    }
+    // Tiles of whole batches (Additive: columns).  Tile i + 1's secrets go up on the copy stream while tile i computes
+    // and tile i - 1's payloads come down; each half of the pinned and of the device buffer is [secrets | clerk
+    // payloads | mask payload].
+    const char* ov = getenv("SDA_PARTICIPANT_TILE_BATCHES");
+    const uint64_t override_units = ov && *ov && atoll(ov) > 0 ? (uint64_t)atoll(ov) : 0;
+    const sda::ParticipantTilePlan plan =
+        sda::participant_job_tiles(s.shape, D, s.share_bytes, host_stage_bytes(), override_units);
+    const uint64_t k = s.packed ? std::max<uint64_t>(ss->secret_count, 1) : 1;
+    const uint64_t te = std::min(D, plan.tile * k);         // secrets of a full tile
+    const size_t sec_b = s.chacha ? 0 : rup(te * 8);
+    const size_t pay_b = rup(n * plan.tile * sda::participant_share_bytes_bound(s.shape) + 64);
+    const size_t mpay_b = s.full ? rup(te * sda::participant_mask_bytes_bound(s.shape) + 64) : 0;
+    const size_t half = sec_b + pay_b + mpay_b;
+    auto run_tiles = [&]() -> sda_status {
+        if (plan.tiles) {
+            if (sda_status e = host_stream_ensure(h, half, 0)) return e;
+            for (int b = 0; b < 2; ++b)
+                if (!h->d2h_done[b]) HIP_TRY(hipEventCreateWithFlags(&h->d2h_done[b], hipEventDisableTiming));
+        }
+        uint8_t* hp[2] = {static_cast<uint8_t*>(h->hs_pin), static_cast<uint8_t*>(h->hs_pin) + rup(half)};
+        uint8_t* dv[2] = {static_cast<uint8_t*>(h->hs_dev), static_cast<uint8_t*>(h->hs_dev) + rup(half)};
+        std::vector<uint64_t> row_bytes[2] = {std::vector<uint64_t>(n + 1, 0), std::vector<uint64_t>(n + 1, 0)};
+        uint64_t mask_bytes[2] = {0, 0};
+        auto tile_range = [&](uint64_t i, uint64_t* u0, uint64_t* s0, uint64_t* ds) {
+            *u0 = i * plan.tile;
+            *s0 = *u0 * k;
+            *ds = std::min(D, std::min(plan.units, *u0 + plan.tile) * k) - *s0;   // the last batch may be short
+        };
+        auto upload = [&](uint64_t i) -> sda_status {
+            uint64_t u0, s0, ds;
+            tile_range(i, &u0, &s0, &ds);
+            const int b = (int)(i & 1);
+            memcpy(hp[b], secrets + s0, ds * 8);
+            HIP_TRY(hipMemcpyAsync(dv[b], hp[b], ds * 8, hipMemcpyHostToDevice, h->copy_stream));
+            HIP_TRY(hipEventRecord(h->h2d_done[b], h->copy_stream));
+            return SDA_OK;
+        };
+        auto drain = [&](uint64_t i) -> sda_status {            // tile i's payloads: pinned memory -> the caller's blobs
+            const int b = (int)(i & 1);
+            HIP_TRY(hipEventSynchronize(h->d2h_done[b]));
+            const uint8_t* src = hp[b] + sec_b;
+            for (uint64_t c = 0; c < n; ++c) {
+                if (row_bytes[b][c]) memcpy(clerk_payloads[c] + lens[c], src, row_bytes[b][c]);
+                lens[c] += row_bytes[b][c];
+                src += row_bytes[b][c];
+            }
+            if (mask_bytes[b]) memcpy(mask_payload + mlen, hp[b] + sec_b + pay_b, mask_bytes[b]);
+            mlen += mask_bytes[b];
+            return SDA_OK;
+        };
+        if (!s.chacha && plan.tiles)
+            if (sda_status e = upload(0)) return e;
+        for (uint64_t i = 0; i < plan.tiles; ++i) {
+            uint64_t u0, s0, ds;
+            tile_range(i, &u0, &s0, &ds);
+            const int b = (int)(i & 1);
+            // the other half's secrets: tile i - 1 has computed (every tile ends with the wait for its payload sizes)
+            if (!s.chacha && i + 1 < plan.tiles)
+                if (sda_status e = upload(i + 1)) return e;
+            if (!s.chacha) HIP_TRY(hipStreamWaitEvent(h->stream, h->h2d_done[b], 0));
+            const uint64_t tb = std::min(plan.units, u0 + plan.tile) - u0;
+            JobRows rows;
+            if (sda_status e = job_rows(h, s, n, tb, ds, &rows)) return e;
+            ParticipantJobArgs job;
+            job.first = u0;
+            if (s.full) {
+                job.mask_key = key;
+                job.mask_stream_id = mask_stream_id;
+                job.mask64 = rows.mask64;
+                job.mask32 = rows.mask32;
+            }
+            const int64_t* tsec = s.chacha ? masked_all + s0 : reinterpret_cast<const int64_t*>(dv[b]);
+            uint8_t* dpay = dv[b] + sec_b;
+            // this half's payload buffers: tile i - 2 was drained while tile i - 1 computed
+            if (sda_status e = participant_share(h, s.chacha ? &no_mask : ms, seed, seed_words, nullptr, ss, tsec, ds, nullptr,
+                                                 mode, rows.sh64, rows.sh32, dpay, pay_b, row_bytes[b].data(), h->stream,
+                                                 &kd, &job))
+                return e;
+            mask_bytes[b] = 0;
+            if (s.full && ds)
+                if (sda_status e = rows.mask32 ? encode_rows(h, rows.mask32, 1, ds, ds, dpay + pay_b, mpay_b, &mask_bytes[b],
+                                                             h->stream, "the mask payload's tile")
+                                               : encode_rows(h, rows.mask64, 1, ds, ds, dpay + pay_b, mpay_b, &mask_bytes[b],
+                                                             h->stream, "the mask payload's tile"))
+                    return e;
+            // both encodes have been waited for: the copy stream may read the payloads now
+            uint64_t total = 0;
+            for (uint64_t c = 0; c < n; ++c) total += row_bytes[b][c];
+            if (total) HIP_TRY(hipMemcpyAsync(hp[b] + sec_b, dpay, total, hipMemcpyDeviceToHost, h->copy_stream));
+            if (mask_bytes[b])
+                HIP_TRY(hipMemcpyAsync(hp[b] + sec_b + pay_b, dpay + pay_b, mask_bytes[b], hipMemcpyDeviceToHost,
+                                       h->copy_stream));
+            HIP_TRY(hipEventRecord(h->d2h_done[b], h->copy_stream));
+            if (i >= 1)
+                if (sda_status e = drain(i - 1)) return e;
+        }
+        if (plan.tiles)
+            if (sda_status e = drain(plan.tiles - 1)) return e;
+        return SDA_OK;
+    };
+    if (sda_status e = run_tiles()) return failed(e);
+    for (uint64_t c = 0; c < n; ++c) clerk_lens[c] = lens[c];
+    *mask_len = mlen;
+    if (D) {
+        if (s.chacha) {                         // the tiles ran as an unmasked job: the mask step's routes stand
+            h->participant_last.mask_route = mask_rec.mask_route;
+            h->participant_last.passes = mask_rec.passes;
+        }
+        h->participant_job_last = {s.mask_route, h->participant_last.share_route, s.share_bytes, plan.tiles};
+    }
+    return finish(h);
+}
+
+sda_status sda_participant_job_last_launch(sda_engine* h, uint32_t* mask_route, uint32_t* share_route,
+                                           uint32_t* share_bytes, uint64_t* tiles) {
+    SDA_ENTRY;
+    if (!h || !mask_route || !share_route || !share_bytes || !tiles) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    // a host-side record, final when the call that made it returned: nothing to wait for
+    const sda_engine::ParticipantJobLaunchInfo& r = h->participant_job_last;
+    *mask_route = r.mask_route;
+    *share_route = r.share_route;
+    *share_bytes = r.share_bytes;
+    *tiles = r.tiles;
+    return ok();
 }
 
 }  // extern "C"

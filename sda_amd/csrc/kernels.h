@@ -370,6 +370,15 @@ hipError_t launch_additive_generate_keyed(const uint32_t* key_host, uint32_t str
                                           const int64_t* secrets, uint64_t D, uint64_t n, int64_t modulus,
                                           int64_t* out64, int32_t* out32, uint64_t out_stride, hipStream_t s);
 
+// ---- mask_keyed.hip ----
+// Full masking with the mask drawn in the kernel: for p < count, mask[p] = draw(first + p) of launch_draws' rule at
+// bound = modulus -- into mask64, or mask32 (int32 values) when that is given -- and masked[p] =
+// (secrets[p] + mask[p]) % modulus as launch_addsub_trem computes it.  All device buffers.  The caller has checked
+// modulus >= 1 (mask32: modulus <= 2^31) and that first + count does not wrap.
+hipError_t launch_full_mask_keyed(const uint32_t* key_host, uint32_t stream_id, uint64_t first, const int64_t* secrets,
+                                  uint64_t count, int64_t modulus, int64_t* masked, int64_t* mask64, int32_t* mask32,
+                                  hipStream_t s);
+
 // ---- snapshot.hip ----
 // One blob of the snapshot transposition: len bytes from src offset to dst offset.
 struct SnapshotCopy {

@@ -93,6 +93,7 @@ PARTICIPANT_MASK_NONE = 1
 PARTICIPANT_MASK_FULL_ADD = 2
 PARTICIPANT_MASK_CHACHA_FUSED = 3
 PARTICIPANT_MASK_CHACHA_COMBINE_ADD = 4
+PARTICIPANT_MASK_FULL_KEYED = 5
 PARTICIPANT_SHARE_ADDITIVE = 1
 PARTICIPANT_SHARE_ADDITIVE_KEYED = 2
 PARTICIPANT_SHARE_PACKED = 3
@@ -108,6 +109,13 @@ RECIPIENT_JOB_MASK_CHACHA_SPLIT = 4
 RECIPIENT_JOB_SHARE_ADDITIVE = 1
 RECIPIENT_JOB_SHARE_PACKED = 2
 RecipientJobLaunch = collections.namedtuple("RecipientJobLaunch", "mask_route share_route seeds_decoded")
+
+# sda_participant_job_last_launch's mask_route codes (share_route: the PARTICIPANT_SHARE_* codes)
+PARTICIPANT_JOB_MASK_NONE = 0
+PARTICIPANT_JOB_MASK_FULL64 = 1
+PARTICIPANT_JOB_MASK_FULL32 = 2
+PARTICIPANT_JOB_MASK_CHACHA = 3
+ParticipantJobLaunch = collections.namedtuple("ParticipantJobLaunch", "mask_route share_route share_bytes tiles")
 
 # Elements one workgroup of the draws kernel produces (csrc/kernels.h kDrawsTile): the sizes at which
 # sda_draws_dev's grid gains a workgroup
@@ -244,6 +252,18 @@ SIGNATURES = [
     ("sda_participant_share32_keyed_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _u32p, C.c_uint64, _vp,
                                                 C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, _u32p, C.c_uint32,
                                                 C.c_int32, _vp, _vp, C.c_uint64, _u64p, _vp]),
+    ("sda_full_mask_keyed_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, _u32p, C.c_uint32, C.c_uint64, _vp, _vp, _vp]),
+    ("sda_full_mask_keyed32_dev", _st, [_vp, C.c_int64, _vp, C.c_uint64, _u32p, C.c_uint32, C.c_uint64, _vp, _vp,
+                                        _vp]),
+    ("sda_participant_job_payload_bound", _st, [C.POINTER(S.MaskingSchemeC), C.POINTER(S.SharingSchemeC), C.c_uint64,
+                                                _u64p, _u64p]),
+    ("sda_participant_job_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _u32p, C.c_uint64,
+                                      C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, _u32p, C.c_uint32, C.c_uint32,
+                                      C.c_int32, _vp, C.c_uint64, _u64p, _vp, C.c_uint64, _u64p, _vp]),
+    ("sda_participant_job", _st, [_vp, C.POINTER(S.MaskingSchemeC), _u32p, C.c_uint64, C.POINTER(S.SharingSchemeC),
+                                  _i64p, C.c_uint64, _u32p, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(_u8p),
+                                  _u64p, _u64p, _u8p, C.c_uint64, _u64p]),
+    ("sda_participant_job_last_launch", _st, [_vp, _u32p, _u32p, _u32p, _u64p]),
 ]
 
 _libs = {}
@@ -297,6 +317,16 @@ def _rows(rows):
     ptrs = (_i64p * max(n, 1))(*[_ptr(a) for a in arrs])
     lens = (C.c_uint64 * max(n, 1))(*[a.size for a in arrs])
     return arrs, ptrs, lens, n
+
+
+def participant_job_payload_bound(masking, sharing, dimension, lib_path: Optional[str] = None):
+    """(clerk_row_bound, mask_bound): the most bytes one clerk's payload and the mask payload of a participant job
+    over `dimension` secrets take (sda_participant_job_payload_bound).  Needs the library but no device."""
+    ms, ss = masking.c(), sharing.c()
+    row, mask = C.c_uint64(), C.c_uint64()
+    _check(load_library(lib_path).sda_participant_job_payload_bound(C.byref(ms), C.byref(ss), dimension,
+                                                                    C.byref(row), C.byref(mask)))
+    return int(row.value), int(mask.value)
 
 
 class _HbmBlock:
@@ -711,6 +741,49 @@ class Engine:
         _check(self.lib.sda_recipient_job_last_launch(self.h, *[C.byref(x) for x in v]))
         return RecipientJobLaunch(*[int(x.value) for x in v])
 
+    def participant_job_last_launch(self):
+        """ParticipantJobLaunch(mask_route, share_route, share_bytes, tiles) of the handle's last participant_job /
+        participant_job_dev of dimension > 0: the PARTICIPANT_JOB_MASK_* and PARTICIPANT_SHARE_* codes, the width of
+        the share rows in handle scratch and the host form's tiles (sda_participant_job_last_launch)."""
+        v = [C.c_uint32() for _ in range(3)]
+        tiles = C.c_uint64()
+        _check(self.lib.sda_participant_job_last_launch(self.h, *[C.byref(x) for x in v], C.byref(tiles)))
+        return ParticipantJobLaunch(*[int(x.value) for x in v], int(tiles.value))
+
+    @staticmethod
+    def participant_job_payload_bound(masking, sharing, dimension):
+        """The module's participant_job_payload_bound."""
+        return participant_job_payload_bound(masking, sharing, dimension)
+
+    def participant_job(self, masking, sharing, secrets, key, mask_stream_id, share_stream_id, seed=None,
+                        mode=REVEAL_EXACT, clerk_caps=None, mask_cap=None):
+        """The participant's whole job on host buffers (sda_participant_job): returns (clerk_payloads, mask_payload)
+        as bytes -- what Encryptor::encrypt seals for each clerk and for the recipient.  clerk_caps / mask_cap
+        override the capacities (default: the payload bound); a failing call raises SdaError carrying `.clerk_lens`
+        and `.mask_len` as the call left them."""
+        ms, ss = masking.c(), sharing.c()
+        sec = _arr(secrets)
+        sd = _arr(seed if seed is not None else [], np.uint32)
+        k = self._key(key) if key is not None else None
+        n = sharing.output_size()
+        row, mb = self.participant_job_payload_bound(masking, sharing, sec.size)
+        caps = _arr(clerk_caps if clerk_caps is not None else [row] * n, np.uint64)
+        mcap = mb if mask_cap is None else mask_cap
+        bufs = [np.zeros(max(int(c), 1), np.uint8) for c in caps]
+        ptrs = (_u8p * max(n, 1))(*[_ptr(b, _u8p) for b in bufs])
+        lens = np.zeros(max(n, 1), np.uint64)
+        mbuf = np.zeros(max(mcap, 1), np.uint8)
+        mlen = C.c_uint64(0)
+        try:
+            _check(self.lib.sda_participant_job(self.h, C.byref(ms), _ptr(sd, _u32p), sd.size, C.byref(ss), _ptr(sec),
+                                                sec.size, _ptr(k, _u32p) if k is not None else None, mask_stream_id,
+                                                share_stream_id, mode, ptrs, _ptr(caps, _u64p) if n else None,
+                                                _ptr(lens, _u64p), _ptr(mbuf, _u8p), mcap, C.byref(mlen)))
+        except SdaError as e:
+            e.clerk_lens, e.mask_len = [int(x) for x in lens[:n]], int(mlen.value)
+            raise
+        return [bufs[c][: int(lens[c])].tobytes() for c in range(n)], mbuf[: mlen.value].tobytes()
+
     def packed_keyed_last_launch(self):
         """(path, staged_bytes) of the handle's last keyed packed-Shamir launch: path 0 none yet, 1 the draws were
         made in the share kernels, 2 staged in device scratch; staged_bytes the draw bytes that crossed HBM
@@ -813,6 +886,39 @@ class Engine:
         _check(self.lib.sda_additive_generate_keyed32_dev(self.h, modulus, share_count, secrets_ptr, dimension,
                                                           _ptr(k, _u32p) if k is not None else None, stream_id,
                                                           first_column, out_ptr, out_stride, stream))
+
+    def full_mask_keyed_dev(self, modulus, secrets_ptr, dimension, key, stream_id, masked_ptr, mask_ptr, first=0,
+                            mask32=False, stream=None):
+        """Full masking with the mask drawn in the kernel (sda_full_mask_keyed_dev): mask[d] = draw(first + d) of
+        (key, stream_id) at bound = modulus, masked[d] = (secrets[d] + mask[d]) % modulus; all device pointers, the
+        mask as int32 values with mask32 (modulus <= 2^31).  key=None passes a NULL key (the status tests)."""
+        k = self._key(key) if key is not None else None
+        fn = self.lib.sda_full_mask_keyed32_dev if mask32 else self.lib.sda_full_mask_keyed_dev
+        _check(fn(self.h, modulus, secrets_ptr, dimension, _ptr(k, _u32p) if k is not None else None, stream_id,
+                  first, masked_ptr, mask_ptr, stream))
+
+    def participant_job_dev(self, masking, sharing, secrets_ptr, dimension, key, mask_stream_id, share_stream_id,
+                            payload_ptr, payload_cap, mask_payload_ptr, mask_payload_cap, seed=None,
+                            mode=REVEAL_EXACT, stream=None):
+        """The participant's whole job on device buffers (sda_participant_job_dev); returns (payload_row_bytes [n],
+        mask_payload_len).  A failing call raises SdaError carrying `.row_bytes` and `.mask_len` as the call left
+        them.  key=None passes a NULL key (the status tests)."""
+        ms, ss = masking.c(), sharing.c()
+        sd = _arr(seed if seed is not None else [], np.uint32)
+        k = self._key(key) if key is not None else None
+        n = sharing.output_size()
+        rb = np.zeros(max(n, 1), np.uint64)
+        mlen = C.c_uint64(0)
+        try:
+            _check(self.lib.sda_participant_job_dev(self.h, C.byref(ms), _ptr(sd, _u32p), sd.size, C.byref(ss),
+                                                    secrets_ptr, dimension, _ptr(k, _u32p) if k is not None else None,
+                                                    mask_stream_id, share_stream_id, mode, payload_ptr, payload_cap,
+                                                    _ptr(rb, _u64p), mask_payload_ptr, mask_payload_cap,
+                                                    C.byref(mlen), stream))
+        except SdaError as e:
+            e.row_bytes, e.mask_len = rb[:n].copy(), int(mlen.value)
+            raise
+        return rb[:n], int(mlen.value)
 
     def chacha_mask_combine_dev(self, modulus, dimension, seeds_ptr, w, n_seeds, out_ptr, stream=None):
         _check(self.lib.sda_chacha_mask_combine_dev(self.h, modulus, dimension, seeds_ptr, w, n_seeds, out_ptr,
