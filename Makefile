@@ -14,7 +14,7 @@ LIB     ?= sda_amd/libsda_engine.so
 GEN_PARTS    := 3_2 9_2 9_4 9_8 27_2 27_4 27_8 27_16 81_2 81_4 81_8 81_16 81_32 81_64
 REVEAL_PARTS := 8 16 32 64 96
 PLAIN   := combine elementwise chacha codec_decode codec_encode snapshot packed_wide draws additive_keyed mask_keyed recipient_job
-HOST    := engine engine_dev hbm engine_codec engine_pipelines engine_host
+HOST    := engine engine_dev hbm engine_codec engine_recipient engine_participant engine_host
 OBJS    := $(patsubst %,$(OBJDIR)/%.o,$(PLAIN)) $(patsubst %,$(OBJDIR)/%.o,$(HOST)) \
            $(OBJDIR)/packed_gen.o $(patsubst %,$(OBJDIR)/packed_gen_%.o,$(GEN_PARTS)) \
            $(OBJDIR)/packed_reveal.o $(patsubst %,$(OBJDIR)/packed_reveal_%.o,$(REVEAL_PARTS))

@@ -152,8 +152,8 @@ bool chacha_fast_path(int64_t m) {
 // 2^62, high rejection rates, or a log overflow) the exact stream path.
 // Every ChaCha launch leaves how it ran in the handle (sda_chacha_last_launch).
 void record_chacha(sda_engine* h, const sda::ChachaLaunchInfo& info) {
-    h->chacha_last = info;
-    h->chacha_split = false;
+    h->last.chacha = info;
+    h->last.chacha_split = false;
 }
 
 sda_status chacha_combine(sda_engine* h, int64_t m, uint64_t D, const uint32_t* seeds, uint32_t w, uint64_t n,
@@ -203,11 +203,11 @@ sda_status chacha_combine_end(sda_engine* h, const PendingChacha& pc, hipStream_
     int fixups = 0;
     HIP_TRY(sda::resolve_chacha_mask_combine(pc.m, pc.D, pc.seeds, pc.w, pc.n, pc.out, h->work, st, *h->rej_host,
                                              &overflow, &fixups));
-    h->chacha_last.fixups = (uint64_t)fixups;    // the late resolve of the plan chacha_combine_begin recorded
+    h->last.chacha.fixups = (uint64_t)fixups;    // the late resolve of the plan chacha_combine_begin recorded
     if (!overflow) return SDA_OK;
     if (sda_status e = ensure(&h->work, &h->work_bytes, sda::chacha_stream_work_bytes(pc.D, pc.n, pc.m))) return e;
     HIP_TRY(sda::launch_chacha_streams_combine(pc.m, pc.D, pc.seeds, pc.w, pc.n, pc.out, h->work, st));
-    h->chacha_last.path = sda::kChachaOverflow;
+    h->last.chacha.path = sda::kChachaOverflow;
     return SDA_OK;
 }
 
@@ -738,11 +738,11 @@ sda_status sda_chacha_last_launch(sda_engine* h, uint32_t* path, uint64_t* grid_
     SDA_ENTRY;
     if (!h || !path || !grid_y || !fixups) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     // host-side records, final when the call that made them returned: nothing to wait for
-    *path = h->chacha_last.path;
-    *grid_y = h->chacha_last.grid_y;
-    uint64_t total = h->chacha_last.fixups;
-    if (h->chacha_split)
-        for (size_t g = 1; g < h->sub.size(); ++g) total += h->sub[g]->chacha_last.fixups;   // sub[0] is the handle
+    *path = h->last.chacha.path;
+    *grid_y = h->last.chacha.grid_y;
+    uint64_t total = h->last.chacha.fixups;
+    if (h->last.chacha_split)
+        for (size_t g = 1; g < h->sub.size(); ++g) total += h->sub[g]->last.chacha.fixups;   // sub[0] is the handle
     *fixups = total;
     return ok();
 }
@@ -752,10 +752,10 @@ sda_status sda_codec_last_launch(sda_engine* h, uint32_t* path, uint32_t* width,
     SDA_ENTRY;
     if (!h || !path || !width || !fell_back || !passes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     // a host-side record, final when the call that made it returned: nothing to wait for
-    *path = h->codec_last.path;
-    *width = h->codec_last.width;
-    *fell_back = h->codec_last.fell_back;
-    *passes = h->codec_last.passes;
+    *path = h->last.codec.path;
+    *width = h->last.codec.width;
+    *fell_back = h->last.codec.fell_back;
+    *passes = h->last.codec.passes;
     return ok();
 }
 
@@ -764,9 +764,9 @@ sda_status sda_clerk_job_last_launch(sda_engine* h, uint32_t* continued, uint32_
     SDA_ENTRY;
     if (!h || !continued || !encode_route || !encode_chunks) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     // a host-side record, final when the call that made it returned: nothing to wait for
-    *continued = h->clerk_job_last.continued;
-    *encode_route = h->clerk_job_last.encode_route;
-    *encode_chunks = h->clerk_job_last.encode_chunks;
+    *continued = h->last.clerk_job.continued;
+    *encode_route = h->last.clerk_job.encode_route;
+    *encode_chunks = h->last.clerk_job.encode_chunks;
     return ok();
 }
 
@@ -778,7 +778,7 @@ sda_status sda_combine_last_launch(sda_engine* h, uint32_t* kind, uint32_t* elem
         return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     // a host-side record, final when the call that made it returned: nothing to wait for.  A multi-device handle
     // is its own first device (sub[0]): its record is that device's
-    const sda::CombineLaunchInfo& c = h->combine_last;
+    const sda::CombineLaunchInfo& c = h->last.combine;
     *kind = c.kind;
     *elem_bytes = c.elem_bytes;
     *vec = c.vec;
@@ -797,7 +797,7 @@ sda_status sda_snapshot_last_launch(sda_engine* h, uint64_t* blobs, uint64_t* ch
     if (!h || !blobs || !chunks || !grid || !chunk_bytes || !shifts)
         return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     // a host-side record, final when the call that made it returned: nothing to wait for
-    const sda::SnapshotLaunchInfo& s = h->snap_last;
+    const sda::SnapshotLaunchInfo& s = h->last.snapshot;
     *blobs = s.blobs;
     *chunks = s.chunks;
     *grid = s.grid;
@@ -812,7 +812,7 @@ sda_status sda_recipient_last_launch(sda_engine* h, uint32_t* mask_kind, uint32_
     if (!h || !mask_kind || !reveal_mode || !fell_back || !compact || !unmask_launches)
         return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     // a host-side record, final when the call that made it returned: nothing to wait for
-    const sda_engine::RecipientLaunchInfo& r = h->recipient_last;
+    const sda_engine::RecipientLaunchInfo& r = h->last.recipient;
     *mask_kind = r.mask_kind;
     *reveal_mode = r.reveal_mode;
     *fell_back = r.fell_back;
@@ -825,7 +825,7 @@ sda_status sda_participant_last_launch(sda_engine* h, uint32_t* mask_route, uint
     SDA_ENTRY;
     if (!h || !mask_route || !share_route || !passes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     // a host-side record, final when the call that made it returned: nothing to wait for
-    const sda_engine::ParticipantLaunchInfo& r = h->participant_last;
+    const sda_engine::ParticipantLaunchInfo& r = h->last.participant;
     *mask_route = r.mask_route;
     *share_route = r.share_route;
     *passes = r.passes;

@@ -38,16 +38,21 @@ static sda_status encode_dev(sda_engine* h, const T* vals, uint64_t rows, uint64
     return ok();
 }
 
-// Shared with the recipient job (engine_pipelines.cpp): declared in engine_internal.h.
+// Shared with the recipient job (engine_recipient.cpp): declared in engine_internal.h.
 namespace sda_host {
+
+sda_status check_blob_buffer(const uint8_t* bytes, const uint64_t* blob_off, uint64_t n_blobs) {
+    if (((uintptr_t)bytes & 15) != 0) return fail(SDA_ERR_INVALID_ARGUMENT, "byte buffer must be 16-byte aligned");
+    for (uint64_t b = 0; b < n_blobs; ++b)
+        if (blob_off[b + 1] < blob_off[b]) return fail(SDA_ERR_INVALID_ARGUMENT, "blob offsets must be non-decreasing");
+    return SDA_OK;
+}
 
 // Plan + count N device-resident blobs; counts[n] on the host.
 sda_status codec_count(sda_engine* h, const uint8_t* bytes, const uint64_t* blob_off, uint64_t n_blobs,
                        sda::VarintPlan* plan, uint64_t* counts, bool* irregular, hipStream_t st,
                        bool sub_counts, bool* long_any) {
-    if (((uintptr_t)bytes & 15) != 0) return fail(SDA_ERR_INVALID_ARGUMENT, "byte buffer must be 16-byte aligned");
-    for (uint64_t b = 0; b < n_blobs; ++b)
-        if (blob_off[b + 1] < blob_off[b]) return fail(SDA_ERR_INVALID_ARGUMENT, "blob offsets must be non-decreasing");
+    if (sda_status e = check_blob_buffer(bytes, blob_off, n_blobs)) return e;
     sda::varint_plan(blob_off, n_blobs, plan);
     if (sda_status e = ensure(&h->codec_work, &h->codec_work_bytes,
                               sda::varint_decode_work_bytes(plan->regions, n_blobs)))
@@ -69,7 +74,7 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
     *out_len = prior;
     if (job && job->payload_len) *job->payload_len = 0;
     // sda_codec_last_launch: NONE until this call returns SDA_OK; `info` collects each decision where it is taken
-    h->codec_last = sda::CodecLaunchInfo();
+    h->last.codec = sda::CodecLaunchInfo();
     sda::CodecLaunchInfo info;
     // sda_clerk_job_last_launch: written by conclude() when the call ends well after launching something
     sda_engine::ClerkJobLaunchInfo rec;
@@ -89,7 +94,7 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
         } else if (job->payload) {
             rec.encode_route = 2;
         }
-        if (launched) h->clerk_job_last = rec;
+        if (launched) h->last.clerk_job = rec;
         return SDA_OK;
     };
     if (cont) {
@@ -134,9 +139,7 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
     // matrix path; any element longer than 5 bytes or outside int32 (malformed or raw i64 payloads)
     // falls back to it as well.
     if (narrow_ok && !want_fused && !(path && strcmp(path, "matrix") == 0)) {
-        if (((uintptr_t)bytes & 15) != 0) return fail(SDA_ERR_INVALID_ARGUMENT, "byte buffer must be 16-byte aligned");
-        for (uint64_t b = 0; b < n_blobs; ++b)
-            if (blob_off[b + 1] < blob_off[b]) return fail(SDA_ERR_INVALID_ARGUMENT, "blob offsets must be non-decreasing");
+        if (sda_status e = check_blob_buffer(bytes, blob_off, n_blobs)) return e;
         sda::varint_plan(blob_off, n_blobs, &plan);
         if (sda_status e = ensure(&h->codec_work, &h->codec_work_bytes,
                                   sda::varint_decode_work_bytes(plan.regions, n_blobs)))
@@ -169,7 +172,7 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
             int64_t mm = 1;
             if (sda_status e = check(dim, &mm)) return e;
             *out_len = dim;
-            h->codec_last = info;
+            h->last.codec = info;
             if (!job) return SDA_OK;
             if (job->payload && dim && !sj.encoded) return conclude(dim, true);      // not reached: dim > 0 queues it
             if (job->payload) {
@@ -180,7 +183,7 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
                     return fail(SDA_ERR_INVALID_ARGUMENT, "payload_cap too small (%llu bytes needed)",
                                 (unsigned long long)sj.payload_bytes);
             }
-            h->clerk_job_last = rec;
+            h->last.clerk_job = rec;
             return SDA_OK;
         }
         info = sda::CodecLaunchInfo();                 // the slot attempt wrote nothing: the count pass takes over
@@ -206,7 +209,7 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
         HIP_TRY(sda::launch_varint_decode_combine(bytes, n_blobs, plan, h->codec_work,
                                                   static_cast<uint64_t*>(h->codec_mat), dim, out, mm, long_elems, st,
                                                   &info));
-        h->codec_last = info;
+        h->last.codec = info;
         return conclude(dim, true);
     }
     if (sda_status e = ensure(&h->codec_mat, &h->codec_mat_bytes, n_blobs * dim * 8)) return e;
@@ -219,18 +222,18 @@ sda_status decode_combine(sda_engine* h, int64_t m, const uint8_t* bytes, const 
         HIP_TRY(sda::launch_varint_decode_narrow(bytes, n_blobs, plan, h->codec_work, mat32, dim, &wide, st,
                                                  &info));
         if (!wide) {
-            HIP_TRY(sda::launch_combine_exact32(mat32, n_blobs, dim, dim, out, mm, st, cont, &h->combine_last));
+            HIP_TRY(sda::launch_combine_exact32(mat32, n_blobs, dim, dim, out, mm, st, cont, &h->last.combine));
             info.path = sda::kCodecMatrix32;
-            h->codec_last = info;
+            h->last.codec = info;
             return conclude(dim, true);
         }
         info.fell_back |= sda::kCodecNarrowWide;
     }
     int64_t* mat = static_cast<int64_t*>(h->codec_mat);
     HIP_TRY(sda::launch_varint_decode(bytes, n_blobs, plan, h->codec_work, mat, dim, dim, irregular, st, &info));
-    HIP_TRY(sda::launch_combine_exact(mat, n_blobs, dim, dim, out, mm, st, cont, &h->combine_last));
+    HIP_TRY(sda::launch_combine_exact(mat, n_blobs, dim, dim, out, mm, st, cont, &h->last.combine));
     info.path = sda::kCodecMatrix64;
-    h->codec_last = info;
+    h->last.codec = info;
     return conclude(dim, true);
 }
 
@@ -325,9 +328,7 @@ sda_status sda_varint_decode_dev(sda_engine* h, const uint8_t* bytes, const uint
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = pick(h, stream);
     if (n_blobs == 0) return ok();
-    if (((uintptr_t)bytes & 15) != 0) return fail(SDA_ERR_INVALID_ARGUMENT, "byte buffer must be 16-byte aligned");
-    for (uint64_t b = 0; b < n_blobs; ++b)
-        if (blob_off[b + 1] < blob_off[b]) return fail(SDA_ERR_INVALID_ARGUMENT, "blob offsets must be non-decreasing");
+    if (sda_status e = check_blob_buffer(bytes, blob_off, n_blobs)) return e;
     sda::VarintPlan plan;
     sda::varint_plan(blob_off, n_blobs, &plan);
     if (sda_status e = ensure(&h->codec_work, &h->codec_work_bytes, sda::varint_decode_work_bytes(plan.regions, n_blobs)))
@@ -404,7 +405,7 @@ sda_status sda_clerk_job(sda_engine* h, const sda_sharing_scheme* s, const uint8
         return fail(SDA_ERR_INVALID_ARGUMENT, "payload_cap too small (%llu bytes needed)", (unsigned long long)nbytes);
     HIP_TRY(hipMemcpyAsync(payload, db, nbytes, hipMemcpyDeviceToHost, h->stream));
     if (sda_status st = finish(h)) return st;
-    h->clerk_job_last = {0u, 2u, sda::varint_encode_chunks(dim)};
+    h->last.clerk_job = {0u, 2u, sda::varint_encode_chunks(dim)};
     return SDA_OK;
 }
 
@@ -468,7 +469,7 @@ sda_status sda_snapshot_transpose_dev(sda_engine* h, const uint8_t* src, const u
     info.blobs = blobs.size();
     info.chunks = cstart.back();
     if (blobs.empty()) {
-        h->snap_last = info;
+        h->last.snapshot = info;
         return ok();
     }
     HIP_TRY(hipSetDevice(h->device));
@@ -482,7 +483,7 @@ sda_status sda_snapshot_transpose_dev(sda_engine* h, const uint8_t* src, const u
                                            reinterpret_cast<const uint64_t*>(plan + b0), blobs.size(),
                                            cstart.back(), st, &info.grid));
     HIP_TRY(hipStreamSynchronize(st));                             // the host plan vectors go out of scope
-    h->snap_last = info;
+    h->last.snapshot = info;
     return ok();
 }
 

@@ -22,8 +22,8 @@ sda_status packed_generate(sda_engine* h, const sda_sharing_scheme* s, sda::Pack
     HIP_TRY(sda::launch_packed_generate(ga, k, t, n, (uint32_t)s->modulus, (uint32_t)s->omega_secrets,
                                         (uint32_t)s->omega_shares, h->gen_tab, h->gen_log, st, &h->gen_log_used));
     if (pl.keyed_path && ga.dimension && ga.n_vectors) {        // sda_packed_keyed_last_launch
-        h->keyed_path = pl.keyed_path;
-        h->keyed_staged_bytes = pl.draw_bytes;
+        h->last.keyed_path = pl.keyed_path;
+        h->last.keyed_staged_bytes = pl.draw_bytes;
     }
     return SDA_OK;
 }
@@ -61,10 +61,10 @@ static sda_status combine_dev(sda_engine* h, int64_t modulus, const T* shares, u
     if (accumulate && n == 0) return ok();
     const uint64_t stride = n > 1 ? row_stride : dim;
     if constexpr (sizeof(T) == 8)
-        HIP_TRY(sda::launch_combine_exact(shares, n, dim, stride, out, m, pick(h, stream), accumulate, &h->combine_last));
+        HIP_TRY(sda::launch_combine_exact(shares, n, dim, stride, out, m, pick(h, stream), accumulate, &h->last.combine));
     else
         HIP_TRY(sda::launch_combine_wide32(shares, n, dim, stride, out, m, pick(h, stream), accumulate,
-                                           &h->combine_last));
+                                           &h->last.combine));
     return ok();
 }
 
@@ -150,7 +150,7 @@ sda_status sda_combine_split_dev(sda_engine* h, int64_t modulus, const int64_t* 
     if (sda_status st = modulus_abs(modulus, &m)) return st;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(sda::launch_combine_split(shares, n, dim, n > 1 ? row_stride : dim, inout, m, flags, pick(h, stream),
-                                      &h->combine_last));
+                                      &h->last.combine));
     return ok();
 }
 
@@ -181,7 +181,7 @@ sda_status sda_combine_split_replay_dev(sda_engine* h, int64_t modulus, const in
     if (sda_status st = modulus_abs(modulus, &m)) return st;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(sda::launch_combine_replay(shares, n, dim, n > 1 ? row_stride : dim, state, code, (int32_t)(2 * rank + 1),
-                                       m, pick(h, stream), &h->combine_last));
+                                       m, pick(h, stream), &h->last.combine));
     return ok();
 }
 
@@ -343,8 +343,8 @@ sda_status sda_packed_generate_keyed32_dev(sda_engine* h, const sda_sharing_sche
 sda_status sda_packed_keyed_last_launch(sda_engine* h, uint32_t* path, uint64_t* staged_bytes) {
     SDA_ENTRY;
     if (!h || !path || !staged_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    *path = h->keyed_path;
-    *staged_bytes = h->keyed_staged_bytes;
+    *path = h->last.keyed_path;
+    *staged_bytes = h->last.keyed_staged_bytes;
     return ok();
 }
 

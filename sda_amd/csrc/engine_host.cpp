@@ -124,9 +124,9 @@ static sda_status stream_combine_slice(sda_engine* h, int64_t m, const int64_t* 
             HIP_TRY(hipStreamWaitEvent(h->stream, h->h2d_done[b], 0));
             if (try32)
                 HIP_TRY(sda::launch_combine_wide32(reinterpret_cast<const int32_t*>(dt[b]), Ri, wc, wc, acc, m,
-                                                   h->stream, i > 0, &h->combine_last));
+                                                   h->stream, i > 0, &h->last.combine));
             else
-                HIP_TRY(sda::launch_combine_exact(dt[b], Ri, wc, wc, acc, m, h->stream, i > 0, &h->combine_last));
+                HIP_TRY(sda::launch_combine_exact(dt[b], Ri, wc, wc, acc, m, h->stream, i > 0, &h->last.combine));
             HIP_TRY(hipEventRecord(h->tile_free[b], h->stream));
             ++(try32 ? h->hs_tiles32 : h->hs_tiles64);
             h->hs_bytes_h2d += bytes;
@@ -286,7 +286,7 @@ sda_status chacha_combine_multi(sda_engine* h, int64_t m, uint64_t D, const std:
     if (st) return st;
     HIP_TRY(hipSetDevice(h->device));
     if (!split) return SDA_OK;
-    h->chacha_split = true;                      // every device recorded its part (sda_chacha_last_launch)
+    h->last.chacha_split = true;                      // every device recorded its part (sda_chacha_last_launch)
     if (sda_status e = ensure_comms(h)) return e;
     Rccl& r = rccl();
     NCCL_TRY(r.group_start());
@@ -332,7 +332,7 @@ sda_status host_decode_combine(sda_engine* h, int64_t m, const uint8_t* const* b
     *out_len = 0;
     if (acc_dev) *acc_dev = nullptr;
     const bool to_host = out || !acc_dev;       // the accumulator alone is wanted: no copy, no capacity check
-    h->codec_last = sda::CodecLaunchInfo();     // this path keeps no record: a stale one must not be read
+    h->last.codec = sda::CodecLaunchInfo();     // this path keeps no record: a stale one must not be read
     if (n == 0) return SDA_OK;                                        // combiner.rs:17: empty input
     const uint64_t stage = host_stage_bytes();
     struct Group { uint64_t b0, nb, bytes; };
@@ -409,7 +409,7 @@ sda_status host_decode_combine(sda_engine* h, int64_t m, const uint8_t* const* b
                 return fail(SDA_ERR_WRONG_DIMENSION, "Wrong dimension (participation %llu decodes to %llu shares, expected %llu)",
                             (unsigned long long)(g.b0 + i), (unsigned long long)counts[i], (unsigned long long)dim);
         if (dim)
-            HIP_TRY(sda::launch_combine_exact(mat, g.nb, dim, stride, acc, mm, h->stream, gi > 0, &h->combine_last));
+            HIP_TRY(sda::launch_combine_exact(mat, g.nb, dim, stride, acc, mm, h->stream, gi > 0, &h->last.combine));
         if (gi == 0) stride = std::max<uint64_t>(dim, 1);            // later groups: rows of exactly dim values
     }
     if (dim && to_host) HIP_TRY(hipMemcpyAsync(out, acc, dim * 8, hipMemcpyDeviceToHost, h->stream));

@@ -1,12 +1,13 @@
 // engine_internal.h -- what the host translation units of the C ABI (include/sda_engine.h) share: the handle, the
 // failure / call-scope plumbing, scratch management, and the helpers that more than one of them calls.
 //
-//   engine.cpp            handle life cycle, call scope, scratch, scheme helpers, the trait calls on host buffers
-//   engine_dev.cpp        the device-resident (`_dev`) entry points
-//   hbm.cpp               sda_hbm_*: HBM buffers built from fixed-size physical chunks
-//   engine_codec.cpp      the share payload codec's host side and the snapshot transposition
-//   engine_pipelines.cpp  the fused recipient and participant pipelines, the participant job
-//   engine_host.cpp       the streaming, multi-device host path (RCCL loaded at run time)
+//   engine.cpp              handle life cycle, call scope, scratch, scheme helpers, the trait calls on host buffers
+//   engine_dev.cpp          the device-resident (`_dev`) entry points
+//   hbm.cpp                 sda_hbm_*: HBM buffers built from fixed-size physical chunks
+//   engine_codec.cpp        the share payload codec's host side and the snapshot transposition
+//   engine_recipient.cpp    the fused recipient pipeline, sda_recipient_reveal and the recipient job
+//   engine_participant.cpp  the participant pipeline's steps, sda_participant_share*_dev and the participant job
+//   engine_host.cpp         the streaming, multi-device host path (RCCL loaded at run time)
 //
 // Host-side responsibilities only: argument validation with the reference's error behaviour
 // (Err strings of client/src/crypto/sharing/*.rs -> status 1..6, assert!/panic -> PRECONDITION),
@@ -45,10 +46,6 @@ struct sda_engine {
     size_t gen32_tmp_bytes = 0;
     void* keyed_draws = nullptr;  // keyed PackedShamir calls on the staged path: the n_vectors * B * t draws made on the device
     size_t keyed_draws_bytes = 0;
-    // sda_packed_keyed_last_launch: how the last keyed packed launch on this handle got its draws -- 0 none yet,
-    // 1 made in the share kernels, 2 staged through keyed_draws -- and the draw bytes that crossed HBM
-    uint32_t keyed_path = 0;
-    uint64_t keyed_staged_bytes = 0;
     void* codec_work = nullptr;   // varint codec plan / scan workspace
     size_t codec_work_bytes = 0;
     void* codec_mat = nullptr;    // decoded [N][len] matrix of the clerk decode+combine path
@@ -67,44 +64,56 @@ struct sda_engine {
     hipEvent_t order_ev = nullptr;
     bool order_ok = true;         // order_ev was recorded when the last call ended (else: host sync)
     unsigned long long* rej_host = nullptr;   // pinned: the ChaCha rejection count of a pipeline's mask
-    // sda_chacha_last_launch: how the last mask combine or participant mask on this handle ran; chacha_split:
-    // that call split its seeds over the handle's devices (chacha_combine_multi), each recording its own part
-    sda::ChachaLaunchInfo chacha_last;
-    bool chacha_split = false;
-    // sda_codec_last_launch: how the last decode -> combine on this handle produced its result (decode_combine)
-    sda::CodecLaunchInfo codec_last;
-    // sda_combine_last_launch: which combine kernel this handle (of a multi-device handle: this device) launched
-    // last and on what grid, filled by the launcher where it decides; a call that launches nothing leaves it
-    sda::CombineLaunchInfo combine_last;
-    // sda_snapshot_last_launch: what the last successful, non-sizing sda_snapshot_transpose_dev planned and launched
-    sda::SnapshotLaunchInfo snap_last;
-    // sda_clerk_job_last_launch: written when a clerk job call that launched something returns SDA_OK
+    // The launch records behind the *_last_launch getters, one block per device, so that a job that fails puts every
+    // one of them back at once (RecordsGuard).  The launchers receive &h->last.combine and so on.
     struct ClerkJobLaunchInfo {
         uint32_t continued = 0, encode_route = 0;
         uint64_t encode_chunks = 0;
-    } clerk_job_last;
-    // sda_recipient_last_launch / sda_participant_last_launch: the decisions the last role pipeline call on this
-    // handle took (engine_pipelines.cpp), written when a call of dimension > 0 returns SDA_OK
+    };
     struct RecipientLaunchInfo {
         uint32_t mask_kind = 0, reveal_mode = 0, fell_back = 0, compact = 0, unmask_launches = 0;
-    } recipient_last;
+    };
     struct ParticipantLaunchInfo {
         uint32_t mask_route = 0, share_route = 0, passes = 0;
-    } participant_last;
-    // sda_recipient_job_last_launch: where the last recipient job's mask and clerk results came from, written as
-    // recipient_last is
+    };
     struct RecipientJobLaunchInfo {
         uint32_t mask_route = 0, share_route = 0, seeds_decoded = 0;
-    } recipient_job_last;
+    };
+    struct ParticipantJobLaunchInfo {
+        uint32_t mask_route = 0, share_route = 0, share_bytes = 0;
+        uint64_t tiles = 0;
+    };
+    struct Records {
+        // sda_chacha_last_launch: how the last mask combine or participant mask on this handle ran; chacha_split:
+        // that call split its seeds over the handle's devices (chacha_combine_multi), each recording its own part
+        sda::ChachaLaunchInfo chacha;
+        bool chacha_split = false;
+        // sda_codec_last_launch: how the last decode -> combine on this handle produced its result (decode_combine)
+        sda::CodecLaunchInfo codec;
+        // sda_combine_last_launch: which combine kernel this handle (of a multi-device handle: this device) launched
+        // last and on what grid, filled by the launcher where it decides; a call that launches nothing leaves it
+        sda::CombineLaunchInfo combine;
+        // sda_snapshot_last_launch: what the last successful, non-sizing sda_snapshot_transpose_dev planned and launched
+        sda::SnapshotLaunchInfo snapshot;
+        // sda_clerk_job_last_launch: written when a clerk job call that launched something returns SDA_OK
+        ClerkJobLaunchInfo clerk_job;
+        // sda_recipient_last_launch / sda_participant_last_launch: the decisions the last role pipeline call on this
+        // handle took (engine_recipient.cpp, engine_participant.cpp), written when a call of dimension > 0 returns SDA_OK
+        RecipientLaunchInfo recipient;
+        ParticipantLaunchInfo participant;
+        // sda_recipient_job_last_launch: where the last recipient job's mask and clerk results came from, written as
+        // `recipient` is; sda_participant_job_last_launch: written when a participant job of dimension > 0 returns SDA_OK
+        RecipientJobLaunchInfo recipient_job;
+        ParticipantJobLaunchInfo participant_job;
+        // sda_packed_keyed_last_launch: how the last keyed packed launch on this handle got its draws -- 0 none yet,
+        // 1 made in the share kernels, 2 staged through keyed_draws -- and the draw bytes that crossed HBM
+        uint32_t keyed_path = 0;
+        uint64_t keyed_staged_bytes = 0;
+    } last;
     // participant job (sda_participant_job, sda_participant_job_dev): the share rows [n][B] of a call (a tile of the
     // host form) and the Full mask row behind them -- int32 where they fit by construction, else i64
     void* job_shares = nullptr;
     size_t job_shares_bytes = 0;
-    // sda_participant_job_last_launch: written when a participant job of dimension > 0 returns SDA_OK
-    struct ParticipantJobLaunchInfo {
-        uint32_t mask_route = 0, share_route = 0, share_bytes = 0;
-        uint64_t tiles = 0;
-    } participant_job_last;
     // streaming host path (host rows -> HBM in row tiles, engine_host.cpp): pinned staging and device
     // tiles, double buffered, and a copy stream so a tile's upload overlaps the previous tile's combine
     hipStream_t copy_stream = nullptr;
@@ -202,6 +211,27 @@ sda_status for_each_device(H* h, F fn) {
     return SDA_OK;
 }
 
+// Every launch record of every device of the handle, copied when the guard is made and written back when it goes
+// out of scope unless keep() was called: a job entry point makes one before its first step and calls keep() on its
+// success return, so each failing path in between leaves every *_last_launch record the previous call's.
+class RecordsGuard {
+    sda_engine* h_;
+    std::vector<sda_engine::Records> saved_;
+    bool keep_ = false;
+
+public:
+    explicit RecordsGuard(sda_engine* h) : h_(h) {
+        for (size_t g = 0; g < n_devices(h); ++g) saved_.push_back(dev_of(h, g)->last);
+    }
+    ~RecordsGuard() {
+        if (!keep_)
+            for (size_t g = 0; g < saved_.size(); ++g) dev_of(h_, g)->last = saved_[g];
+    }
+    void keep() { keep_ = true; }
+    RecordsGuard(const RecordsGuard&) = delete;
+    RecordsGuard& operator=(const RecordsGuard&) = delete;
+};
+
 // ---------------- ChaCha mask combine (engine.cpp) ----------------
 // The fast counter-mode kernel may serve modulus m; SDA_CHACHA_PATH=stream (read per call) is the test hook that
 // forces the stream path (both paths are exact; the tests compare them at sizes the oracle cannot finish)
@@ -245,6 +275,9 @@ sda_status encode_rows(sda_engine* h, const T* vals, uint64_t rows, uint64_t len
                        uint64_t dst_cap, uint64_t* row_bytes, hipStream_t st, const char* cap_name);
 
 // ---------------- payload decoder (engine_codec.cpp) ----------------
+// The checks every `_dev` call makes of a (bytes, blob_off) pair before anything reads it: the alignment, then the
+// offsets' order.  A caller that accepts any pointer with no blobs tests n_blobs first.
+sda_status check_blob_buffer(const uint8_t* bytes, const uint64_t* blob_off, uint64_t n_blobs);
 // Plan + count n_blobs device-resident blobs (the argument checks of every `_dev` byte buffer, then one wait);
 // counts[n_blobs] on the host.
 sda_status codec_count(sda_engine* h, const uint8_t* bytes, const uint64_t* blob_off, uint64_t n_blobs,

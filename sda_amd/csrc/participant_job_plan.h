@@ -1,5 +1,5 @@
 // participant_job_plan.h -- the payload bound and the tile plan of the participant job (sda_participant_job,
-// sda_participant_job_dev; engine_pipelines.cpp).  Header-only and HIP-free, so a plain C++ program can test it
+// sda_participant_job_dev; engine_participant.cpp).  Header-only and HIP-free, so a plain C++ program can test it
 // under a host sanitizer (tests/host_c).
 #pragma once
 #include <stdint.h>

@@ -1,6 +1,6 @@
-"""The decisions of the two role pipelines (sda_amd/csrc/engine_pipelines.cpp), restated once in Python: what
-sda_recipient_last_launch and sda_participant_last_launch must report for a call, and the status of every early
-return, in the order the host code takes them.  No GPU, no product import beyond the scheme descriptors.
+"""The decisions of the two role pipelines (sda_amd/csrc/engine_recipient.cpp, engine_participant.cpp), restated once
+in Python: what sda_recipient_last_launch and sda_participant_last_launch must report for a call, and the status of
+every early return, in the order the host code takes them.  No GPU, no product import beyond the scheme descriptors.
 
 tests/pipeline_matrix_cases.py builds its cases on these functions, tests/test_pipeline_matrix_plan.py holds the case
 tables against them, tests/test_gpu_pipeline_matrix.py asserts them on the device.
@@ -61,14 +61,14 @@ def chacha_pending(ms, n_masks, env_path=None):
 
 # ---------------------------------------------------------------- recipient
 def residue_only(ms, ss, output_modulus, env_exact=None):
-    """engine_pipelines.cpp `residue_only`: q is |masking modulus|."""
+    """engine_recipient.cpp `residue_only`: q is |masking modulus|."""
     p = ss.prime_modulus
     keep = env_exact is not None and env_exact.strip().lstrip("+-").isdigit() and int(env_exact) == 1
     return output_modulus == p and (isinstance(ms, S.NoMasking) or abs(ms.modulus) == p) and not keep
 
 
 def run_mode(ms, ss, output_modulus, mode, env_exact=None):
-    """engine_pipelines.cpp `run_mode`."""
+    """engine_recipient.cpp `run_mode`."""
     return CANONICAL if mode == EXACT and residue_only(ms, ss, output_modulus, env_exact) else mode
 
 
@@ -82,7 +82,7 @@ def fell_back(ms, ss, output_modulus, mode, indices, env_exact=None):
 
 
 def compact(ss, dimension, share_len):
-    """engine_pipelines.cpp `compact`."""
+    """engine_recipient.cpp `compact`."""
     return is_packed(ss) and share_len != batches(ss, dimension)
 
 
@@ -131,7 +131,7 @@ def check_packed(ss):
 
 
 def mask_combine_status(ms, n_masks, mask_width):
-    """engine_pipelines.cpp mask_combine_checks -> (status or None, mask_len)."""
+    """engine_recipient.cpp mask_combine_checks -> (status or None, mask_len)."""
     if isinstance(ms, S.NoMasking):
         if n_masks and mask_width:
             return (PRECONDITION, "masks.iter().all"), 0

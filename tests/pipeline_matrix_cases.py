@@ -1,5 +1,6 @@
 """The plan of tests/test_gpu_pipeline_matrix.py as data: every case of the two role pipelines
-(sda_amd/csrc/engine_pipelines.cpp) with the inputs it runs on.  No GPU, no product import beyond the schemes.
+(sda_amd/csrc/engine_recipient.cpp, engine_participant.cpp) with the inputs it runs on.  No GPU, no product import
+beyond the schemes.
 
 tests/test_pipeline_matrix_plan.py holds the tables against tests/pipeline_dispatch.py (every decision value is taken
 by a case), against the model and the oracle (tests/pipeline_model.py, tests/oracle_backend.py) and against what each

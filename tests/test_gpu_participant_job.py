@@ -259,8 +259,11 @@ def test_job_forms_existing_sequence_and_round_trip(engine, oracle, monkeypatch,
 # the status matrix: a failing call leaves buffers and records as they were
 # ---------------------------------------------------------------------------------------------------------------
 def _records(engine):
+    """every *_last_launch record of the handle"""
     return (engine.participant_job_last_launch(), engine.participant_last_launch(), engine.chacha_last_launch(),
-            engine.packed_keyed_last_launch())
+            engine.packed_keyed_last_launch(), engine.codec_last_launch(), tuple(engine.combine_last_launch()),
+            engine.snapshot_last_launch(), engine.clerk_job_last_launch(), tuple(engine.recipient_last_launch()),
+            tuple(engine.recipient_job_last_launch()))
 
 
 def _untouched(bufs):

@@ -32,9 +32,11 @@ JOB_MESSAGES.update({RJ.ALIGN: "16-byte aligned", RJ.OFFSETS: "non-decreasing", 
 
 
 def _records(eng):
-    """every record a recipient call can write"""
+    """every *_last_launch record of the handle"""
     return (tuple(eng.recipient_job_last_launch()), tuple(eng.recipient_last_launch()), eng.codec_last_launch(),
-            tuple(eng.combine_last_launch()), eng.chacha_last_launch(), eng.clerk_job_last_launch())
+            tuple(eng.combine_last_launch()), eng.chacha_last_launch(), eng.clerk_job_last_launch(),
+            eng.snapshot_last_launch(), tuple(eng.participant_last_launch()), tuple(eng.participant_job_last_launch()),
+            eng.packed_keyed_last_launch())
 
 
 class DevBlobs:
