@@ -14,6 +14,7 @@ pub mod factories;
 pub mod ffi;
 
 use self::ffi::*;
+use libc::c_void;
 use super::*;
 use rand::distributions::{IndependentSample, Range};
 use rand::{OsRng, Rng};
@@ -228,9 +229,53 @@ pub struct GpuReconstructor {
     dimension: usize,
 }
 
+/// What `GpuReconstructor::check` found in the shares a reveal would read (sda_secret_check).
+pub struct ShareCheck {
+    /// shares beyond the k + t the polynomial needs; location needs at least 2
+    pub redundancy: usize,
+    pub bad_batches: usize,
+    /// the first bad batch, if any
+    pub first_bad: Option<usize>,
+    /// blame[i]: batches in which the share of indexed_shares[i] alone disagrees with all the others
+    pub blame: Vec<usize>,
+    /// per batch: 0 consistent, i + 1 located at indexed_shares[i], 0xFFFF inconsistent and not located
+    pub verdict: Vec<u16>,
+}
+
 impl GpuReconstructor {
     pub fn new(dev: Arc<Device>, scheme: &LinearSecretSharingScheme, dimension: usize) -> GpuReconstructor {
         GpuReconstructor { dev: dev, c: sharing_c(scheme), dimension: dimension }
+    }
+
+    /// Do the clerk results agree?  Call before `reconstruct`, which uses every share it is given and returns a
+    /// wrong aggregate without an error when one of them is wrong.
+    pub fn check(&self, indexed_shares: &Vec<(usize, Vec<Share>)>) -> SdaClientResult<ShareCheck> {
+        let idx: Vec<u64> = indexed_shares.iter().map(|&(i, _)| i as u64).collect();
+        let ptrs: Vec<*const i64> = indexed_shares.iter().map(|&(_, ref r)| r.as_ptr()).collect();
+        let lens: Vec<u64> = indexed_shares.iter().map(|&(_, ref r)| r.len() as u64).collect();
+        let widest = lens.iter().cloned().max().unwrap_or(0) as usize;
+        let mut verdict = vec![0_u16; std::cmp::max(self.dimension, widest)];
+        let mut blame = vec![0_u64; std::cmp::max(idx.len(), 1)];
+        let (mut r, mut bad, mut first) = (0_u64, 0_u64, 0_u64);
+        let (c, dim) = (self.c, self.dimension as u64);
+        self.dev.call(|h| unsafe {
+            sda_secret_check(h, &c, dim, idx.as_ptr(), ptrs.as_ptr(), lens.as_ptr(), ptrs.len() as u64,
+                             verdict.as_mut_ptr() as *mut c_void, &mut r, &mut bad, &mut first, blame.as_mut_ptr())
+        })?;
+        let batches = if c.kind == SDA_SHARING_PACKED_SHAMIR && c.secret_count > 0 {
+            (self.dimension + c.secret_count as usize - 1) / c.secret_count as usize
+        } else {
+            lens.first().cloned().unwrap_or(0) as usize
+        };
+        verdict.truncate(batches);
+        blame.truncate(idx.len());
+        Ok(ShareCheck {
+            redundancy: r as usize,
+            bad_batches: bad as usize,
+            first_bad: if first == u64::max_value() { None } else { Some(first as usize) },
+            blame: blame.into_iter().map(|x| x as usize).collect(),
+            verdict: verdict,
+        })
     }
 }
 

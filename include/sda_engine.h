@@ -455,6 +455,53 @@ sda_status sda_packed_reconstruct32_dev(sda_engine* h, const sda_sharing_scheme*
                                         const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
                                         const int32_t* shares, int64_t* out, int32_t mode, void* stream);
 
+/* ---- share consistency check with faulty-clerk location ----
+ * A packed-Shamir sharing polynomial has degree below L = k + t + 1, and a reveal interpolates through the inserted
+ * point (1, 0) and ALL n_idx clerk shares: from more than k + t shares some are redundant, and a wrong one still
+ * gives an aggregate with status SDA_OK.  These calls read the shares a reveal would read and tell whether they
+ * agree.  Points: x_0 = 1, y_0 = 0; x_j = omega_shares^(indices[j-1] + 1), y_j = the residue mod p of share j
+ * (any i64 value is reduced exactly; signed and canonical representatives are the same share).  With
+ * r = n_idx - (k + t), the redundancy:
+ *   a batch is consistent iff one polynomial of degree < L passes through all n_idx + 1 points;
+ *   with r >= 2 a bad batch is located at position j (1 <= j <= n_idx) iff the points without point j are
+ *   consistent (at most one such j exists); with r < 2 nothing is located; point 0 is never a suspect.
+ * Verdict per batch (uint16_t): 0 consistent, j located at position j (1-based into indices), 0xFFFF inconsistent
+ * and not located.
+ *
+ * shares [n_vectors][n_idx][B] as sda_packed_reconstruct_dev takes them, B = ceil(dimension / k).  verdict: device
+ * uint16_t [n_vectors][B], 2-byte aligned, or NULL (declared void*: every binding maps it without a 16-bit type).  Host outputs (all required; blame may be NULL when n_idx == 0): *redundancy = r,
+ * *bad_batches, *first_bad = the smallest bad vec * B + b (UINT64_MAX when nothing is bad), blame[j-1] = the batches
+ * located at position j (unlocated ones: bad_batches - sum of blame).
+ * The checks, their order and their statuses are those of sda_packed_reconstruct_dev on the same arguments (NULL
+ * arguments where the int32 reveal checks them; SDA_ERR_NOT_ENOUGH_SHARES included); repeated indices return
+ * SDA_ERR_UNSUPPORTED, as a CANONICAL reveal does.  An Additive scheme (B = dimension), r == 0, dimension == 0 and
+ * n_vectors == 0 return SDA_OK with zero counts and launch nothing; a given verdict buffer is zero-filled.  The call
+ * drains its stream before it returns (it reads the counts); a failing call writes nothing.  Stream ordering on the
+ * handle is that of every `_dev` call; on a multi-device handle the call runs on ordinals[0].
+ * SDA_CHECK_LOG_CAP (read per call, 0 .. 65536, default 65536): the entries of the bad-batch log used; more bad
+ * batches than that and the location pass walks every batch of the call (same results, slower). */
+sda_status sda_packed_check_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
+                                const int64_t* shares, void* verdict, uint64_t* redundancy,
+                                uint64_t* bad_batches, uint64_t* first_bad, uint64_t* blame, void* stream);
+sda_status sda_packed_check32_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                  const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
+                                  const int32_t* shares, void* verdict, uint64_t* redundancy,
+                                  uint64_t* bad_batches, uint64_t* first_bad, uint64_t* blame, void* stream);
+/* The same check of host share rows, as sda_secret_reconstruct takes them (one vector; verdict: HOST [B] or NULL).
+ * Checks and statuses are those of sda_secret_reconstruct, ragged rows included; an Additive scheme returns SDA_OK
+ * with zero counts (verdict, when given, holds share_lens[0] zeros for n_idx > 0). */
+sda_status sda_secret_check(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                            const uint64_t* indices, const int64_t* const* share_rows, const uint64_t* share_lens,
+                            uint64_t n_idx, void* verdict, uint64_t* redundancy, uint64_t* bad_batches,
+                            uint64_t* first_bad, uint64_t* blame);
+/* How the last check on this handle that launched something ran (written when it returns SDA_OK; host-side only; all
+ * zeros before): path 1 a register kernel / 2 the looped kernel (33 .. 1023 shares); bucket 8 / 16 / 32 shares, 0
+ * on the looped path; located = batches the location pass walked (the bad ones, or every batch when the log
+ * overflowed; 0 when r < 2 or nothing was bad); overflowed = more bad batches than the log held. */
+sda_status sda_packed_check_last_launch(sda_engine* h, uint32_t* path, uint32_t* bucket, uint64_t* located,
+                                        uint32_t* overflowed);
+
 /* Additive share generation: secrets [dimension], draws [dimension][n-1], out [n][dimension]. */
 sda_status sda_additive_generate_dev(sda_engine* h, int64_t modulus, uint64_t share_count,
                                      const int64_t* secrets, uint64_t dimension,

@@ -326,6 +326,7 @@ void sda_engine_destroy(sda_engine* h) {
     (void)hipDeviceSynchronize();            // _dev work may still be queued on callers' streams
     dev_free(h->work);
     dev_free(h->gen_log);
+    dev_free(h->chk_buf);
     dev_free(h->gen32_tmp);
     dev_free(h->keyed_draws);
     dev_free(h->codec_work);
@@ -337,6 +338,7 @@ void sda_engine_destroy(sda_engine* h) {
     dev_free(h->stage);
     sda::free_table(h->gen_tab);
     sda::free_table(h->rev_tab);
+    sda::free_table(h->chk_tab);
     if (h->rej_host) (void)hipHostFree(h->rej_host);
     if (h->hs_pin) (void)hipHostFree(h->hs_pin);
     dev_free(h->hs_dev);

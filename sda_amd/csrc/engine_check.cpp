@@ -1,0 +1,208 @@
+// engine_check.cpp -- the packed-Shamir share consistency check's entry points (include/sda_engine.h):
+// sda_packed_check_dev / sda_packed_check32_dev on device shares, sda_secret_check on host rows, and their record.
+// Argument checks follow the reveal entry points on the same arguments; the arithmetic is packed_check.hip's.
+#include "engine_internal.h"
+
+using namespace sda_host;
+
+namespace {
+
+// what a call hands back once it has succeeded (a failing call writes nothing)
+struct CheckOutputs {
+    uint64_t *redundancy, *bad_batches, *first_bad, *blame;
+    uint64_t n_idx;
+    void zero(uint64_t r) const {
+        *redundancy = r;
+        *bad_batches = 0;
+        *first_bad = UINT64_MAX;
+        for (uint64_t j = 0; j < n_idx; ++j) blame[j] = 0;
+    }
+};
+
+uint32_t check_log_cap() {                                 // SDA_CHECK_LOG_CAP, read per call
+    const char* e = getenv("SDA_CHECK_LOG_CAP");
+    if (!e || !*e) return sda::kCheckLogCap;
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    return v < sda::kCheckLogCap ? (uint32_t)v : sda::kCheckLogCap;
+}
+
+// SDA_OK with zero counts and nothing launched; a given device verdict buffer of `words` entries is zero-filled
+sda_status nothing_to_check(const CheckOutputs& o, uint64_t r, uint16_t* verdict, uint64_t words, hipStream_t st) {
+    if (verdict && words) {
+        HIP_TRY(hipMemsetAsync(verdict, 0, words * sizeof(uint16_t), st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    o.zero(r);
+    return SDA_OK;
+}
+
+// The check of a validated call (PackedShamir, n_idx >= k + t, at most 1023 shares and 65535 vectors) on stream st.
+sda_status run_check(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedCheckArgs& ca, const uint64_t* indices,
+                     uint64_t n_idx, const CheckOutputs& o, hipStream_t st) {
+    if (sda_status e = ensure(&h->chk_buf, &h->chk_buf_bytes, sda::packed_check_buf_bytes())) return e;
+    const uint64_t k = s->secret_count, B = (ca.dimension + k - 1) / k;
+    std::vector<uint64_t> blame(n_idx, 0);
+    sda::PackedCheckResult res{};
+    const hipError_t e = sda::launch_packed_check(ca, indices, (uint32_t)n_idx, (uint32_t)k,
+                                                  (uint32_t)s->privacy_threshold, (uint32_t)s->modulus,
+                                                  (uint32_t)s->omega_secrets, (uint32_t)s->omega_shares, h->chk_tab,
+                                                  h->chk_buf, check_log_cap(), st, blame.data(), &res);
+    if (e == hipErrorInvalidValue) return fail(SDA_ERR_UNSUPPORTED, "the share check needs distinct clerk indices");
+    HIP_TRY(e);
+    if (!res.launched) return nothing_to_check(o, res.plan.redundancy, ca.verdict, ca.n_vectors * B, st);
+    *o.redundancy = res.plan.redundancy;
+    *o.bad_batches = res.bad;
+    *o.first_bad = res.first_bad;
+    for (uint64_t j = 0; j < n_idx; ++j) o.blame[j] = blame[j];
+    h->last.check.path = res.plan.path;
+    h->last.check.bucket = res.plan.bucket;
+    h->last.check.located = res.located;
+    h->last.check.overflowed = res.overflowed ? 1 : 0;
+    return SDA_OK;
+}
+
+// Both device entry points, T the share type: sda_packed_reconstruct_dev's checks in its order.
+template <typename T>
+sda_status packed_check(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension, const uint64_t* indices,
+                        uint64_t n_idx, uint64_t n_vectors, const T* shares, uint16_t* verdict, const CheckOutputs& o,
+                        void* stream) {
+    if (!h || !s) return fail(SDA_ERR_INVALID_ARGUMENT, "need a PackedShamir scheme");
+    if (!o.redundancy || !o.bad_batches || !o.first_bad || (n_idx && !o.blame))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (s->kind == SDA_SHARING_ADDITIVE) {                  // every share is needed: no redundancy to check
+        if (n_vectors > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 vectors per launch");
+        HIP_TRY(hipSetDevice(h->device));
+        if (sda_status e = nothing_to_check(o, 0, verdict, n_vectors * dimension, pick(h, stream))) return e;
+        return ok();
+    }
+    if (s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "need a PackedShamir scheme");
+    if (sda_status st = check_packed(s)) return st;
+    const uint64_t kt = s->privacy_threshold + s->secret_count;
+    if (dimension == 0) {                                   // batched.rs:77-81: no batch, no check
+        o.zero(n_idx > kt ? n_idx - kt : 0);
+        return ok();
+    }
+    if (n_idx < kt) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");
+    if (n_idx > sda::kRevealMaxShares)
+        return fail(SDA_ERR_UNSUPPORTED, "more than %u clerk shares per batch", sda::kRevealMaxShares);
+    if (n_vectors > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 vectors per launch");
+    if (n_vectors && (!shares || !indices)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (n_vectors == 0) {
+        o.zero(n_idx - kt);
+        return ok();
+    }
+    sda::PackedCheckArgs ca{nullptr, nullptr, dimension, n_vectors, verdict};
+    if constexpr (sizeof(T) == 4) ca.shares32 = shares; else ca.shares = shares;
+    if (sda_status e = run_check(h, s, ca, indices, n_idx, o, pick(h, stream))) return e;
+    return ok();
+}
+
+}  // namespace
+
+extern "C" {
+
+sda_status sda_packed_check_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors, const int64_t* shares,
+                                void* verdict, uint64_t* redundancy, uint64_t* bad_batches, uint64_t* first_bad,
+                                uint64_t* blame, void* stream) {
+    SDA_ENTRY;
+    return packed_check(h, s, dimension, indices, n_idx, n_vectors, shares, static_cast<uint16_t*>(verdict),
+                        CheckOutputs{redundancy, bad_batches, first_bad, blame, n_idx}, stream);
+}
+
+sda_status sda_packed_check32_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                  const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors, const int32_t* shares,
+                                  void* verdict, uint64_t* redundancy, uint64_t* bad_batches, uint64_t* first_bad,
+                                  uint64_t* blame, void* stream) {
+    SDA_ENTRY;
+    return packed_check(h, s, dimension, indices, n_idx, n_vectors, shares, static_cast<uint16_t*>(verdict),
+                        CheckOutputs{redundancy, bad_batches, first_bad, blame, n_idx}, stream);
+}
+
+// sda_secret_reconstruct's checks in its order (no output buffer here), then the device form on the staged rows
+sda_status sda_secret_check(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension, const uint64_t* indices,
+                            const int64_t* const* rows, const uint64_t* lens, uint64_t n_rows, void* verdict,
+                            uint64_t* redundancy, uint64_t* bad_batches, uint64_t* first_bad, uint64_t* blame) {
+    SDA_ENTRY;
+    if (!h || !s || !redundancy || !bad_batches || !first_bad || (n_rows && !blame))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    const CheckOutputs o{redundancy, bad_batches, first_bad, blame, n_rows};
+    if (s->kind == SDA_SHARING_ADDITIVE) {
+        // additive.rs:56-72 through combine_rows' checks: the dimension is row 0's length
+        if (n_rows && (!rows || !lens)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+        const uint64_t dim = n_rows ? lens[0] : 0;
+        int64_t m;
+        if (dim && s->modulus == 0) return modulus_abs(s->modulus, &m);
+        for (uint64_t i = 0; i < n_rows; ++i)
+            if (lens[i] != dim) return fail(SDA_ERR_MISMATCHING_DIMENSION, "Mismatching dimension (row %llu has %llu elements, expected %llu)",
+                                            (unsigned long long)i, (unsigned long long)lens[i], (unsigned long long)dim);
+        if (dim && n_rows)
+            if (sda_status st = modulus_abs(s->modulus, &m)) return st;
+        if (verdict) memset(verdict, 0, dim * sizeof(uint16_t));
+        o.zero(0);
+        return ok();
+    }
+    if (s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown sharing scheme kind");
+    if (sda_status st = check_packed(s)) return st;
+    HIP_TRY(hipSetDevice(h->device));
+    const uint64_t k = s->secret_count, kt = s->privacy_threshold + k;
+    const uint64_t B = (dimension + k - 1) / k;             // batched.rs:77
+    if (B == 0) {                                           // no batch => no error checks run
+        o.zero(n_rows > kt ? n_rows - kt : 0);
+        return ok();
+    }
+    if (n_rows && (!rows || !lens || !indices)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    const bool enough = n_rows >= kt;
+    for (uint64_t i = 0; i < n_rows; ++i)
+        if (lens[i] < (enough ? B : 1))
+            return fail(SDA_ERR_PRECONDITION, "index out of bounds: row %llu has %llu < %llu batches",
+                        (unsigned long long)i, (unsigned long long)lens[i], (unsigned long long)(enough ? B : 1));
+    if (!enough)
+        return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct (%llu < %llu)",
+                    (unsigned long long)n_rows, (unsigned long long)kt);
+    if (n_rows > sda::kRevealMaxShares)
+        return fail(SDA_ERR_UNSUPPORTED, "more than %u clerk shares per batch", sda::kRevealMaxShares);
+    for (uint64_t i = 0; i < n_rows; ++i)
+        if (!rows[i]) return fail(SDA_ERR_INVALID_ARGUMENT, "row %llu is NULL", (unsigned long long)i);
+    (void)pick(h, h->stream);                               // host entry points run on the engine's own stream
+    DevArena a;
+    if (sda_status e = stage(h, rup(n_rows * B * 8) + rup(B * 2), &a)) return e;
+    int64_t* din = a.take<int64_t>(n_rows * B);
+    uint16_t* dver = a.take<uint16_t>(B);
+    for (uint64_t i = 0; i < n_rows; ++i)                   // batched.rs:83-85: clerk i's batches
+        HIP_TRY(hipMemcpyAsync(din + i * B, rows[i], B * 8, hipMemcpyHostToDevice, h->stream));
+    // the counts go to locals first: the verdict copy below may still fail
+    uint64_t r = 0, bad = 0, first = UINT64_MAX;
+    std::vector<uint64_t> bl(n_rows, 0);
+    const CheckOutputs tmp{&r, &bad, &first, bl.data(), n_rows};
+    const sda_engine::CheckLaunchInfo before = h->last.check;
+    sda::PackedCheckArgs ca{din, nullptr, dimension, 1, verdict ? dver : nullptr};
+    if (sda_status e = run_check(h, s, ca, indices, n_rows, tmp, h->stream)) return e;
+    if (verdict) {
+        std::vector<uint16_t> hv(B);
+        hipError_t ce = hipMemcpyAsync(hv.data(), dver, B * 2, hipMemcpyDeviceToHost, h->stream);
+        if (ce == hipSuccess) ce = hipStreamSynchronize(h->stream);
+        if (ce != hipSuccess) h->last.check = before;
+        HIP_TRY(ce);
+        memcpy(verdict, hv.data(), B * 2);
+    }
+    *redundancy = r;
+    *bad_batches = bad;
+    *first_bad = first;
+    for (uint64_t j = 0; j < n_rows; ++j) blame[j] = bl[j];
+    return ok();
+}
+
+sda_status sda_packed_check_last_launch(sda_engine* h, uint32_t* path, uint32_t* bucket, uint64_t* located,
+                                        uint32_t* overflowed) {
+    SDA_ENTRY;
+    if (!h || !path || !bucket || !located || !overflowed) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    *path = h->last.check.path;
+    *bucket = h->last.check.bucket;
+    *located = h->last.check.located;
+    *overflowed = h->last.check.overflowed;
+    return ok();
+}
+
+}  // extern "C"

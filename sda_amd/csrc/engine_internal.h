@@ -3,6 +3,7 @@
 //
 //   engine.cpp              handle life cycle, call scope, scratch, scheme helpers, the trait calls on host buffers
 //   engine_dev.cpp          the device-resident (`_dev`) entry points
+//   engine_check.cpp        the packed-Shamir share consistency check (device and host forms) and its record
 //   hbm.cpp                 sda_hbm_*: HBM buffers built from fixed-size physical chunks
 //   engine_codec.cpp        the share payload codec's host side and the snapshot transposition
 //   engine_recipient.cpp    the fused recipient pipeline, sda_recipient_reveal and the recipient job
@@ -56,6 +57,9 @@ struct sda_engine {
     void* pipe = nullptr;         // recipient / participant pipeline scratch (mask, masked, compacted shares)
     size_t pipe_bytes = 0;
     sda::DeviceTable rev_tab;     // packed-Shamir Newton/Lagrange tables (per scheme + clerk set)
+    sda::DeviceTable chk_tab;     // share consistency check: parity weights (per scheme + clerk set)
+    void* chk_buf = nullptr;      // its counters, blame words and bad-batch log (sda::packed_check_buf_bytes())
+    size_t chk_buf_bytes = 0;
     void* snap = nullptr;         // snapshot transposition copy plan
     size_t snap_bytes = 0;
     // The scratch buffers above are shared by every call on the handle.  A call on another stream
@@ -83,6 +87,10 @@ struct sda_engine {
         uint32_t mask_route = 0, share_route = 0, share_bytes = 0;
         uint64_t tiles = 0;
     };
+    struct CheckLaunchInfo {
+        uint32_t path = 0, bucket = 0, overflowed = 0;
+        uint64_t located = 0;
+    };
     struct Records {
         // sda_chacha_last_launch: how the last mask combine or participant mask on this handle ran; chacha_split:
         // that call split its seeds over the handle's devices (chacha_combine_multi), each recording its own part
@@ -109,6 +117,8 @@ struct sda_engine {
         // 1 made in the share kernels, 2 staged through keyed_draws -- and the draw bytes that crossed HBM
         uint32_t keyed_path = 0;
         uint64_t keyed_staged_bytes = 0;
+        // sda_packed_check_last_launch: written when a share check that launched something returns SDA_OK
+        CheckLaunchInfo check;
     } last;
     // participant job (sda_participant_job, sda_participant_job_dev): the share rows [n][B] of a call (a tile of the
     // host form) and the Full mask row behind them -- int32 where they fit by construction, else i64

@@ -8,6 +8,7 @@
 
 #include "modarith.h"
 #include "reveal_plan.h"
+#include "check_plan.h"
 
 namespace sda {
 
@@ -178,6 +179,32 @@ hipError_t launch_packed_reveal(const PackedRevealArgs& a, const uint64_t* indic
 hipError_t launch_packed_reveal_wide(const PackedRevealArgs& a, const uint64_t* indices, uint32_t n_idx, uint32_t k,
                                      uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, int mode,
                                      DeviceTable& tab, hipStream_t s);
+
+// ---- packed_check.hip ----
+// Share consistency check of a reveal's input (sda_packed_check_dev): the shares as PackedRevealArgs lays them out,
+// the per-batch verdicts (device [n_vectors][B], or nullptr) and the counts.
+struct PackedCheckArgs {
+    const int64_t* shares; const int32_t* shares32;   // one of the two
+    uint64_t dimension; uint64_t n_vectors;
+    uint16_t* verdict;
+};
+struct PackedCheckResult {
+    PackedCheckPlan plan;
+    bool launched;            // false: no redundancy or no batch -- nothing ran, the counts are zero
+    uint64_t bad, first_bad;  // bad batches; the smallest bad vec * B + b, UINT64_MAX for none
+    uint64_t located;         // batches the location pass walked: the bad ones, or on overflow every batch
+    bool overflowed;          // more bad batches than the log holds
+};
+constexpr uint32_t kCheckLogCap = 1u << 16;
+size_t packed_check_buf_bytes();
+// Runs the call as packed_check_plan (check_plan.h) decides it and waits for it: *res and blame_host[n_idx] (written
+// only when the location pass ran) are final on return.  `buf`: device memory of packed_check_buf_bytes() bytes;
+// log_cap <= kCheckLogCap entries of its log are used.  hipErrorInvalidValue for repeated clerk points: nothing is
+// launched and `tab` keeps its key.  The caller has checked n_idx >= k + t.
+hipError_t launch_packed_check(const PackedCheckArgs& a, const uint64_t* indices, uint32_t n_idx, uint32_t k,
+                               uint32_t t, uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, DeviceTable& tab,
+                               void* buf, uint32_t log_cap, hipStream_t s, uint64_t* blame_host,
+                               PackedCheckResult* res);
 
 // ---- codec_decode.hip (share payload codec: sodium.rs:36-41 / :82-88, integer-encoding 1.0 VarInt) ----
 // Host-side plan of the decode: blobs are split into 4 KiB regions aligned to the (16-byte

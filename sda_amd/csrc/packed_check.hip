@@ -1,0 +1,371 @@
+// packed_check.hip -- packed-Shamir share consistency check with faulty-clerk location (sda_packed_check_dev).
+//
+// A sharing polynomial has degree below L = k + t + 1, so of the m = n_idx + 1 points of a batch -- the inserted
+// (1, 0) and the n_idx clerk shares -- the first L fix it and the other r = n_idx - (k + t) are redundant.  The check
+// is the systematic one (packed_common.h, make_check_weights): parity row c < r is
+//   syndrome_c = share_{kt+c} + sum_{s < kt} w[c][s] share_s  (mod p),   kt = k + t,
+// and a batch is consistent iff every syndrome is 0.  A single error e in share j gives syndrome = e x column j of
+// the parity matrix H = [W | I]; any two columns of H are independent when r >= 2 (the code is MDS), so at most one
+// position explains a bad batch, and packed_check_locate_kernel finds it: one wave per bad batch, lane j tests
+// "syndrome is a multiple of column j" by cross-multiplication (no inverse).
+//
+// Device table (u32 words, Montgomery form): w[c][s] at c * KS + s, KS = kt rounded up to even, the pad word 0 (the
+// kernels take the products of a row in pairs that share one REDC, as reveal_canon_body does).
+//
+// Counter block (u64 words; `buf` of packed_check_buf_bytes()): [0] bad batches, [1] ~(first bad flat index) under
+// atomicMax (0: none), [kCheckHdr, +kCheckBlameCap) blame per position, then the log of bad flat indices vec * B + b.
+#include "packed_common.h"
+#include "check_plan.h"
+
+namespace sda {
+using namespace packed;
+
+namespace {
+
+constexpr uint32_t kCheckHdr = 4, kCheckBlameCap = 1024;
+static_assert(kRevealMaxShares < kCheckBlameCap, "one blame word per clerk position");
+
+// the exact canonical residue of any share value
+__device__ __forceinline__ uint32_t canon_exact(int64_t v, int64_t P, const Mod64& PM) {
+    const int64_t r = trem64(v, PM);
+    return (uint32_t)(r < 0 ? r + P : r);
+}
+template <class ST>
+__device__ __forceinline__ uint32_t canon_any(ST v, uint32_t p, int64_t P, const Mod64& PM) {
+    return share_in_range(v, p, P) ? canon32((int32_t)v, p) : canon_exact((int64_t)v, P, PM);
+}
+
+// What a lane reports for its batch: the provisional verdict (0 / 0xFFFF; the location pass overwrites located ones),
+// and per wave one add of its bad count, one max for the first bad index and a log slot per bad lane.
+// The first thread id of the calling wave, as a uniform value (workgroups are 256 x 1 x 1: a wave's lanes are 64
+// consecutive threads).
+__device__ __forceinline__ uint32_t wave_first_thread() {
+    return __builtin_amdgcn_readfirstlane(threadIdx.x) & ~63u;
+}
+
+__device__ __forceinline__ void check_report(bool nonzero, uint32_t wave0, uint64_t B, uint16_t* __restrict__ verdict,
+                                             unsigned long long* __restrict__ cnt, uint32_t cap) {
+    // The batch's place is worked out here, after the arithmetic, from uniform values (wave0: taken before the
+    // loads, a scalar) and the lane's number in its wave: no vector register carries it across the loads.
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const uint32_t tid = wave0 + lane;
+    const uint64_t b0 = (uint64_t)blockIdx.x * 256;
+    const bool live = tid < B - b0;
+    const bool bad = live && nonzero;
+    const uint64_t flat = ((uint64_t)blockIdx.y * B + b0) + tid;
+    const uint64_t mask = __ballot(bad);
+    if (mask) {
+        const uint32_t first = (uint32_t)__ffsll((unsigned long long)mask) - 1;
+        uint32_t lo = 0, hi = 0;
+        if (lane == first) {                     // lanes hold ascending batches of one vector: the wave's minimum
+            const unsigned long long base = atomicAdd(cnt, (unsigned long long)__popcll(mask));
+            atomicMax(cnt + 1, ~(unsigned long long)flat);
+            lo = (uint32_t)base;
+            hi = (uint32_t)(base >> 32);
+        }
+        lo = __shfl(lo, first);
+        hi = __shfl(hi, first);
+        if (bad) {
+            const uint64_t slot = (((uint64_t)hi << 32) | lo) + __popcll(mask & ((1ull << lane) - 1));
+            if (slot < cap) cnt[kCheckHdr + kCheckBlameCap + slot] = flat;
+        }
+    }
+    if (verdict && live) verdict[flat] = bad ? (uint16_t)0xFFFF : (uint16_t)0;
+}
+
+// One lane = one batch, its n_idx <= NMAX shares in registers: every load is issued before the first wait, each
+// share becomes its canonical residue as it lands (raw i64 shares outside (-p, p): reduced exactly in registers,
+// reloaded; rare), then r rows of kt Montgomery MACs, two products per REDC (2 p^2 < p R).
+template <class ST, int NMAX>
+__device__ __forceinline__ void check_body(const ST* __restrict__ shares, uint64_t B, uint32_t n_idx, uint32_t kt,
+                                           const uint32_t* __restrict__ tab, uint32_t ks, const MontP& M,
+                                           uint16_t* __restrict__ verdict, unsigned long long* __restrict__ cnt,
+                                           uint32_t cap) {
+    // lanes past the last batch read the last batch again (check_report drops them)
+    const uint32_t wave0 = wave_first_thread();
+    const uint64_t b0 = (uint64_t)blockIdx.x * 256, rest = B - b0;
+    const ST* sh = shares + ((uint64_t)blockIdx.y * n_idx * B + b0) + (threadIdx.x < rest ? threadIdx.x : (uint32_t)rest - 1);
+    auto share = [&](uint32_t i) { return sh[(uint64_t)i * B]; };
+    const uint32_t p = M.p;
+    const int64_t P = (int64_t)p;
+
+    // the residues as one register tuple: share kt + c of parity row c is then a uniform-index move, not a select
+    using SV = uint32_t __attribute__((ext_vector_type(NMAX)));
+    SV S;
+    bool in_range = true;
+    {
+        ST v[NMAX];
+        static_for<0, NMAX>([&](auto i) { v[i] = share((uint32_t)i < n_idx ? i : 0); });
+        static_for<0, NMAX>([&](auto i) {
+            in_range = in_range && ((uint32_t)i >= n_idx || share_in_range(v[i], p, P));
+            S[(int)i] = (uint32_t)i < n_idx ? canon32((int32_t)v[i], p) : 0u;
+        });
+    }
+    if (!in_range) {
+        const Mod64 PM = make_mod64(P);
+        for (uint32_t i = 0; i < n_idx; ++i) S[i & (NMAX - 1)] = canon_exact((int64_t)share(i), P, PM);
+    }
+    const uint32_t r = n_idx - kt;
+    uint32_t nz = 0;
+    for (uint32_t c = 0; c < r; ++c) {
+        const uint32_t* w = tab + (size_t)c * ks;
+        uint32_t acc = 0;
+        static_for<0, NMAX, 2>([&](auto i) {
+            if ((uint32_t)i < kt) {
+                uint64_t T = (uint64_t)w[i] * S[(int)i];
+                if constexpr (i + 1 < NMAX) T += (uint64_t)w[i + 1] * S[(int)i + 1];     // the pad word past kt is 0
+                acc = addm(acc, red1(redc_lazy(T, M), p), p);
+            }
+        });
+        nz |= addm(acc, S[(kt + c) & (NMAX - 1)], p);     // kt + c < n_idx <= NMAX
+    }
+    check_report(nz != 0, wave0, B, verdict, cnt, cap);
+}
+
+template <int NMAX>
+__global__ __launch_bounds__(256) void packed_check_kernel(const int64_t* __restrict__ shares, uint64_t B,
+                                                           uint32_t n_idx, uint32_t kt,
+                                                           const uint32_t* __restrict__ tab, uint32_t ks, MontP M,
+                                                           uint16_t* __restrict__ verdict,
+                                                           unsigned long long* __restrict__ cnt, uint32_t cap) {
+    check_body<int64_t, NMAX>(shares, B, n_idx, kt, tab, ks, M, verdict, cnt, cap);
+}
+
+template <int NMAX>
+__global__ __launch_bounds__(256) void packed_check32_kernel(const int32_t* __restrict__ shares, uint64_t B,
+                                                             uint32_t n_idx, uint32_t kt,
+                                                             const uint32_t* __restrict__ tab, uint32_t ks, MontP M,
+                                                             uint16_t* __restrict__ verdict,
+                                                             unsigned long long* __restrict__ cnt, uint32_t cap) {
+    check_body<int32_t, NMAX>(shares, B, n_idx, kt, tab, ks, M, verdict, cnt, cap);
+}
+
+// 33 ... 1023 shares: the parity rows in groups of 8 accumulators; a group reads the kt basis shares of the batch
+// once (the first group from HBM, the others from cache) and the weights with uniform loads from the global table.
+template <class ST>
+__device__ __forceinline__ void check_loop_body(const ST* __restrict__ shares, uint64_t B, uint32_t n_idx, uint32_t kt,
+                                                const uint32_t* __restrict__ tab, uint32_t ks, const MontP& M,
+                                                uint16_t* __restrict__ verdict, unsigned long long* __restrict__ cnt,
+                                                uint32_t cap) {
+    constexpr int G = 8;
+    // lanes past the last batch read the last batch again (check_report drops them)
+    const uint32_t wave0 = wave_first_thread();
+    const uint64_t b0 = (uint64_t)blockIdx.x * 256, rest = B - b0;
+    const ST* sh = shares + ((uint64_t)blockIdx.y * n_idx * B + b0) + (threadIdx.x < rest ? threadIdx.x : (uint32_t)rest - 1);
+    auto share = [&](uint32_t i) { return sh[(uint64_t)i * B]; };
+    const uint32_t p = M.p, r = n_idx - kt;
+    const int64_t P = (int64_t)p;
+    const Mod64 PM = make_mod64(P);
+    uint32_t nz = 0;
+    for (uint32_t c0 = 0; c0 < r; c0 += G) {
+        uint32_t acc[G];
+        static_for<0, G>([&](auto u) { acc[u] = 0; });
+        for (uint32_t i = 0; i < kt; i += 2) {
+            const uint32_t s0 = canon_any(share(i), p, P, PM);
+            const uint32_t s1 = i + 1 < kt ? canon_any(share(i + 1), p, P, PM) : 0u;
+            static_for<0, G>([&](auto u) {
+                const uint32_t* w = tab + (size_t)min(c0 + (uint32_t)u, r - 1) * ks + i;      // rows past r: row r - 1 again
+                acc[u] = addm(acc[u], red1(redc_lazy((uint64_t)w[0] * s0 + (uint64_t)w[1] * s1, M), p), p);
+            });
+        }
+        static_for<0, G>([&](auto u) {
+            if (c0 + (uint32_t)u < r)
+                nz |= addm(acc[u], canon_any(share(kt + c0 + (uint32_t)u), p, P, PM), p);
+        });
+    }
+    check_report(nz != 0, wave0, B, verdict, cnt, cap);
+}
+
+__global__ __launch_bounds__(256) void packed_check_loop_kernel(const int64_t* __restrict__ shares, uint64_t B,
+                                                                uint32_t n_idx, uint32_t kt,
+                                                                const uint32_t* __restrict__ tab, uint32_t ks, MontP M,
+                                                                uint16_t* __restrict__ verdict,
+                                                                unsigned long long* __restrict__ cnt, uint32_t cap) {
+    check_loop_body(shares, B, n_idx, kt, tab, ks, M, verdict, cnt, cap);
+}
+
+__global__ __launch_bounds__(256) void packed_check32_loop_kernel(const int32_t* __restrict__ shares, uint64_t B,
+                                                                  uint32_t n_idx, uint32_t kt,
+                                                                  const uint32_t* __restrict__ tab, uint32_t ks,
+                                                                  MontP M, uint16_t* __restrict__ verdict,
+                                                                  unsigned long long* __restrict__ cnt, uint32_t cap) {
+    check_loop_body(shares, B, n_idx, kt, tab, ks, M, verdict, cnt, cap);
+}
+
+// Location (r >= 2): one wave per bad batch -- the `total` logged ones, or with `all` every batch of the launch (the
+// log overflowed; consistent batches are recognised and skipped).  The wave computes syndrome c as a sum over its
+// lanes (lane l holds share l; shares past 64 are re-read) and lane j tests position j0 + j against it as the rows
+// go by:  a basis position j < kt needs  s_c w[0][j] == s_0 w[c][j]  for every c (column j of W has no zero entry);
+// a check position kt + c' needs s_c != 0 exactly at c = c'.  At most one position passes.  The located batch gets
+// its verdict, and the wave adds to blame[] once per run of equal positions (a whole wrong row is one long run).
+template <class ST>
+__device__ __forceinline__ void check_locate_body(const ST* __restrict__ shares, uint64_t B, uint32_t n_idx,
+                                                  uint32_t kt, const uint32_t* __restrict__ tab, uint32_t ks,
+                                                  const MontP& M, uint16_t* __restrict__ verdict,
+                                                  unsigned long long* __restrict__ cnt, uint64_t total, int all) {
+    const uint32_t lane = threadIdx.x, p = M.p, r = n_idx - kt;
+    const int64_t P = (int64_t)p;
+    const Mod64 PM = make_mod64(P);
+    const unsigned long long* list = cnt + kCheckHdr + kCheckBlameCap;
+    uint32_t run_pos = 0;                         // wave-uniform: the current run of located positions (1-based)
+    unsigned long long run = 0;
+    auto flush = [&]() {
+        if (run && lane == 0) atomicAdd(cnt + kCheckHdr + (run_pos - 1), run);
+        run = 0;
+    };
+    for (uint64_t wv = blockIdx.x; wv < total; wv += gridDim.x) {
+        const uint64_t gb = all ? wv : list[wv];
+        const uint64_t vec = gb / B, b = gb - vec * B;
+        const ST* sh = shares + vec * (uint64_t)n_idx * B + b;
+        const uint32_t own = lane < n_idx ? canon_any(sh[(uint64_t)lane * B], p, P, PM) : 0u;
+        uint32_t found = 0;
+        for (uint32_t j0 = 0; j0 < n_idx && !found; j0 += 64) {
+            const uint32_t j = j0 + lane;
+            const bool basis = j < kt;
+            const uint32_t w0j = basis ? tab[j] : 0u;
+            bool ok = j < n_idx, any = false;
+            uint32_t s0 = 0;
+            for (uint32_t c = 0; c < r; ++c) {
+                const uint32_t* w = tab + (size_t)c * ks;
+                uint32_t part = 0;
+                for (uint32_t i = lane; i < kt; i += 64)
+                    part = addm(part, mont_mul(w[i], i < 64 ? own : canon_any(sh[(uint64_t)i * B], p, P, PM), M), p);
+                const uint32_t ci = kt + c;
+                if ((ci & 63) == lane) part = addm(part, ci < 64 ? own : canon_any(sh[(uint64_t)ci * B], p, P, PM), p);
+                for (int off = 32; off; off >>= 1) part = addm(part, (uint32_t)__shfl_xor((int)part, off), p);
+                if (c == 0) s0 = part;
+                any = any || part != 0;
+                if (basis) ok = ok && mont_mul(w0j, part, M) == mont_mul(w[j], s0, M);
+                else ok = ok && ((part != 0) == (j - kt == c));
+            }
+            if (!any) break;                      // consistent (full pass only)
+            const uint64_t mask = __ballot(ok);
+            if (mask) found = j0 + (uint32_t)__ffsll((unsigned long long)mask);
+        }
+        if (found) {
+            if (verdict && lane == 0) verdict[gb] = (uint16_t)found;
+            if (found != run_pos) {
+                flush();
+                run_pos = found;
+            }
+            ++run;
+        }
+    }
+    flush();
+}
+
+__global__ __launch_bounds__(64) void packed_check_locate_kernel(const int64_t* __restrict__ shares, uint64_t B,
+                                                                 uint32_t n_idx, uint32_t kt,
+                                                                 const uint32_t* __restrict__ tab, uint32_t ks, MontP M,
+                                                                 uint16_t* __restrict__ verdict,
+                                                                 unsigned long long* __restrict__ cnt, uint64_t total,
+                                                                 int all) {
+    check_locate_body(shares, B, n_idx, kt, tab, ks, M, verdict, cnt, total, all);
+}
+
+__global__ __launch_bounds__(64) void packed_check32_locate_kernel(const int32_t* __restrict__ shares, uint64_t B,
+                                                                   uint32_t n_idx, uint32_t kt,
+                                                                   const uint32_t* __restrict__ tab, uint32_t ks,
+                                                                   MontP M, uint16_t* __restrict__ verdict,
+                                                                   unsigned long long* __restrict__ cnt, uint64_t total,
+                                                                   int all) {
+    check_locate_body(shares, B, n_idx, kt, tab, ks, M, verdict, cnt, total, all);
+}
+
+// The launches of one call for share type ST: the kernel the plan names, the counters read back (one wait), then the
+// location pass over what the first pass logged (a second wait) when something is bad and r >= 2.
+template <class ST>
+hipError_t check_launch_t(const PackedCheckPlan& pl, const PackedCheckArgs& a, const ST* sh, uint64_t B, uint32_t n_idx,
+                          uint32_t kt, const uint32_t* tab, uint32_t ks, const MontP& M, unsigned long long* cnt,
+                          uint32_t cap, hipStream_t s, uint64_t* blame_host, PackedCheckResult* res) {
+    constexpr bool I32 = sizeof(ST) == 4;
+    const dim3 grid((unsigned)((B + 255) / 256), (unsigned)a.n_vectors);
+    auto run = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, sh, B, n_idx, kt, tab, ks, M, a.verdict, cnt, cap);
+    };
+    auto bucket = [&](auto nmax) {
+        if constexpr (I32) run(packed_check32_kernel<nmax>); else run(packed_check_kernel<nmax>);
+    };
+    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)(kCheckHdr + kCheckBlameCap) * sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    if (pl.path == kCheckLooped) {
+        if constexpr (I32) run(packed_check32_loop_kernel); else run(packed_check_loop_kernel);
+    } else if (pl.bucket == 8) {
+        bucket(std::integral_constant<int, 8>{});
+    } else if (pl.bucket == 16) {
+        bucket(std::integral_constant<int, 16>{});
+    } else if (pl.bucket == 32) {
+        bucket(std::integral_constant<int, 32>{});
+    } else {
+        return hipErrorInvalidValue;
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    uint64_t head[2] = {0, 0};
+    if ((e = hipMemcpyAsync(head, cnt, sizeof(head), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+    res->bad = head[0];
+    res->first_bad = ~head[1];                              // 0 (no max taken) -> UINT64_MAX
+    res->located = 0;
+    res->overflowed = false;
+    if (!pl.locate || res->bad == 0) return hipSuccess;
+    res->overflowed = res->bad > cap;
+    const uint64_t total = res->overflowed ? B * a.n_vectors : res->bad;
+    res->located = total;
+    const unsigned waves = (unsigned)(total < 8192 ? total : 8192);
+    if constexpr (I32)
+        hipLaunchKernelGGL(packed_check32_locate_kernel, dim3(waves), dim3(64), 0, s, sh, B, n_idx, kt, tab, ks, M,
+                           a.verdict, cnt, total, res->overflowed ? 1 : 0);
+    else
+        hipLaunchKernelGGL(packed_check_locate_kernel, dim3(waves), dim3(64), 0, s, sh, B, n_idx, kt, tab, ks, M,
+                           a.verdict, cnt, total, res->overflowed ? 1 : 0);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(blame_host, cnt + kCheckHdr, (size_t)n_idx * sizeof(uint64_t), hipMemcpyDeviceToHost, s)) !=
+        hipSuccess)
+        return e;
+    return hipStreamSynchronize(s);
+}
+
+}  // namespace
+
+size_t packed_check_buf_bytes() { return (size_t)(kCheckHdr + kCheckBlameCap + kCheckLogCap) * sizeof(uint64_t); }
+
+hipError_t launch_packed_check(const PackedCheckArgs& a, const uint64_t* indices, uint32_t n_idx, uint32_t k,
+                               uint32_t t, uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, DeviceTable& tab,
+                               void* buf, uint32_t log_cap, hipStream_t s, uint64_t* blame_host,
+                               PackedCheckResult* res) {
+    const PackedCheckPlan pl = packed_check_plan(n_idx, k, t);
+    const uint32_t kt = k + t, r = pl.redundancy, ks = (kt + 1) & ~1u;
+    const uint64_t B = (a.dimension + k - 1) / k;
+    std::vector<uint8_t> key(sizeof(uint32_t) * 6 + sizeof(uint64_t) * n_idx);
+    const uint32_t kv[6] = {n_idx, k, t, p, omega_secrets, omega_shares};
+    memcpy(key.data(), kv, sizeof(kv));
+    memcpy(key.data() + sizeof(kv), indices, sizeof(uint64_t) * n_idx);
+    // repeated points have no systematic form: refused before anything is launched, and `tab` keeps its key
+    if (tab.key != key) {
+        const RevealTables T = make_reveal_tables(indices, n_idx, k, p, omega_secrets, omega_shares);
+        if (T.duplicate) return hipErrorInvalidValue;
+        std::vector<uint32_t> host((size_t)(r ? r : 1) * ks, 0);
+        if (r) {
+            const std::vector<int64_t> w = make_check_weights(T, n_idx, kt, p);
+            for (uint32_t c = 0; c < r; ++c)
+                for (uint32_t i = 0; i < kt; ++i) host[(size_t)c * ks + i] = to_mont(w[(size_t)c * kt + i], p);
+        }
+        const hipError_t e = ensure_table(tab, key, host.data(), host.size() * sizeof(uint32_t));
+        if (e != hipSuccess) return e;
+    }
+    res->plan = pl;
+    res->bad = res->located = 0;
+    res->first_bad = UINT64_MAX;
+    res->overflowed = false;
+    res->launched = false;
+    if (pl.path == kCheckNothing || B == 0 || a.n_vectors == 0) return hipSuccess;
+    res->launched = true;
+    const MontP M = make_mont(p);
+    const uint32_t cap = log_cap < kCheckLogCap ? log_cap : kCheckLogCap;
+    unsigned long long* cnt = static_cast<unsigned long long*>(buf);
+    const uint32_t* dtab = static_cast<const uint32_t*>(tab.dev);
+    return a.shares32 ? check_launch_t(pl, a, a.shares32, B, n_idx, kt, dtab, ks, M, cnt, cap, s, blame_host, res)
+                      : check_launch_t(pl, a, a.shares, B, n_idx, kt, dtab, ks, M, cnt, cap, s, blame_host, res);
+}
+
+}  // namespace sda

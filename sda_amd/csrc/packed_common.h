@@ -165,6 +165,36 @@ inline RevealTables make_reveal_tables(const uint64_t* indices, uint32_t n_idx, 
     return T;
 }
 
+// The parity weights of the share consistency check (packed_check.hip), from make_reveal_tables' points and inverses.
+// A sharing polynomial has degree below L = kt + 1 (kt = k + t), so the first L points -- the inserted (1, 0) and
+// shares 0 .. kt - 1 -- fix it, and each further share kt + c, c < r = n_idx - kt, must equal its value there:
+//   syndrome_c = share_{kt+c} + sum_{s < kt} w[c kt + s] share_s  (mod p),  w[c kt + s] = -l_{s+1}(x_{L+c}),
+// l_i the Lagrange basis over the first L points (point 0 carries the value 0, so it has no weight).  Canonical words;
+// every one is nonzero (l_i vanishes at the other basis points only).  Distinct points only (!T.duplicate).
+inline std::vector<int64_t> make_check_weights(const RevealTables& T, uint32_t n_idx, uint32_t kt, int64_t p) {
+    const uint32_t m = n_idx + 1, L = kt + 1, r = n_idx - kt;
+    auto inv = [&](uint32_t a, uint32_t b) { return T.h[(uint64_t)(a - b) * m + a]; };   // 1 / (x_a - x_b), a > b
+    // den[i] = prod_{j < L, j != i} 1 / (x_i - x_j)
+    std::vector<int64_t> den(L, 1), w((uint64_t)r * kt, 0);
+    for (uint32_t i = 1; i < L; ++i)
+        for (uint32_t j = 0; j < L; ++j) {
+            if (j == i) continue;
+            den[i] = den[i] * (j < i ? inv(i, j) : p - inv(j, i)) % p;
+        }
+    for (uint32_t c = 0; c < r; ++c) {
+        int64_t num = 1;                                  // prod_{j < L} (x_{L+c} - x_j)
+        for (uint32_t j = 0; j < L; ++j) {
+            int64_t d = (T.pts[L + c] - T.pts[j]) % p; if (d < 0) d += p;
+            num = num * d % p;
+        }
+        for (uint32_t i = 1; i < L; ++i) {
+            const int64_t l = num * inv(L + c, i) % p * den[i] % p;
+            w[(uint64_t)c * kt + (i - 1)] = (p - l) % p;
+        }
+    }
+    return w;
+}
+
 // Rust `v % p` from the canonical residue c and the sign word sw of the exact dividend v.
 //   exact (LAZY = false): trunc_rep, 5 VALU ops incl. the c == 0 case (v < 0, v = 0 mod p -> 0);
 //   LAZY: c - (p & sign), 3 ops, which gives -p instead of 0 exactly when v < 0 and v = 0 mod p
@@ -287,6 +317,16 @@ template <bool ASM>
 __device__ __forceinline__ uint32_t montu2(uint32_t a_m, uint32_t x, uint32_t b_m, uint32_t y, const MontP& M) {
     if constexpr (ASM) return red1(redc_su(mad_su(b_m, y, mul_su(a_m, x)), M), M.p);
     else return red1(redc_lazy((uint64_t)a_m * x + (uint64_t)b_m * y, M), M.p);
+}
+
+// A share v lies in (-p, p) (packed_reveal.hip, packed_check.hip).  An int32 share is checked in 32 bits: v + (p - 1)
+// mod 2^32 lies in [0, 2p - 2] exactly for those v (above p - 1 the sum stays below 2^32, below -(p - 1) it is at
+// least 2^31 + p - 1 > 2p - 2, as p < 2^31).
+__device__ __forceinline__ bool share_in_range(int64_t v, uint32_t, int64_t P) {
+    return (uint64_t)(v + (P - 1)) < (uint64_t)(2 * P - 1);
+}
+__device__ __forceinline__ bool share_in_range(int32_t v, uint32_t p, int64_t) {
+    return (uint32_t)v + (p - 1) <= 2 * p - 2;
 }
 
 constexpr int ilog(int x, int b) { return x <= 1 ? 0 : 1 + ilog(x / b, b); }

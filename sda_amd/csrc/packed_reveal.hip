@@ -62,16 +62,7 @@ __device__ __forceinline__ void reveal_flush(int64_t* lds_o, int64_t* o, uint64_
 // gather [clerk][batch] -> [clerk] (batched.rs:83-85); point 1 carries value 0.  Clamped,
 // branch-free indices, so every load can be issued before the first wait; each share is turned into
 // its (sign, residue) pair as it lands, so no i64 copy stays live.  Returns whether every share lies
-// in (-p, p).
-// v in (-p, p).  An int32 share is checked in 32 bits: v + (p - 1) mod 2^32 lies in [0, 2p - 2] exactly for those
-// v (above p - 1 the sum stays below 2^32, below -(p - 1) it is at least 2^31 + p - 1 > 2p - 2, as p < 2^31).
-__device__ __forceinline__ bool share_in_range(int64_t v, uint32_t, int64_t P) {
-    return (uint64_t)(v + (P - 1)) < (uint64_t)(2 * P - 1);
-}
-__device__ __forceinline__ bool share_in_range(int32_t v, uint32_t p, int64_t) {
-    return (uint32_t)v + (p - 1) <= 2 * p - 2;
-}
-
+// in (-p, p) (share_in_range, packed_common.h).
 // ST is the share type, int64_t or int32_t (sda_packed_reconstruct32_dev): an int32 share is sign-extended as it
 // lands and takes the same range check -- for small p most of the int32 range lies outside (-p, p).
 template <int MMAX, bool EAGER, class ST>

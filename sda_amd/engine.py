@@ -117,6 +117,15 @@ PARTICIPANT_JOB_MASK_FULL32 = 2
 PARTICIPANT_JOB_MASK_CHACHA = 3
 ParticipantJobLaunch = collections.namedtuple("ParticipantJobLaunch", "mask_route share_route share_bytes tiles")
 
+# Share consistency check (sda_packed_check_dev): a batch's verdict is 0 (consistent), the 1-based position of the one
+# share that does not agree, or CHECK_UNLOCATED; sda_packed_check_last_launch's path codes
+CHECK_UNLOCATED = 0xFFFF
+CHECK_NO_BAD = (1 << 64) - 1
+CHECK_PATH_REGISTERS = 1
+CHECK_PATH_LOOPED = 2
+ShareCheck = collections.namedtuple("ShareCheck", "redundancy bad_batches first_bad blame")
+CheckLaunch = collections.namedtuple("CheckLaunch", "path bucket located overflowed")
+
 # Elements one workgroup of the draws kernel produces (csrc/kernels.h kDrawsTile): the sizes at which
 # sda_draws_dev's grid gains a workgroup
 DRAWS_TILE = 2048
@@ -190,6 +199,13 @@ SIGNATURES = [
                                         _vp, C.c_int32, _vp]),
     ("sda_packed_reconstruct32_dev", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.c_uint64,
                                            C.c_uint64, _vp, _vp, C.c_int32, _vp]),
+    ("sda_packed_check_dev", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.c_uint64, C.c_uint64,
+                                   _vp, _vp, _u64p, _u64p, _u64p, _u64p, _vp]),
+    ("sda_packed_check32_dev", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.c_uint64, C.c_uint64,
+                                     _vp, _vp, _u64p, _u64p, _u64p, _u64p, _vp]),
+    ("sda_secret_check", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.POINTER(_i64p), _u64p,
+                               C.c_uint64, _vp, _u64p, _u64p, _u64p, _u64p]),
+    ("sda_packed_check_last_launch", _st, [_vp, _u32p, _u32p, _u64p, _u32p]),
     ("sda_additive_generate_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp]),
     ("sda_chacha_mask_combine_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
     ("sda_draws_dev", _st, [_vp, _u32p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp]),
@@ -844,6 +860,56 @@ class Engine:
         idx = _arr(indices, np.uint64)
         _check(self.lib.sda_packed_reconstruct32_dev(self.h, C.byref(s), dimension, _ptr(idx, _u64p), idx.size,
                                                      n_vectors, shares_ptr, out_ptr, mode, stream))
+
+    # share consistency check of a reveal's input (include/sda_engine.h "share consistency check")
+    def _packed_check(self, fn, scheme, dimension, indices, n_vectors, shares_ptr, verdict_ptr, stream):
+        s = scheme.c()
+        idx = _arr(indices, np.uint64)
+        r, bad, first = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        blame = np.zeros(max(idx.size, 1), np.uint64)
+        _check(fn(self.h, C.byref(s), dimension, _ptr(idx, _u64p), idx.size, n_vectors, shares_ptr, verdict_ptr,
+                  C.byref(r), C.byref(bad), C.byref(first), _ptr(blame, _u64p), stream))
+        return ShareCheck(int(r.value), int(bad.value), int(first.value), [int(x) for x in blame[: idx.size]])
+
+    def packed_check_dev(self, scheme, dimension, indices, n_vectors, shares_ptr, verdict_ptr=None, stream=None):
+        """Do the i64 shares [n_vectors][n_idx][B] a reveal would read agree?  Returns ShareCheck(redundancy,
+        bad_batches, first_bad, blame); verdict_ptr: device uint16 [n_vectors][B] or None (sda_packed_check_dev).
+        Waits for its stream."""
+        return self._packed_check(self.lib.sda_packed_check_dev, scheme, dimension, indices, n_vectors, shares_ptr,
+                                  verdict_ptr, stream)
+
+    def packed_check32_dev(self, scheme, dimension, indices, n_vectors, shares_ptr, verdict_ptr=None, stream=None):
+        """packed_check_dev over int32 shares (sda_packed_check32_dev)."""
+        return self._packed_check(self.lib.sda_packed_check32_dev, scheme, dimension, indices, n_vectors, shares_ptr,
+                                  verdict_ptr, stream)
+
+    def secret_check(self, scheme, dimension: int, indexed_shares, want_verdict=True):
+        """The check of host share rows, as secret_reconstruct takes them (sda_secret_check): (ShareCheck, verdict)
+        with verdict a uint16 array of one entry per batch, or None."""
+        s = scheme.c()
+        idx = _arr([i for i, _ in indexed_shares], np.uint64)
+        arrs, ptrs, lens, n = _rows([r for _, r in indexed_shares])
+        k = max(int(getattr(scheme, "secret_count", 1) or 1), 1)
+        nb = max((dimension + k - 1) // k, arrs[0].size if arrs else 0, 1)
+        verdict = np.full(nb, 0xAAAA, np.uint16) if want_verdict else None
+        r, bad, first = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        blame = np.zeros(max(n, 1), np.uint64)
+        _check(self.lib.sda_secret_check(self.h, C.byref(s), dimension, _ptr(idx, _u64p), ptrs, lens, n,
+                                         verdict.ctypes.data if want_verdict else None,
+                                         C.byref(r), C.byref(bad), C.byref(first), _ptr(blame, _u64p)))
+        res = ShareCheck(int(r.value), int(bad.value), int(first.value), [int(x) for x in blame[:n]])
+        if not want_verdict:
+            return res, None
+        packed = getattr(s, "kind", 0) == 1
+        return res, verdict[: (dimension + k - 1) // k if packed else (arrs[0].size if arrs else 0)]
+
+    def packed_check_last_launch(self):
+        """CheckLaunch(path, bucket, located, overflowed) of the handle's last share check that launched something
+        (sda_packed_check_last_launch): all zeros before the first."""
+        path, bucket, located, over = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint32()
+        _check(self.lib.sda_packed_check_last_launch(self.h, C.byref(path), C.byref(bucket), C.byref(located),
+                                                     C.byref(over)))
+        return CheckLaunch(int(path.value), int(bucket.value), int(located.value), int(over.value))
 
     def packed_generate_keyed_dev(self, scheme, secrets_ptr, dimension, n_vectors, key, stream_id, out_ptr, mode,
                                   first_batch=0, stream=None):
