@@ -279,6 +279,39 @@ impl GpuReconstructor {
     }
 }
 
+impl GpuReconstructor {
+    /// `reconstruct` and `check` in one call (sda_secret_reconstruct_checked): the canonical secrets, with a batch in
+    /// which one clerk's share is wrong revealed from the others, and what the check found.  A batch whose verdict is
+    /// 0xFFFF holds the reveal from the first k + t shares and is not to be trusted.  PackedShamir only.
+    pub fn reconstruct_checked(&self, indexed_shares: &Vec<(usize, Vec<Share>)>)
+                               -> SdaClientResult<(Vec<Secret>, ShareCheck)> {
+        let idx: Vec<u64> = indexed_shares.iter().map(|&(i, _)| i as u64).collect();
+        let ptrs: Vec<*const i64> = indexed_shares.iter().map(|&(_, ref r)| r.as_ptr()).collect();
+        let lens: Vec<u64> = indexed_shares.iter().map(|&(_, ref r)| r.len() as u64).collect();
+        let mut out = vec![0_i64; std::cmp::max(self.dimension, 1)];
+        let mut verdict = vec![0_u16; std::cmp::max(self.dimension, 1)];
+        let mut blame = vec![0_u64; std::cmp::max(idx.len(), 1)];
+        let (mut r, mut bad, mut first) = (0_u64, 0_u64, 0_u64);
+        let (c, dim) = (self.c, self.dimension as u64);
+        self.dev.call(|h| unsafe {
+            sda_secret_reconstruct_checked(h, &c, dim, idx.as_ptr(), ptrs.as_ptr(), lens.as_ptr(), ptrs.len() as u64,
+                                           verdict.as_mut_ptr() as *mut c_void, &mut r, &mut bad, &mut first,
+                                           blame.as_mut_ptr(), out.as_mut_ptr())
+        })?;
+        let k = std::cmp::max(c.secret_count as usize, 1);
+        out.truncate(self.dimension);
+        verdict.truncate((self.dimension + k - 1) / k);
+        blame.truncate(idx.len());
+        Ok((out, ShareCheck {
+            redundancy: r as usize,
+            bad_batches: bad as usize,
+            first_bad: if first == u64::max_value() { None } else { Some(first as usize) },
+            blame: blame.into_iter().map(|x| x as usize).collect(),
+            verdict: verdict,
+        }))
+    }
+}
+
 impl SecretReconstructor for GpuReconstructor {
     fn reconstruct(&self, indexed_shares: &Vec<(usize, Vec<Share>)>) -> SdaClientResult<Vec<Secret>> {
         let idx: Vec<u64> = indexed_shares.iter().map(|&(i, _)| i as u64).collect();

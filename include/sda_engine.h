@@ -502,6 +502,53 @@ sda_status sda_secret_check(sda_engine* h, const sda_sharing_scheme* s, uint64_t
 sda_status sda_packed_check_last_launch(sda_engine* h, uint32_t* path, uint32_t* bucket, uint64_t* located,
                                         uint32_t* overflowed);
 
+/* ---- checked reveal: the check and the CANONICAL reveal in one pass, a located wrong share corrected ----
+ * Inputs as sda_packed_check_dev takes them; out [n_vectors][dimension] i64 as sda_packed_reconstruct_dev writes it
+ * (never NULL), verdict and the host outputs as the check gives them.  Per batch, with the check's verdict:
+ *   0 (consistent)          the k secrets of sda_packed_reconstruct_dev(..., SDA_REVEAL_CANONICAL) on the same
+ *                           arguments, bit for bit;
+ *   j (located at j)        the CANONICAL reveal of the n_idx - 1 shares without position j, whether j is one of the
+ *                           first k + t positions or a later one: one clerk's wrong share costs nothing;
+ *   0xFFFF (not located)    the CANONICAL reveal from the first k + t shares in the order given.  Such a batch is
+ *                           flagged garbage, as it is in sda_packed_reconstruct_dev; the rule is this one so that it
+ *                           is the same on every path.  Fall back to dropping a clerk and revealing from the rest
+ *                           (INTEGRATION.md).
+ * Output is always canonical, in [0, p): tss defines no signed representative for a corrected set, so there is no
+ * EXACT form.  The tail batch is cut at `dimension`; raw i64 shares outside (-p, p) are reduced exactly, as in the
+ * check.  r == 0 is the plain canonical reveal with zero counts; r == 1 detects and flags only.
+ * The checks, their order and their statuses are those of sda_packed_check_dev, with out == NULL where the reveal
+ * checks it (SDA_ERR_INVALID_ARGUMENT); repeated indices return SDA_ERR_UNSUPPORTED; an Additive scheme returns
+ * SDA_ERR_UNSUPPORTED (nothing to correct, no packed reveal).  dimension == 0 and n_vectors == 0 return SDA_OK with
+ * zero counts and launch nothing.  A failing call writes nothing; the call drains its stream before it returns.
+ * Schemes with at most 32 shares and k <= 8 run one fused kernel over the shares (one memset, one kernel, one small
+ * copy and one wait when every batch is consistent; bad batches add the location pass, a fix-up over them and the
+ * blame copy); all others run the check, the CANONICAL reveal and the fix-up one after the other: there a consistent
+ * batch is what sda_packed_reconstruct_dev CANONICAL returns, which past 32 shares follows tss' wrapping i64 steps for
+ * raw shares within 2^62 of the i64 limits.  The call shares the check's counter block and bad-batch log, and
+ * SDA_CHECK_LOG_CAP. */
+sda_status sda_packed_reveal_checked_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                         const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
+                                         const int64_t* shares, int64_t* out, void* verdict, uint64_t* redundancy,
+                                         uint64_t* bad_batches, uint64_t* first_bad, uint64_t* blame, void* stream);
+sda_status sda_packed_reveal_checked32_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                           const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
+                                           const int32_t* shares, int64_t* out, void* verdict, uint64_t* redundancy,
+                                           uint64_t* bad_batches, uint64_t* first_bad, uint64_t* blame, void* stream);
+/* The same from host share rows, as sda_secret_check takes them (one vector; verdict: HOST [B] or NULL; out: HOST
+ * [dimension], required when dimension > 0).  Checks and statuses are those of sda_secret_check, ragged rows included,
+ * except that an Additive scheme returns SDA_ERR_UNSUPPORTED. */
+sda_status sda_secret_reconstruct_checked(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                          const uint64_t* indices, const int64_t* const* share_rows,
+                                          const uint64_t* share_lens, uint64_t n_idx, void* verdict,
+                                          uint64_t* redundancy, uint64_t* bad_batches, uint64_t* first_bad,
+                                          uint64_t* blame, int64_t* out);
+/* How the last checked reveal on this handle that launched something ran (written when it returns SDA_OK; host-side
+ * only; all zeros before): path 1 the fused register kernel / 2 the composed path; bucket 8 / 16 / 32 shares on the
+ * fused path, else 0; fixed = the batches the fix-up kernel rewrote (fused: those located among the first k + t
+ * positions; composed: every bad batch); overflowed = more bad batches than the log held. */
+sda_status sda_packed_reveal_checked_last_launch(sda_engine* h, uint32_t* path, uint32_t* bucket, uint64_t* fixed,
+                                                 uint32_t* overflowed);
+
 /* Additive share generation: secrets [dimension], draws [dimension][n-1], out [n][dimension]. */
 sda_status sda_additive_generate_dev(sda_engine* h, int64_t modulus, uint64_t share_count,
                                      const int64_t* secrets, uint64_t dimension,

@@ -327,6 +327,7 @@ void sda_engine_destroy(sda_engine* h) {
     dev_free(h->work);
     dev_free(h->gen_log);
     dev_free(h->chk_buf);
+    dev_free(h->rep_ver);
     dev_free(h->gen32_tmp);
     dev_free(h->keyed_draws);
     dev_free(h->codec_work);
@@ -339,6 +340,7 @@ void sda_engine_destroy(sda_engine* h) {
     sda::free_table(h->gen_tab);
     sda::free_table(h->rev_tab);
     sda::free_table(h->chk_tab);
+    sda::free_table(h->rep_tab);
     if (h->rej_host) (void)hipHostFree(h->rej_host);
     if (h->hs_pin) (void)hipHostFree(h->hs_pin);
     dev_free(h->hs_dev);

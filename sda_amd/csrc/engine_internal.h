@@ -3,7 +3,7 @@
 //
 //   engine.cpp              handle life cycle, call scope, scratch, scheme helpers, the trait calls on host buffers
 //   engine_dev.cpp          the device-resident (`_dev`) entry points
-//   engine_check.cpp        the packed-Shamir share consistency check (device and host forms) and its record
+//   engine_check.cpp        the packed-Shamir share consistency check and the checked reveal (device and host forms)
 //   hbm.cpp                 sda_hbm_*: HBM buffers built from fixed-size physical chunks
 //   engine_codec.cpp        the share payload codec's host side and the snapshot transposition
 //   engine_recipient.cpp    the fused recipient pipeline, sda_recipient_reveal and the recipient job
@@ -60,6 +60,9 @@ struct sda_engine {
     sda::DeviceTable chk_tab;     // share consistency check: parity weights (per scheme + clerk set)
     void* chk_buf = nullptr;      // its counters, blame words and bad-batch log (sda::packed_check_buf_bytes())
     size_t chk_buf_bytes = 0;
+    sda::DeviceTable rep_tab;     // checked reveal: parity rows, basis Lagrange rows, inverse weights (same key)
+    void* rep_ver = nullptr;      // its verdict words when the caller gives no buffer and something is bad
+    size_t rep_ver_bytes = 0;
     void* snap = nullptr;         // snapshot transposition copy plan
     size_t snap_bytes = 0;
     // The scratch buffers above are shared by every call on the handle.  A call on another stream
@@ -91,6 +94,10 @@ struct sda_engine {
         uint32_t path = 0, bucket = 0, overflowed = 0;
         uint64_t located = 0;
     };
+    struct RepairLaunchInfo {
+        uint32_t path = 0, bucket = 0, overflowed = 0;
+        uint64_t fixed = 0;
+    };
     struct Records {
         // sda_chacha_last_launch: how the last mask combine or participant mask on this handle ran; chacha_split:
         // that call split its seeds over the handle's devices (chacha_combine_multi), each recording its own part
@@ -119,6 +126,8 @@ struct sda_engine {
         uint64_t keyed_staged_bytes = 0;
         // sda_packed_check_last_launch: written when a share check that launched something returns SDA_OK
         CheckLaunchInfo check;
+        // sda_packed_reveal_checked_last_launch: written when a checked reveal that launched something returns SDA_OK
+        RepairLaunchInfo repair;
     } last;
     // participant job (sda_participant_job, sda_participant_job_dev): the share rows [n][B] of a call (a tile of the
     // host form) and the Full mask row behind them -- int32 where they fit by construction, else i64

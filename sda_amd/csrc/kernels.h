@@ -9,6 +9,7 @@
 #include "modarith.h"
 #include "reveal_plan.h"
 #include "check_plan.h"
+#include "repair_plan.h"
 
 namespace sda {
 
@@ -205,6 +206,44 @@ hipError_t launch_packed_check(const PackedCheckArgs& a, const uint64_t* indices
                                uint32_t t, uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, DeviceTable& tab,
                                void* buf, uint32_t log_cap, hipStream_t s, uint64_t* blame_host,
                                PackedCheckResult* res);
+// The location pass alone, over `total` logged batches of `buf` or with `all` over every batch: a.verdict (when given)
+// gets the located positions and buf's blame words their counts.  tab: parity rows at stride ks.  Only enqueues.
+hipError_t launch_packed_check_locate(const PackedCheckArgs& a, uint64_t B, uint32_t n_idx, uint32_t kt,
+                                      const uint32_t* tab, uint32_t ks, const MontP& M, void* buf, uint64_t total,
+                                      bool all, hipStream_t s);
+
+// ---- packed_repair.hip ----
+// Checked reveal (sda_packed_reveal_checked_dev): the check's arguments plus out [n_vectors][dimension].
+struct PackedRepairArgs {
+    const int64_t* shares; const int32_t* shares32;   // one of the two
+    uint64_t dimension; uint64_t n_vectors;
+    uint16_t* verdict;        // device [n_vectors][B], or nullptr
+    int64_t* out;
+};
+struct PackedRepairResult {
+    uint64_t bad, first_bad;  // bad batches; the smallest bad vec * B + b, UINT64_MAX for none
+    uint64_t fixed;           // batches packed_repair_fix_kernel rewrote
+    bool overflowed;          // more bad batches than the log holds
+};
+// The table of a (scheme, indices) pair: the check's parity rows, the basis Lagrange rows and the inverse weights
+// (packed_repair.hip gives the layout).  hipErrorInvalidValue for repeated clerk points: `tab` keeps its key.
+hipError_t ensure_repair_table(DeviceTable& tab, const uint64_t* indices, uint32_t n_idx, uint32_t k, uint32_t t,
+                               uint32_t p, uint32_t omega_secrets, uint32_t omega_shares);
+// The fused first pass (packed_repair_plan: kRepairFused) and its one wait: out holds the reveal of every batch from
+// its first k + t shares, a.verdict (when given) the provisional verdicts, *res the counts.  `tab`: ensure_repair_table's;
+// `buf` and log_cap as launch_packed_check takes them.
+hipError_t launch_packed_repair(const PackedRepairArgs& a, uint32_t n_idx, uint32_t k, uint32_t t, uint32_t p,
+                                const DeviceTable& tab, void* buf, uint32_t log_cap, hipStream_t s,
+                                PackedRepairResult* res);
+// What follows a pass that counted res->bad > 0 bad batches into `buf`, and its wait.  `verdict`: never nullptr (the
+// caller's buffer, or zeroed scratch when it gave none).  locate: the location pass first (fused path; the composed
+// path's share check has run it).  recompute: every bad batch is first revealed again from its first k + t shares
+// (composed path: out holds the reveal from all shares); a batch located at a basis position is corrected either way.
+// Fills res->fixed, res->overflowed and, with locate, blame_host[n_idx].
+hipError_t launch_packed_repair_fix(const PackedRepairArgs& a, uint16_t* verdict, uint32_t n_idx, uint32_t k,
+                                    uint32_t t, uint32_t p, const DeviceTable& tab, void* buf, uint32_t log_cap,
+                                    bool locate, bool recompute, hipStream_t s, uint64_t* blame_host,
+                                    PackedRepairResult* res);
 
 // ---- codec_decode.hip (share payload codec: sodium.rs:36-41 / :82-88, integer-encoding 1.0 VarInt) ----
 // Host-side plan of the decode: blobs are split into 4 KiB regions aligned to the (16-byte

@@ -12,66 +12,15 @@
 // Device table (u32 words, Montgomery form): w[c][s] at c * KS + s, KS = kt rounded up to even, the pad word 0 (the
 // kernels take the products of a row in pairs that share one REDC, as reveal_canon_body does).
 //
-// Counter block (u64 words; `buf` of packed_check_buf_bytes()): [0] bad batches, [1] ~(first bad flat index) under
-// atomicMax (0: none), [kCheckHdr, +kCheckBlameCap) blame per position, then the log of bad flat indices vec * B + b.
-#include "packed_common.h"
+// The counter block, check_report and the register tuple of a batch are check_common.h's (shared with the checked
+// reveal, packed_repair.hip).
+#include "check_common.h"
 #include "check_plan.h"
 
 namespace sda {
 using namespace packed;
 
 namespace {
-
-constexpr uint32_t kCheckHdr = 4, kCheckBlameCap = 1024;
-static_assert(kRevealMaxShares < kCheckBlameCap, "one blame word per clerk position");
-
-// the exact canonical residue of any share value
-__device__ __forceinline__ uint32_t canon_exact(int64_t v, int64_t P, const Mod64& PM) {
-    const int64_t r = trem64(v, PM);
-    return (uint32_t)(r < 0 ? r + P : r);
-}
-template <class ST>
-__device__ __forceinline__ uint32_t canon_any(ST v, uint32_t p, int64_t P, const Mod64& PM) {
-    return share_in_range(v, p, P) ? canon32((int32_t)v, p) : canon_exact((int64_t)v, P, PM);
-}
-
-// What a lane reports for its batch: the provisional verdict (0 / 0xFFFF; the location pass overwrites located ones),
-// and per wave one add of its bad count, one max for the first bad index and a log slot per bad lane.
-// The first thread id of the calling wave, as a uniform value (workgroups are 256 x 1 x 1: a wave's lanes are 64
-// consecutive threads).
-__device__ __forceinline__ uint32_t wave_first_thread() {
-    return __builtin_amdgcn_readfirstlane(threadIdx.x) & ~63u;
-}
-
-__device__ __forceinline__ void check_report(bool nonzero, uint32_t wave0, uint64_t B, uint16_t* __restrict__ verdict,
-                                             unsigned long long* __restrict__ cnt, uint32_t cap) {
-    // The batch's place is worked out here, after the arithmetic, from uniform values (wave0: taken before the
-    // loads, a scalar) and the lane's number in its wave: no vector register carries it across the loads.
-    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const uint32_t tid = wave0 + lane;
-    const uint64_t b0 = (uint64_t)blockIdx.x * 256;
-    const bool live = tid < B - b0;
-    const bool bad = live && nonzero;
-    const uint64_t flat = ((uint64_t)blockIdx.y * B + b0) + tid;
-    const uint64_t mask = __ballot(bad);
-    if (mask) {
-        const uint32_t first = (uint32_t)__ffsll((unsigned long long)mask) - 1;
-        uint32_t lo = 0, hi = 0;
-        if (lane == first) {                     // lanes hold ascending batches of one vector: the wave's minimum
-            const unsigned long long base = atomicAdd(cnt, (unsigned long long)__popcll(mask));
-            atomicMax(cnt + 1, ~(unsigned long long)flat);
-            lo = (uint32_t)base;
-            hi = (uint32_t)(base >> 32);
-        }
-        lo = __shfl(lo, first);
-        hi = __shfl(hi, first);
-        if (bad) {
-            const uint64_t slot = (((uint64_t)hi << 32) | lo) + __popcll(mask & ((1ull << lane) - 1));
-            if (slot < cap) cnt[kCheckHdr + kCheckBlameCap + slot] = flat;
-        }
-    }
-    if (verdict && live) verdict[flat] = bad ? (uint16_t)0xFFFF : (uint16_t)0;
-}
 
 // One lane = one batch, its n_idx <= NMAX shares in registers: every load is issued before the first wait, each
 // share becomes its canonical residue as it lands (raw i64 shares outside (-p, p): reduced exactly in registers,
@@ -85,40 +34,12 @@ __device__ __forceinline__ void check_body(const ST* __restrict__ shares, uint64
     const uint32_t wave0 = wave_first_thread();
     const uint64_t b0 = (uint64_t)blockIdx.x * 256, rest = B - b0;
     const ST* sh = shares + ((uint64_t)blockIdx.y * n_idx * B + b0) + (threadIdx.x < rest ? threadIdx.x : (uint32_t)rest - 1);
-    auto share = [&](uint32_t i) { return sh[(uint64_t)i * B]; };
     const uint32_t p = M.p;
-    const int64_t P = (int64_t)p;
-
-    // the residues as one register tuple: share kt + c of parity row c is then a uniform-index move, not a select
-    using SV = uint32_t __attribute__((ext_vector_type(NMAX)));
-    SV S;
-    bool in_range = true;
-    {
-        ST v[NMAX];
-        static_for<0, NMAX>([&](auto i) { v[i] = share((uint32_t)i < n_idx ? i : 0); });
-        static_for<0, NMAX>([&](auto i) {
-            in_range = in_range && ((uint32_t)i >= n_idx || share_in_range(v[i], p, P));
-            S[(int)i] = (uint32_t)i < n_idx ? canon32((int32_t)v[i], p) : 0u;
-        });
-    }
-    if (!in_range) {
-        const Mod64 PM = make_mod64(P);
-        for (uint32_t i = 0; i < n_idx; ++i) S[i & (NMAX - 1)] = canon_exact((int64_t)share(i), P, PM);
-    }
+    const ShareTuple<NMAX> S = load_residues<ST, NMAX>(sh, B, n_idx, p);
     const uint32_t r = n_idx - kt;
     uint32_t nz = 0;
-    for (uint32_t c = 0; c < r; ++c) {
-        const uint32_t* w = tab + (size_t)c * ks;
-        uint32_t acc = 0;
-        static_for<0, NMAX, 2>([&](auto i) {
-            if ((uint32_t)i < kt) {
-                uint64_t T = (uint64_t)w[i] * S[(int)i];
-                if constexpr (i + 1 < NMAX) T += (uint64_t)w[i + 1] * S[(int)i + 1];     // the pad word past kt is 0
-                acc = addm(acc, red1(redc_lazy(T, M), p), p);
-            }
-        });
-        nz |= addm(acc, S[(kt + c) & (NMAX - 1)], p);     // kt + c < n_idx <= NMAX
-    }
+    for (uint32_t c = 0; c < r; ++c)
+        nz |= addm(row_mac<NMAX>(tab + (size_t)c * ks, S, kt, M), S[(kt + c) & (NMAX - 1)], p);     // kt + c < n_idx <= NMAX
     check_report(nz != 0, wave0, B, verdict, cnt, cap);
 }
 
@@ -272,6 +193,21 @@ __global__ __launch_bounds__(64) void packed_check32_locate_kernel(const int32_t
     check_locate_body(shares, B, n_idx, kt, tab, ks, M, verdict, cnt, total, all);
 }
 
+// The location pass over `total` logged batches, or with `all` over every batch of the launch.
+template <class ST>
+hipError_t check_locate_launch_t(const ST* sh, uint16_t* verdict, uint64_t B, uint32_t n_idx, uint32_t kt,
+                                 const uint32_t* tab, uint32_t ks, const MontP& M, unsigned long long* cnt,
+                                 uint64_t total, bool all, hipStream_t s) {
+    const unsigned waves = (unsigned)(total < 8192 ? total : 8192);
+    if constexpr (sizeof(ST) == 4)
+        hipLaunchKernelGGL(packed_check32_locate_kernel, dim3(waves), dim3(64), 0, s, sh, B, n_idx, kt, tab, ks, M,
+                           verdict, cnt, total, all ? 1 : 0);
+    else
+        hipLaunchKernelGGL(packed_check_locate_kernel, dim3(waves), dim3(64), 0, s, sh, B, n_idx, kt, tab, ks, M,
+                           verdict, cnt, total, all ? 1 : 0);
+    return hipGetLastError();
+}
+
 // The launches of one call for share type ST: the kernel the plan names, the counters read back (one wait), then the
 // location pass over what the first pass logged (a second wait) when something is bad and r >= 2.
 template <class ST>
@@ -311,14 +247,8 @@ hipError_t check_launch_t(const PackedCheckPlan& pl, const PackedCheckArgs& a, c
     res->overflowed = res->bad > cap;
     const uint64_t total = res->overflowed ? B * a.n_vectors : res->bad;
     res->located = total;
-    const unsigned waves = (unsigned)(total < 8192 ? total : 8192);
-    if constexpr (I32)
-        hipLaunchKernelGGL(packed_check32_locate_kernel, dim3(waves), dim3(64), 0, s, sh, B, n_idx, kt, tab, ks, M,
-                           a.verdict, cnt, total, res->overflowed ? 1 : 0);
-    else
-        hipLaunchKernelGGL(packed_check_locate_kernel, dim3(waves), dim3(64), 0, s, sh, B, n_idx, kt, tab, ks, M,
-                           a.verdict, cnt, total, res->overflowed ? 1 : 0);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = check_locate_launch_t(sh, a.verdict, B, n_idx, kt, tab, ks, M, cnt, total, res->overflowed, s)) != hipSuccess)
+        return e;
     if ((e = hipMemcpyAsync(blame_host, cnt + kCheckHdr, (size_t)n_idx * sizeof(uint64_t), hipMemcpyDeviceToHost, s)) !=
         hipSuccess)
         return e;
@@ -326,6 +256,14 @@ hipError_t check_launch_t(const PackedCheckPlan& pl, const PackedCheckArgs& a, c
 }
 
 }  // namespace
+
+hipError_t launch_packed_check_locate(const PackedCheckArgs& a, uint64_t B, uint32_t n_idx, uint32_t kt,
+                                      const uint32_t* tab, uint32_t ks, const MontP& M, void* buf, uint64_t total,
+                                      bool all, hipStream_t s) {
+    unsigned long long* cnt = static_cast<unsigned long long*>(buf);
+    return a.shares32 ? check_locate_launch_t(a.shares32, a.verdict, B, n_idx, kt, tab, ks, M, cnt, total, all, s)
+                      : check_locate_launch_t(a.shares, a.verdict, B, n_idx, kt, tab, ks, M, cnt, total, all, s);
+}
 
 size_t packed_check_buf_bytes() { return (size_t)(kCheckHdr + kCheckBlameCap + kCheckLogCap) * sizeof(uint64_t); }
 

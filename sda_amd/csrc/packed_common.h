@@ -171,16 +171,24 @@ inline RevealTables make_reveal_tables(const uint64_t* indices, uint32_t n_idx, 
 //   syndrome_c = share_{kt+c} + sum_{s < kt} w[c kt + s] share_s  (mod p),  w[c kt + s] = -l_{s+1}(x_{L+c}),
 // l_i the Lagrange basis over the first L points (point 0 carries the value 0, so it has no weight).  Canonical words;
 // every one is nonzero (l_i vanishes at the other basis points only).  Distinct points only (!T.duplicate).
-inline std::vector<int64_t> make_check_weights(const RevealTables& T, uint32_t n_idx, uint32_t kt, int64_t p) {
-    const uint32_t m = n_idx + 1, L = kt + 1, r = n_idx - kt;
+// den[i] = prod_{j < L, j != i} 1 / (x_i - x_j), 1 <= i < L: the Lagrange denominators over the first L of the m
+// points, from the table's inverses (den[0] stays 1: point 0 has no weight).
+inline std::vector<int64_t> basis_denominators(const RevealTables& T, uint32_t m, uint32_t L, int64_t p) {
     auto inv = [&](uint32_t a, uint32_t b) { return T.h[(uint64_t)(a - b) * m + a]; };   // 1 / (x_a - x_b), a > b
-    // den[i] = prod_{j < L, j != i} 1 / (x_i - x_j)
-    std::vector<int64_t> den(L, 1), w((uint64_t)r * kt, 0);
+    std::vector<int64_t> den(L, 1);
     for (uint32_t i = 1; i < L; ++i)
         for (uint32_t j = 0; j < L; ++j) {
             if (j == i) continue;
             den[i] = den[i] * (j < i ? inv(i, j) : p - inv(j, i)) % p;
         }
+    return den;
+}
+
+inline std::vector<int64_t> make_check_weights(const RevealTables& T, uint32_t n_idx, uint32_t kt, int64_t p) {
+    const uint32_t m = n_idx + 1, L = kt + 1, r = n_idx - kt;
+    auto inv = [&](uint32_t a, uint32_t b) { return T.h[(uint64_t)(a - b) * m + a]; };   // 1 / (x_a - x_b), a > b
+    const std::vector<int64_t> den = basis_denominators(T, m, L, p);
+    std::vector<int64_t> w((uint64_t)r * kt, 0);
     for (uint32_t c = 0; c < r; ++c) {
         int64_t num = 1;                                  // prod_{j < L} (x_{L+c} - x_j)
         for (uint32_t j = 0; j < L; ++j) {
@@ -193,6 +201,38 @@ inline std::vector<int64_t> make_check_weights(const RevealTables& T, uint32_t n
         }
     }
     return w;
+}
+
+// The tables of the checked reveal's correction (packed_repair.hip), from the same points and inverses.  Canonical
+// words; distinct points only (!T.duplicate).
+//   lam[e kt + s]  the basis Lagrange rows: l_{s+1}(omega_secrets^(e+1)) over the first L = kt + 1 points, e < k,
+//                  s < kt -- the CANONICAL reveal's weights for indices[0 .. kt) alone (point 0 carries the value 0 and
+//                  has no weight), so  secret_e = sum_s lam[e kt + s] share_s  for a consistent batch
+//   winv[s]        1 / w[0][s] for parity row 0 of make_check_weights (`w`; r >= 1), else empty: a single error e at
+//                  basis position s gives syndrome_0 = e w[0][s], so e = syndrome_0 winv[s]
+// A secret's point is never a clerk's: omega_secrets has order 2^a, omega_shares order 3^b, and neither power is 1.
+struct RepairTables { std::vector<int64_t> lam, winv; };
+inline RepairTables make_repair_tables(const RevealTables& T, uint32_t n_idx, uint32_t k, uint32_t kt, int64_t p,
+                                       int64_t ws, const std::vector<int64_t>& w) {
+    const uint32_t m = n_idx + 1, L = kt + 1;
+    const std::vector<int64_t> den = basis_denominators(T, m, L, p);
+    RepairTables R;
+    R.lam.assign((uint64_t)k * kt, 0);
+    for (uint32_t e = 0; e < k; ++e) {
+        const int64_t point = h_powmod(ws, e + 1, p);
+        std::vector<int64_t> d(L);                        // X - x_j, canonical
+        int64_t num = 1;
+        for (uint32_t j = 0; j < L; ++j) {
+            d[j] = (point - T.pts[j]) % p; if (d[j] < 0) d[j] += p;
+            num = num * d[j] % p;
+        }
+        for (uint32_t i = 1; i < L; ++i) R.lam[(uint64_t)e * kt + (i - 1)] = num * h_modinv(d[i], p) % p * den[i] % p;
+    }
+    if (n_idx > kt) {
+        R.winv.resize(kt);
+        for (uint32_t s = 0; s < kt; ++s) R.winv[s] = h_modinv(w[s], p);
+    }
+    return R;
 }
 
 // Rust `v % p` from the canonical residue c and the sign word sw of the exact dividend v.
@@ -327,6 +367,33 @@ __device__ __forceinline__ bool share_in_range(int64_t v, uint32_t, int64_t P) {
 }
 __device__ __forceinline__ bool share_in_range(int32_t v, uint32_t p, int64_t) {
     return (uint32_t)v + (p - 1) <= 2 * p - 2;
+}
+
+// The k secrets of a batch are adjacent in `out` (batched.rs:94 appends batch after batch), so a
+// lane's own stores would stride by 8k bytes.  With STAGED the workgroup parks its results in
+// LDS ([lane][k]) and writes the nb*k block back with coalesced stores.
+// The results leave as nontemporal stores (written once, streamed out), 16 bytes per lane when the block's
+// output is 16-byte aligned (lds_o is the dynamic LDS base, so 16-byte aligned too): canonical reveal -1.4 to
+// -2.8 %, exact -0.7 to -1.1 % against 8-byte cached stores (in-process A/B on two boxes, profiles/r06ab, r06ac).
+template <bool STAGED>
+__device__ __forceinline__ void reveal_flush(int64_t* lds_o, int64_t* o, uint64_t b0, uint64_t B, uint64_t D,
+                                             uint32_t k) {
+    if constexpr (STAGED) {
+        __syncthreads();
+        const uint64_t first = b0 * k;
+        const uint64_t last = (b0 + 256 < B ? b0 + 256 : B) * k;
+        const uint32_t cnt = (uint32_t)((last < D ? last : D) - first);
+        int64_t* dst = o + first;
+        if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+            using V2 = int64_t __attribute__((ext_vector_type(2)));
+            const V2* src2 = reinterpret_cast<const V2*>(lds_o);
+            V2* dst2 = reinterpret_cast<V2*>(dst);
+            for (uint32_t j = threadIdx.x; j < cnt / 2; j += 256) __builtin_nontemporal_store(src2[j], dst2 + j);
+            if ((cnt & 1) && threadIdx.x == 0) __builtin_nontemporal_store(lds_o[cnt - 1], dst + cnt - 1);
+        } else {
+            for (uint32_t j = threadIdx.x; j < cnt; j += 256) __builtin_nontemporal_store(lds_o[j], dst + j);
+        }
+    }
 }
 
 constexpr int ilog(int x, int b) { return x <= 1 ? 0 : 1 + ilog(x / b, b); }

@@ -1,0 +1,261 @@
+// packed_repair.hip -- checked reveal: the share consistency check and the CANONICAL reveal in one pass over the
+// shares, with a located wrong share corrected (sda_packed_reveal_checked_dev).
+//
+// The check is systematic (packed_check.hip): the first kt = k + t shares of a batch fix its polynomial and r parity
+// rows test the others.  Once a batch is consistent, its reveal from all n_idx shares equals its reveal from the kt
+// basis shares alone, so packed_repair_kernel computes, from one load of the batch,
+//   syndrome_c = share_{kt+c} + sum_{s < kt} w[c][s] share_s,  c < r        (bad iff some syndrome != 0)
+//   secret_e   = sum_{s < kt} lam[e][s] share_s,               e < k        (make_repair_tables' basis rows)
+// and reports a bad batch exactly as the check does.  What the basis reveal means for a bad batch:
+//   located at a check position j > kt   the basis is clean: already the reveal without share j
+//   not located                          the reveal from the first kt shares: flagged garbage, the rule on every path
+//   located at a basis position j <= kt  share j carries an error err with syndrome_0 = err w[0][j-1], so
+//                                        err = syndrome_0 winv[j-1]  and  secret_e -= lam[e][j-1] err
+// The last is packed_repair_fix_kernel's work, behind packed_check_locate_kernel, launched only when something is bad.
+// Schemes past the fused kernel (repair_plan.h) run the share check and the CANONICAL reveal as they are, and the
+// fix-up then recomputes every bad batch from its basis before it corrects.
+//
+// Device table (u32 words, Montgomery form, rows of KS = kt rounded up to even words, pad word 0):
+//   rows [0, r)       the check's parity rows w[c][s]
+//   rows [r, r + k)   lam[e][s]
+//   row  r + k        winv[s] (zeros when r == 0)
+#include "check_common.h"
+#include "repair_plan.h"
+
+namespace sda {
+using namespace packed;
+
+namespace {
+
+// One lane = one batch, in check_body's shape: the loads, the residues as one register tuple, the r syndrome rows,
+// then k rows against lam into the workgroup's LDS block ([lane][k]), the report, and reveal_flush's coalesced
+// write-back (16-byte nontemporal stores when the block's output is 16-byte aligned, 8-byte ones otherwise; the tail
+// batch is cut at `dimension` there).  Lanes past the last batch hold the last batch again; neither pass keeps them.
+template <class ST, int NMAX>
+__device__ __forceinline__ void repair_body(const ST* __restrict__ shares, uint64_t B, uint64_t D,
+                                            int64_t* __restrict__ out, uint32_t n_idx, uint32_t kt, uint32_t k,
+                                            const uint32_t* __restrict__ tab, uint32_t ks, const MontP& M,
+                                            uint16_t* __restrict__ verdict, unsigned long long* __restrict__ cnt,
+                                            uint32_t cap, int64_t* lds_o) {
+    const uint32_t wave0 = wave_first_thread();
+    const uint64_t b0 = (uint64_t)blockIdx.x * 256, rest = B - b0;
+    const ST* sh = shares + ((uint64_t)blockIdx.y * n_idx * B + b0) + (threadIdx.x < rest ? threadIdx.x : (uint32_t)rest - 1);
+    const uint32_t p = M.p;
+    const ShareTuple<NMAX> S = load_residues<ST, NMAX>(sh, B, n_idx, p);
+    const uint32_t r = n_idx - kt;
+    uint32_t nz = 0;
+    for (uint32_t c = 0; c < r; ++c)
+        nz |= addm(row_mac<NMAX>(tab + (size_t)c * ks, S, kt, M), S[(kt + c) & (NMAX - 1)], p);     // kt + c < n_idx <= NMAX
+    const uint32_t* lam = tab + (size_t)r * ks;
+    int64_t* dst = lds_o + threadIdx.x * k;
+    for (uint32_t e = 0; e < k; ++e) dst[e] = (int64_t)row_mac<NMAX>(lam + (size_t)e * ks, S, kt, M);
+    check_report(nz != 0, wave0, B, verdict, cnt, cap);
+    reveal_flush<true>(lds_o, out + (uint64_t)blockIdx.y * D, b0, B, D, k);
+}
+
+template <int NMAX>
+__global__ __launch_bounds__(256) void packed_repair_kernel(const int64_t* __restrict__ shares, uint64_t B, uint64_t D,
+                                                            int64_t* __restrict__ out, uint32_t n_idx, uint32_t kt,
+                                                            uint32_t k, const uint32_t* __restrict__ tab, uint32_t ks,
+                                                            MontP M, uint16_t* __restrict__ verdict,
+                                                            unsigned long long* __restrict__ cnt, uint32_t cap) {
+    extern __shared__ int64_t lds_o[];
+    repair_body<int64_t, NMAX>(shares, B, D, out, n_idx, kt, k, tab, ks, M, verdict, cnt, cap, lds_o);
+}
+
+template <int NMAX>
+__global__ __launch_bounds__(256) void packed_repair32_kernel(const int32_t* __restrict__ shares, uint64_t B,
+                                                              uint64_t D, int64_t* __restrict__ out, uint32_t n_idx,
+                                                              uint32_t kt, uint32_t k,
+                                                              const uint32_t* __restrict__ tab, uint32_t ks, MontP M,
+                                                              uint16_t* __restrict__ verdict,
+                                                              unsigned long long* __restrict__ cnt, uint32_t cap) {
+    extern __shared__ int64_t lds_o[];
+    repair_body<int32_t, NMAX>(shares, B, D, out, n_idx, kt, k, tab, ks, M, verdict, cnt, cap, lds_o);
+}
+
+// One lane per bad batch -- the `total` logged ones, or with `all` every batch of the call (the log overflowed).  A
+// batch located at a basis position (1 <= verdict <= kt) is corrected; syndrome_0 is recomputed from the batch's
+// kt + 1 shares.  Without `recompute` (fused path) the others are right as they stand; with it (composed path) every
+// batch whose verdict is not 0 is first revealed again from its basis.  cnt[2] counts the batches rewritten.
+template <class ST>
+__device__ __forceinline__ void repair_fix_body(const ST* __restrict__ shares, uint64_t B, uint64_t D,
+                                                int64_t* __restrict__ out, uint32_t n_idx, uint32_t kt, uint32_t k,
+                                                const uint32_t* __restrict__ tab, uint32_t ks, const MontP& M,
+                                                const uint16_t* __restrict__ verdict,
+                                                unsigned long long* __restrict__ cnt, uint64_t total, int all,
+                                                int recompute) {
+    const uint32_t p = M.p, r = n_idx - kt;
+    const int64_t P = (int64_t)p;
+    const Mod64 PM = make_mod64(P);
+    const uint32_t* lam = tab + (size_t)r * ks;
+    const uint32_t* winv = lam + (size_t)k * ks;
+    const unsigned long long* list = cnt + kCheckHdr + kCheckBlameCap;
+    uint32_t mine = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t gb = all ? i : list[i];
+        const uint32_t v = verdict[gb];
+        const bool basis = v >= 1 && v <= kt;
+        if (recompute ? v == 0 : !basis) continue;
+        const uint64_t vec = gb / B, b = gb - vec * B;
+        const uint32_t lim = b * k < D ? (uint32_t)(D - b * k < k ? D - b * k : k) : 0u;
+        const ST* sh = shares + vec * (uint64_t)n_idx * B + b;
+        int64_t* dst = out + vec * D + b * k;
+        auto share = [&](uint32_t s) { return canon_any(sh[(uint64_t)s * B], p, P, PM); };
+        uint32_t err = 0;
+        if (basis) {                                      // located: r >= 2, so share kt exists
+            uint32_t s0 = share(kt);
+            for (uint32_t s = 0; s < kt; ++s) s0 = addm(s0, mont_mul(tab[s], share(s), M), p);
+            err = mont_mul(winv[v - 1], s0, M);
+        }
+        for (uint32_t e = 0; e < lim; ++e) {
+            const uint32_t* le = lam + (size_t)e * ks;
+            uint32_t acc = 0;
+            if (recompute)
+                for (uint32_t s = 0; s < kt; ++s) acc = addm(acc, mont_mul(le[s], share(s), M), p);
+            else
+                acc = (uint32_t)dst[e];
+            if (basis) acc = subm(acc, mont_mul(le[v - 1], err, M), p);
+            dst[e] = (int64_t)acc;
+        }
+        ++mine;
+    }
+    for (int off = 32; off; off >>= 1) mine += (uint32_t)__shfl_xor((int)mine, off);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(cnt + 2, (unsigned long long)mine);
+}
+
+__global__ __launch_bounds__(256) void packed_repair_fix_kernel(const int64_t* __restrict__ shares, uint64_t B,
+                                                                uint64_t D, int64_t* __restrict__ out, uint32_t n_idx,
+                                                                uint32_t kt, uint32_t k,
+                                                                const uint32_t* __restrict__ tab, uint32_t ks, MontP M,
+                                                                const uint16_t* __restrict__ verdict,
+                                                                unsigned long long* __restrict__ cnt, uint64_t total,
+                                                                int all, int recompute) {
+    repair_fix_body(shares, B, D, out, n_idx, kt, k, tab, ks, M, verdict, cnt, total, all, recompute);
+}
+
+__global__ __launch_bounds__(256) void packed_repair32_fix_kernel(const int32_t* __restrict__ shares, uint64_t B,
+                                                                  uint64_t D, int64_t* __restrict__ out,
+                                                                  uint32_t n_idx, uint32_t kt, uint32_t k,
+                                                                  const uint32_t* __restrict__ tab, uint32_t ks,
+                                                                  MontP M, const uint16_t* __restrict__ verdict,
+                                                                  unsigned long long* __restrict__ cnt, uint64_t total,
+                                                                  int all, int recompute) {
+    repair_fix_body(shares, B, D, out, n_idx, kt, k, tab, ks, M, verdict, cnt, total, all, recompute);
+}
+
+// The fused first pass for share type ST: counters zeroed, the bucket's kernel, the counts read back (one wait).
+template <class ST>
+hipError_t repair_launch_t(const PackedRepairPlan& pl, const PackedRepairArgs& a, const ST* sh, uint64_t B,
+                           uint32_t n_idx, uint32_t kt, uint32_t k, const uint32_t* tab, uint32_t ks, const MontP& M,
+                           unsigned long long* cnt, uint32_t cap, hipStream_t s, PackedRepairResult* res) {
+    const dim3 grid((unsigned)((B + 255) / 256), (unsigned)a.n_vectors);
+    const size_t lds = (size_t)256 * k * sizeof(int64_t);
+    auto bucket = [&](auto nmax) {
+        auto kernel = [&] {
+            if constexpr (sizeof(ST) == 4) return packed_repair32_kernel<nmax>; else return packed_repair_kernel<nmax>;
+        }();
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, sh, B, a.dimension, a.out, n_idx, kt, k, tab, ks, M,
+                           a.verdict, cnt, cap);
+    };
+    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)(kCheckHdr + kCheckBlameCap) * sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    if (pl.bucket == 8) bucket(std::integral_constant<int, 8>{});
+    else if (pl.bucket == 16) bucket(std::integral_constant<int, 16>{});
+    else if (pl.bucket == 32) bucket(std::integral_constant<int, 32>{});
+    else return hipErrorInvalidValue;
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    uint64_t head[2] = {0, 0};
+    if ((e = hipMemcpyAsync(head, cnt, sizeof(head), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+    res->bad = head[0];
+    res->first_bad = ~head[1];                              // 0 (no max taken) -> UINT64_MAX
+    return hipSuccess;
+}
+
+std::vector<uint8_t> repair_key(const uint64_t* indices, uint32_t n_idx, uint32_t k, uint32_t t, uint32_t p,
+                                uint32_t omega_secrets, uint32_t omega_shares) {
+    std::vector<uint8_t> key(sizeof(uint32_t) * 6 + sizeof(uint64_t) * n_idx);
+    const uint32_t kv[6] = {n_idx, k, t, p, omega_secrets, omega_shares};
+    memcpy(key.data(), kv, sizeof(kv));
+    memcpy(key.data() + sizeof(kv), indices, sizeof(uint64_t) * n_idx);
+    return key;
+}
+
+}  // namespace
+
+hipError_t ensure_repair_table(DeviceTable& tab, const uint64_t* indices, uint32_t n_idx, uint32_t k, uint32_t t,
+                               uint32_t p, uint32_t omega_secrets, uint32_t omega_shares) {
+    const std::vector<uint8_t> key = repair_key(indices, n_idx, k, t, p, omega_secrets, omega_shares);
+    if (tab.key == key) return hipSuccess;
+    const uint32_t kt = k + t, r = n_idx - kt, ks = (kt + 1) & ~1u;
+    const RevealTables T = make_reveal_tables(indices, n_idx, k, p, omega_secrets, omega_shares);
+    if (T.duplicate) return hipErrorInvalidValue;         // repeated points have no systematic form
+    const std::vector<int64_t> w = r ? make_check_weights(T, n_idx, kt, p) : std::vector<int64_t>();
+    const RepairTables R = make_repair_tables(T, n_idx, k, kt, p, omega_secrets, w);
+    std::vector<uint32_t> host((size_t)(r + k + 1) * ks, 0);
+    for (uint32_t c = 0; c < r; ++c)
+        for (uint32_t i = 0; i < kt; ++i) host[(size_t)c * ks + i] = to_mont(w[(size_t)c * kt + i], p);
+    for (uint32_t e = 0; e < k; ++e)
+        for (uint32_t i = 0; i < kt; ++i) host[(size_t)(r + e) * ks + i] = to_mont(R.lam[(size_t)e * kt + i], p);
+    for (uint32_t i = 0; i < kt && r; ++i) host[(size_t)(r + k) * ks + i] = to_mont(R.winv[i], p);
+    return ensure_table(tab, key, host.data(), host.size() * sizeof(uint32_t));
+}
+
+hipError_t launch_packed_repair(const PackedRepairArgs& a, uint32_t n_idx, uint32_t k, uint32_t t, uint32_t p,
+                                const DeviceTable& tab, void* buf, uint32_t log_cap, hipStream_t s,
+                                PackedRepairResult* res) {
+    const PackedRepairPlan pl = packed_repair_plan(n_idx, k, t);
+    if (pl.path != kRepairFused) return hipErrorInvalidValue;
+    const uint32_t kt = k + t, ks = (kt + 1) & ~1u;
+    const uint64_t B = (a.dimension + k - 1) / k;
+    const MontP M = make_mont(p);
+    const uint32_t cap = log_cap < kCheckLogCap ? log_cap : kCheckLogCap;
+    unsigned long long* cnt = static_cast<unsigned long long*>(buf);
+    const uint32_t* dtab = static_cast<const uint32_t*>(tab.dev);
+    res->bad = res->fixed = 0;
+    res->first_bad = UINT64_MAX;
+    res->overflowed = false;
+    return a.shares32 ? repair_launch_t(pl, a, a.shares32, B, n_idx, kt, k, dtab, ks, M, cnt, cap, s, res)
+                      : repair_launch_t(pl, a, a.shares, B, n_idx, kt, k, dtab, ks, M, cnt, cap, s, res);
+}
+
+hipError_t launch_packed_repair_fix(const PackedRepairArgs& a, uint16_t* verdict, uint32_t n_idx, uint32_t k,
+                                    uint32_t t, uint32_t p, const DeviceTable& tab, void* buf, uint32_t log_cap,
+                                    bool locate, bool recompute, hipStream_t s, uint64_t* blame_host,
+                                    PackedRepairResult* res) {
+    const uint32_t kt = k + t, ks = (kt + 1) & ~1u;
+    const uint64_t B = (a.dimension + k - 1) / k;
+    const MontP M = make_mont(p);
+    const uint32_t cap = log_cap < kCheckLogCap ? log_cap : kCheckLogCap;
+    unsigned long long* cnt = static_cast<unsigned long long*>(buf);
+    const uint32_t* dtab = static_cast<const uint32_t*>(tab.dev);
+    res->overflowed = res->bad > cap;
+    const uint64_t total = res->overflowed ? B * a.n_vectors : res->bad;
+    const int all = res->overflowed ? 1 : 0;
+    hipError_t e;
+    if (locate) {
+        const PackedCheckArgs ca{a.shares, a.shares32, a.dimension, a.n_vectors, verdict};
+        if ((e = launch_packed_check_locate(ca, B, n_idx, kt, dtab, ks, M, buf, total, res->overflowed, s)) != hipSuccess)
+            return e;
+    }
+    const uint64_t blocks = (total + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
+    if (a.shares32)
+        hipLaunchKernelGGL(packed_repair32_fix_kernel, grid, dim3(256), 0, s, a.shares32, B, a.dimension, a.out, n_idx,
+                           kt, k, dtab, ks, M, verdict, cnt, total, all, recompute ? 1 : 0);
+    else
+        hipLaunchKernelGGL(packed_repair_fix_kernel, grid, dim3(256), 0, s, a.shares, B, a.dimension, a.out, n_idx, kt,
+                           k, dtab, ks, M, verdict, cnt, total, all, recompute ? 1 : 0);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    std::vector<uint64_t> back(kCheckHdr + n_idx, 0);
+    if ((e = hipMemcpyAsync(back.data(), cnt, back.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
+        return e;
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+    res->fixed = back[2];
+    if (locate)
+        for (uint32_t j = 0; j < n_idx; ++j) blame_host[j] = back[kCheckHdr + j];
+    return hipSuccess;
+}
+
+}  // namespace sda

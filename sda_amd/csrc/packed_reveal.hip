@@ -32,32 +32,7 @@ struct FE {
     uint32_t c;
 };
 
-// The k secrets of a batch are adjacent in `out` (batched.rs:94 appends batch after batch), so a
-// lane's own stores would stride by 8k bytes.  With STAGED the workgroup parks its results in
-// LDS ([lane][k]) and writes the nb*k block back with coalesced stores.
-// The results leave as nontemporal stores (written once, streamed out), 16 bytes per lane when the block's
-// output is 16-byte aligned (lds_o is the dynamic LDS base, so 16-byte aligned too): canonical reveal -1.4 to
-// -2.8 %, exact -0.7 to -1.1 % against 8-byte cached stores (in-process A/B on two boxes, profiles/r06ab, r06ac).
-template <bool STAGED>
-__device__ __forceinline__ void reveal_flush(int64_t* lds_o, int64_t* o, uint64_t b0, uint64_t B, uint64_t D,
-                                             uint32_t k) {
-    if constexpr (STAGED) {
-        __syncthreads();
-        const uint64_t first = b0 * k;
-        const uint64_t last = (b0 + 256 < B ? b0 + 256 : B) * k;
-        const uint32_t cnt = (uint32_t)((last < D ? last : D) - first);
-        int64_t* dst = o + first;
-        if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-            using V2 = int64_t __attribute__((ext_vector_type(2)));
-            const V2* src2 = reinterpret_cast<const V2*>(lds_o);
-            V2* dst2 = reinterpret_cast<V2*>(dst);
-            for (uint32_t j = threadIdx.x; j < cnt / 2; j += 256) __builtin_nontemporal_store(src2[j], dst2 + j);
-            if ((cnt & 1) && threadIdx.x == 0) __builtin_nontemporal_store(lds_o[cnt - 1], dst + cnt - 1);
-        } else {
-            for (uint32_t j = threadIdx.x; j < cnt; j += 256) __builtin_nontemporal_store(lds_o[j], dst + j);
-        }
-    }
-}
+// reveal_flush (packed_common.h) writes a workgroup's staged results back.
 
 // gather [clerk][batch] -> [clerk] (batched.rs:83-85); point 1 carries value 0.  Clamped,
 // branch-free indices, so every load can be issued before the first wait; each share is turned into

@@ -125,6 +125,10 @@ CHECK_PATH_REGISTERS = 1
 CHECK_PATH_LOOPED = 2
 ShareCheck = collections.namedtuple("ShareCheck", "redundancy bad_batches first_bad blame")
 CheckLaunch = collections.namedtuple("CheckLaunch", "path bucket located overflowed")
+# Checked reveal (sda_packed_reveal_checked_dev): sda_packed_reveal_checked_last_launch's path codes and record
+REPAIR_PATH_FUSED = 1
+REPAIR_PATH_COMPOSED = 2
+RepairLaunch = collections.namedtuple("RepairLaunch", "path bucket fixed overflowed")
 
 # Elements one workgroup of the draws kernel produces (csrc/kernels.h kDrawsTile): the sizes at which
 # sda_draws_dev's grid gains a workgroup
@@ -206,6 +210,13 @@ SIGNATURES = [
     ("sda_secret_check", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.POINTER(_i64p), _u64p,
                                C.c_uint64, _vp, _u64p, _u64p, _u64p, _u64p]),
     ("sda_packed_check_last_launch", _st, [_vp, _u32p, _u32p, _u64p, _u32p]),
+    ("sda_packed_reveal_checked_dev", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.c_uint64,
+                                            C.c_uint64, _vp, _vp, _vp, _u64p, _u64p, _u64p, _u64p, _vp]),
+    ("sda_packed_reveal_checked32_dev", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.c_uint64,
+                                              C.c_uint64, _vp, _vp, _vp, _u64p, _u64p, _u64p, _u64p, _vp]),
+    ("sda_secret_reconstruct_checked", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.POINTER(_i64p),
+                                             _u64p, C.c_uint64, _vp, _u64p, _u64p, _u64p, _u64p, _i64p]),
+    ("sda_packed_reveal_checked_last_launch", _st, [_vp, _u32p, _u32p, _u64p, _u32p]),
     ("sda_additive_generate_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp]),
     ("sda_chacha_mask_combine_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
     ("sda_draws_dev", _st, [_vp, _u32p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp]),
@@ -910,6 +921,57 @@ class Engine:
         _check(self.lib.sda_packed_check_last_launch(self.h, C.byref(path), C.byref(bucket), C.byref(located),
                                                      C.byref(over)))
         return CheckLaunch(int(path.value), int(bucket.value), int(located.value), int(over.value))
+
+    # checked reveal (include/sda_engine.h "checked reveal"): the check's arguments plus out
+    def _packed_reveal_checked(self, fn, scheme, dimension, indices, n_vectors, shares_ptr, out_ptr, verdict_ptr,
+                               stream):
+        s = scheme.c()
+        idx = _arr(indices, np.uint64)
+        r, bad, first = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        blame = np.zeros(max(idx.size, 1), np.uint64)
+        _check(fn(self.h, C.byref(s), dimension, _ptr(idx, _u64p), idx.size, n_vectors, shares_ptr, out_ptr,
+                  verdict_ptr, C.byref(r), C.byref(bad), C.byref(first), _ptr(blame, _u64p), stream))
+        return ShareCheck(int(r.value), int(bad.value), int(first.value), [int(x) for x in blame[: idx.size]])
+
+    def packed_reveal_checked_dev(self, scheme, dimension, indices, n_vectors, shares_ptr, out_ptr,
+                                  verdict_ptr=None, stream=None):
+        """The canonical reveal of i64 shares [n_vectors][n_idx][B] into out_ptr (device i64 [n_vectors][dimension])
+        with the share check in the same pass and a located wrong share corrected; returns the check's ShareCheck
+        (sda_packed_reveal_checked_dev).  Waits for its stream."""
+        return self._packed_reveal_checked(self.lib.sda_packed_reveal_checked_dev, scheme, dimension, indices,
+                                           n_vectors, shares_ptr, out_ptr, verdict_ptr, stream)
+
+    def packed_reveal_checked32_dev(self, scheme, dimension, indices, n_vectors, shares_ptr, out_ptr,
+                                    verdict_ptr=None, stream=None):
+        """packed_reveal_checked_dev over int32 shares (sda_packed_reveal_checked32_dev)."""
+        return self._packed_reveal_checked(self.lib.sda_packed_reveal_checked32_dev, scheme, dimension, indices,
+                                           n_vectors, shares_ptr, out_ptr, verdict_ptr, stream)
+
+    def secret_reconstruct_checked(self, scheme, dimension: int, indexed_shares, want_verdict=True):
+        """The checked reveal of host share rows, as secret_check takes them (sda_secret_reconstruct_checked):
+        (secrets, ShareCheck, verdict) with verdict a uint16 array of one entry per batch, or None."""
+        s = scheme.c()
+        idx = _arr([i for i, _ in indexed_shares], np.uint64)
+        arrs, ptrs, lens, n = _rows([r for _, r in indexed_shares])
+        k = max(int(getattr(scheme, "secret_count", 1) or 1), 1)
+        nb = (dimension + k - 1) // k
+        verdict = np.full(max(nb, 1), 0xAAAA, np.uint16) if want_verdict else None
+        out = np.zeros(max(dimension, 1), np.int64)
+        r, bad, first = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        blame = np.zeros(max(n, 1), np.uint64)
+        _check(self.lib.sda_secret_reconstruct_checked(self.h, C.byref(s), dimension, _ptr(idx, _u64p), ptrs, lens, n,
+                                                       verdict.ctypes.data if want_verdict else None, C.byref(r),
+                                                       C.byref(bad), C.byref(first), _ptr(blame, _u64p), _ptr(out)))
+        res = ShareCheck(int(r.value), int(bad.value), int(first.value), [int(x) for x in blame[:n]])
+        return out[:dimension], res, verdict[:nb] if want_verdict else None
+
+    def packed_reveal_checked_last_launch(self):
+        """RepairLaunch(path, bucket, fixed, overflowed) of the handle's last checked reveal that launched something
+        (sda_packed_reveal_checked_last_launch): all zeros before the first."""
+        path, bucket, fixed, over = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint32()
+        _check(self.lib.sda_packed_reveal_checked_last_launch(self.h, C.byref(path), C.byref(bucket), C.byref(fixed),
+                                                              C.byref(over)))
+        return RepairLaunch(int(path.value), int(bucket.value), int(fixed.value), int(over.value))
 
     def packed_generate_keyed_dev(self, scheme, secrets_ptr, dimension, n_vectors, key, stream_id, out_ptr, mode,
                                   first_batch=0, stream=None):
