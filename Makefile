@@ -18,7 +18,7 @@ HOST    := engine engine_dev engine_check hbm engine_codec engine_recipient engi
 OBJS    := $(patsubst %,$(OBJDIR)/%.o,$(PLAIN)) $(patsubst %,$(OBJDIR)/%.o,$(HOST)) \
            $(OBJDIR)/packed_gen.o $(patsubst %,$(OBJDIR)/packed_gen_%.o,$(GEN_PARTS)) \
            $(OBJDIR)/packed_reveal.o $(patsubst %,$(OBJDIR)/packed_reveal_%.o,$(REVEAL_PARTS))
-HDRS    := $(CSRC)/packed_common.h $(CSRC)/kernels.h $(CSRC)/reveal_plan.h $(CSRC)/check_plan.h $(CSRC)/repair_plan.h $(CSRC)/check_common.h $(CSRC)/modarith.h $(CSRC)/xcd.h $(CSRC)/draws_common.h $(CSRC)/codec_common.h include/sda_engine.h
+HDRS    := $(CSRC)/packed_common.h $(CSRC)/kernels.h $(CSRC)/reveal_plan.h $(CSRC)/check_plan.h $(CSRC)/repair_plan.h $(CSRC)/check_common.h $(CSRC)/check_launch.h $(CSRC)/modarith.h $(CSRC)/xcd.h $(CSRC)/draws_common.h $(CSRC)/codec_common.h include/sda_engine.h
 
 all: $(LIB) oracle
 

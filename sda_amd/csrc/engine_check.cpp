@@ -1,8 +1,9 @@
 // engine_check.cpp -- the packed-Shamir share consistency check's entry points (include/sda_engine.h):
 // sda_packed_check_dev / sda_packed_check32_dev on device shares, sda_secret_check on host rows, and their record --
 // and the checked reveal's on the same arguments plus `out`: sda_packed_reveal_checked_dev / 32, the host form
-// sda_secret_reconstruct_checked and its record.  Argument checks follow the reveal entry points on the same
-// arguments; the arithmetic is packed_check.hip's and packed_repair.hip's.
+// sda_secret_reconstruct_checked and its record.  The two families share one argument front (validate), one host
+// form (host_form) and one device table (sda::ensure_check_table); run_check and run_reveal_checked are the two
+// algorithms, and the arithmetic is packed_check.hip's and packed_repair.hip's.
 #include "engine_internal.h"
 
 using namespace sda_host;
@@ -13,12 +14,22 @@ namespace {
 struct CheckOutputs {
     uint64_t *redundancy, *bad_batches, *first_bad, *blame;
     uint64_t n_idx;
-    void zero(uint64_t r) const {
+    bool complete() const { return redundancy && bad_batches && first_bad && (!n_idx || blame); }
+    void commit(uint64_t r, const sda::PackedCheckResult& res, const uint64_t* bl) const {
         *redundancy = r;
-        *bad_batches = 0;
-        *first_bad = UINT64_MAX;
-        for (uint64_t j = 0; j < n_idx; ++j) blame[j] = 0;
+        *bad_batches = res.bad;
+        *first_bad = res.first_bad;
+        for (uint64_t j = 0; j < n_idx; ++j) blame[j] = bl ? bl[j] : 0;
     }
+    void zero(uint64_t r) const { commit(r, sda::PackedCheckResult{}, nullptr); }
+};
+
+// the counts of a run before they reach the caller: what follows the run may still fail
+struct Counts {
+    uint64_t redundancy = 0;
+    sda::PackedCheckResult res;
+    std::vector<uint64_t> blame;
+    explicit Counts(uint64_t n_idx) : blame(n_idx, 0) {}
 };
 
 uint32_t check_log_cap() {                                 // SDA_CHECK_LOG_CAP, read per call
@@ -28,93 +39,56 @@ uint32_t check_log_cap() {                                 // SDA_CHECK_LOG_CAP,
     return v < sda::kCheckLogCap ? (uint32_t)v : sda::kCheckLogCap;
 }
 
-// SDA_OK with zero counts and nothing launched; a given device verdict buffer of `words` entries is zero-filled
-sda_status nothing_to_check(const CheckOutputs& o, uint64_t r, uint16_t* verdict, uint64_t words, hipStream_t st) {
+// nothing to check and nothing launched: a given device verdict buffer of `words` entries is zero-filled
+sda_status zero_verdict(uint16_t* verdict, uint64_t words, hipStream_t st) {
     if (verdict && words) {
         HIP_TRY(hipMemsetAsync(verdict, 0, words * sizeof(uint16_t), st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    o.zero(r);
     return SDA_OK;
 }
 
-// The check of a validated call (PackedShamir, n_idx >= k + t, at most 1023 shares and 65535 vectors) on stream st.
-sda_status run_check(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedCheckArgs& ca, const uint64_t* indices,
-                     uint64_t n_idx, const CheckOutputs& o, hipStream_t st) {
-    if (sda_status e = ensure(&h->chk_buf, &h->chk_buf_bytes, sda::packed_check_buf_bytes())) return e;
-    const uint64_t k = s->secret_count, B = (ca.dimension + k - 1) / k;
-    std::vector<uint64_t> blame(n_idx, 0);
-    sda::PackedCheckResult res{};
-    const hipError_t e = sda::launch_packed_check(ca, indices, (uint32_t)n_idx, (uint32_t)k,
-                                                  (uint32_t)s->privacy_threshold, (uint32_t)s->modulus,
-                                                  (uint32_t)s->omega_secrets, (uint32_t)s->omega_shares, h->chk_tab,
-                                                  h->chk_buf, check_log_cap(), st, blame.data(), &res);
-    if (e == hipErrorInvalidValue) return fail(SDA_ERR_UNSUPPORTED, "the share check needs distinct clerk indices");
-    HIP_TRY(e);
-    if (!res.launched) return nothing_to_check(o, res.plan.redundancy, ca.verdict, ca.n_vectors * B, st);
-    *o.redundancy = res.plan.redundancy;
-    *o.bad_batches = res.bad;
-    *o.first_bad = res.first_bad;
-    for (uint64_t j = 0; j < n_idx; ++j) o.blame[j] = blame[j];
-    h->last.check.path = res.plan.path;
-    h->last.check.bucket = res.plan.bucket;
-    h->last.check.located = res.located;
-    h->last.check.overflowed = res.overflowed ? 1 : 0;
-    return SDA_OK;
-}
-
-// Both device entry points, T the share type: sda_packed_reconstruct_dev's checks in its order.
-template <typename T>
-sda_status packed_check(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension, const uint64_t* indices,
-                        uint64_t n_idx, uint64_t n_vectors, const T* shares, uint16_t* verdict, const CheckOutputs& o,
-                        void* stream) {
-    if (!h || !s) return fail(SDA_ERR_INVALID_ARGUMENT, "need a PackedShamir scheme");
-    if (!o.redundancy || !o.bad_batches || !o.first_bad || (n_idx && !o.blame))
-        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (s->kind == SDA_SHARING_ADDITIVE) {                  // every share is needed: no redundancy to check
-        if (n_vectors > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 vectors per launch");
-        HIP_TRY(hipSetDevice(h->device));
-        if (sda_status e = nothing_to_check(o, 0, verdict, n_vectors * dimension, pick(h, stream))) return e;
-        return ok();
-    }
-    if (s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "need a PackedShamir scheme");
-    if (sda_status st = check_packed(s)) return st;
-    const uint64_t kt = s->privacy_threshold + s->secret_count;
-    if (dimension == 0) {                                   // batched.rs:77-81: no batch, no check
-        o.zero(n_idx > kt ? n_idx - kt : 0);
-        return ok();
-    }
-    if (n_idx < kt) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");
-    if (n_idx > sda::kRevealMaxShares)
-        return fail(SDA_ERR_UNSUPPORTED, "more than %u clerk shares per batch", sda::kRevealMaxShares);
-    if (n_vectors > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 vectors per launch");
-    if (n_vectors && (!shares || !indices)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (n_vectors == 0) {
-        o.zero(n_idx - kt);
-        return ok();
-    }
-    sda::PackedCheckArgs ca{nullptr, nullptr, dimension, n_vectors, verdict};
-    if constexpr (sizeof(T) == 4) ca.shares32 = shares; else ca.shares = shares;
-    if (sda_status e = run_check(h, s, ca, indices, n_idx, o, pick(h, stream))) return e;
-    return ok();
-}
-
-// The checked reveal of a validated call (PackedShamir, n_idx >= k + t, at most 1023 shares and 65535 vectors, at
-// least one batch and one vector) on stream st, as packed_repair_plan decides it.
-sda_status run_reveal_checked(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedRepairArgs& ra,
-                              const uint64_t* indices, uint64_t n_idx, const CheckOutputs& o, hipStream_t st) {
+// What both algorithms start from: the counter block, the (scheme, clerk set)'s table -- repeated clerk points are
+// refused with the family's own message `repeated` -- and the geometry of the call's launches.
+sda_status prepare(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedCheckArgs& a, const uint64_t* indices,
+                   uint64_t n_idx, const char* repeated, sda::CheckGeom* g) {
     if (sda_status e = ensure(&h->chk_buf, &h->chk_buf_bytes, sda::packed_check_buf_bytes())) return e;
     const uint32_t k = (uint32_t)s->secret_count, t = (uint32_t)s->privacy_threshold, p = (uint32_t)s->modulus;
-    const uint32_t ws = (uint32_t)s->omega_secrets, wn = (uint32_t)s->omega_shares, n = (uint32_t)n_idx;
-    const uint64_t words = ra.n_vectors * ((ra.dimension + k - 1) / k);
-    const sda::PackedRepairPlan pl = sda::packed_repair_plan(n, k, t);
-    const hipError_t te = sda::ensure_repair_table(h->rep_tab, indices, n, k, t, p, ws, wn);
-    if (te == hipErrorInvalidValue) return fail(SDA_ERR_UNSUPPORTED, "the checked reveal needs distinct clerk indices");
+    const hipError_t te = sda::ensure_check_table(h->chk_tab, indices, (uint32_t)n_idx, k, t, p,
+                                                  (uint32_t)s->omega_secrets, (uint32_t)s->omega_shares);
+    if (te == hipErrorInvalidValue) return fail(SDA_ERR_UNSUPPORTED, "%s", repeated);
     HIP_TRY(te);
-    const uint32_t cap = check_log_cap();
-    std::vector<uint64_t> blame(n_idx, 0);
-    sda::PackedRepairResult res{0, UINT64_MAX, 0, false};
+    *g = sda::check_geom(a, (uint32_t)n_idx, k, t, p, h->chk_tab, h->chk_buf, check_log_cap());
+    return SDA_OK;
+}
+
+// The check of a validated call (PackedShamir, n_idx >= k + t, at most 1023 shares and 65535 vectors, at least one
+// batch and one vector) on stream st.
+sda_status run_check(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedCheckArgs& ca, const uint64_t* indices,
+                     uint64_t n_idx, Counts* c, hipStream_t st) {
+    sda::CheckGeom g;
+    if (sda_status e = prepare(h, s, ca, indices, n_idx, "the share check needs distinct clerk indices", &g)) return e;
+    const sda::PackedCheckPlan pl = sda::packed_check_plan(g.n_idx, g.k, g.kt - g.k);
+    c->redundancy = pl.redundancy;
+    HIP_TRY(sda::launch_packed_check(ca, g, st, c->blame.data(), &c->res));
+    if (!c->res.launched) return zero_verdict(ca.verdict, ca.n_vectors * g.B, st);
+    h->last.check.path = pl.path;
+    h->last.check.bucket = pl.bucket;
+    h->last.check.located = c->res.located;
+    h->last.check.overflowed = c->res.overflowed ? 1 : 0;
+    return SDA_OK;
+}
+
+// The checked reveal of a call validated as run_check's, on stream st, as packed_repair_plan decides it.
+sda_status run_reveal_checked(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedRepairArgs& ra,
+                              const uint64_t* indices, uint64_t n_idx, Counts* c, hipStream_t st) {
+    sda::CheckGeom g;
+    if (sda_status e = prepare(h, s, ra, indices, n_idx, "the checked reveal needs distinct clerk indices", &g)) return e;
+    const uint64_t words = ra.n_vectors * g.B;
+    const sda::PackedRepairPlan pl = sda::packed_repair_plan(g.n_idx, g.k, g.kt - g.k);
+    sda::PackedCheckResult& res = c->res;
+    uint64_t* blame = c->blame.data();
+    c->redundancy = pl.redundancy;
     // the verdict words the fix-up reads when the caller keeps none: zeros, then the located positions
     uint16_t* ver = ra.verdict;
     auto own_verdict = [&]() -> sda_status {
@@ -125,21 +99,17 @@ sda_status run_reveal_checked(sda_engine* h, const sda_sharing_scheme* s, const 
         return SDA_OK;
     };
     if (pl.path == sda::kRepairFused) {
-        HIP_TRY(sda::launch_packed_repair(ra, n, k, t, p, h->rep_tab, h->chk_buf, cap, st, &res));
+        HIP_TRY(sda::launch_packed_repair(ra, g, st, &res));
         if (res.bad && pl.locate) {
             if (sda_status e = own_verdict()) return e;
-            HIP_TRY(sda::launch_packed_repair_fix(ra, ver, n, k, t, p, h->rep_tab, h->chk_buf, cap, true, false, st,
-                                                  blame.data(), &res));
+            HIP_TRY(sda::launch_packed_repair_fix(ra, ver, g, true, false, st, blame, &res));
         }
     } else {
         if (pl.redundancy) {                                // the share check locates in the same call: ahead of it
             if (sda_status e = own_verdict()) return e;
-            const sda::PackedCheckArgs ca{ra.shares, ra.shares32, ra.dimension, ra.n_vectors, ver};
-            sda::PackedCheckResult cr{};
-            HIP_TRY(sda::launch_packed_check(ca, indices, n, k, t, p, ws, wn, h->chk_tab, h->chk_buf, cap, st,
-                                             blame.data(), &cr));
-            res.bad = cr.bad;
-            res.first_bad = cr.first_bad;
+            sda::PackedCheckArgs ca = ra;
+            ca.verdict = ver;
+            HIP_TRY(sda::launch_packed_check(ca, g, st, blame, &res));
         } else if (ra.verdict) {
             HIP_TRY(hipMemsetAsync(ra.verdict, 0, words * sizeof(uint16_t), st));
         }
@@ -147,15 +117,10 @@ sda_status run_reveal_checked(sda_engine* h, const sda_sharing_scheme* s, const 
         rv.shares32 = ra.shares32;
         if (sda_status e = packed_reveal(h, s, rv, indices, n_idx, SDA_REVEAL_CANONICAL, st)) return e;
         if (res.bad)
-            HIP_TRY(sda::launch_packed_repair_fix(ra, ver, n, k, t, p, h->rep_tab, h->chk_buf, cap, false, true, st,
-                                                  blame.data(), &res));
+            HIP_TRY(sda::launch_packed_repair_fix(ra, ver, g, false, true, st, blame, &res));
         else
             HIP_TRY(hipStreamSynchronize(st));
     }
-    *o.redundancy = pl.redundancy;
-    *o.bad_batches = res.bad;
-    *o.first_bad = res.first_bad;
-    for (uint64_t j = 0; j < n_idx; ++j) o.blame[j] = blame[j];
     h->last.repair.path = pl.path;
     h->last.repair.bucket = pl.bucket;
     h->last.repair.fixed = res.fixed;
@@ -163,16 +128,24 @@ sda_status run_reveal_checked(sda_engine* h, const sda_sharing_scheme* s, const 
     return SDA_OK;
 }
 
-// Both device entry points of the checked reveal, T the share type: packed_check's checks in its order, `out` where
-// the reveal checks it; an Additive scheme has nothing to correct and no packed reveal.
-template <typename T>
-sda_status packed_reveal_checked(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
-                                 const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors, const T* shares,
-                                 uint16_t* verdict, int64_t* out, const CheckOutputs& o, void* stream) {
+// The argument ladder of the four device entry points: sda_packed_reconstruct_dev's checks in its order.
+// additive_clean: an Additive scheme needs every share, so it has no redundancy to check and the call is done with
+// zero counts (the share check); otherwise it is refused (no packed reveal to correct).  need_out: `out` is checked
+// where the reveal checks it.  *run: the call goes on to its algorithm; else the status returned is the call's.
+sda_status validate(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension, const uint64_t* indices,
+                    uint64_t n_idx, uint64_t n_vectors, const void* shares, uint16_t* verdict, bool additive_clean,
+                    bool need_out, const int64_t* out, const CheckOutputs& o, void* stream, bool* run) {
+    *run = false;
     if (!h || !s) return fail(SDA_ERR_INVALID_ARGUMENT, "need a PackedShamir scheme");
-    if (!o.redundancy || !o.bad_batches || !o.first_bad || (n_idx && !o.blame))
-        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (s->kind == SDA_SHARING_ADDITIVE) return fail(SDA_ERR_UNSUPPORTED, "an Additive scheme has no checked reveal");
+    if (!o.complete()) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (s->kind == SDA_SHARING_ADDITIVE) {
+        if (!additive_clean) return fail(SDA_ERR_UNSUPPORTED, "an Additive scheme has no checked reveal");
+        if (n_vectors > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 vectors per launch");
+        HIP_TRY(hipSetDevice(h->device));
+        if (sda_status e = zero_verdict(verdict, n_vectors * dimension, pick(h, stream))) return e;
+        o.zero(0);
+        return ok();
+    }
     if (s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "need a PackedShamir scheme");
     if (sda_status st = check_packed(s)) return st;
     const uint64_t kt = s->privacy_threshold + s->secret_count;
@@ -184,15 +157,32 @@ sda_status packed_reveal_checked(sda_engine* h, const sda_sharing_scheme* s, uin
     if (n_idx > sda::kRevealMaxShares)
         return fail(SDA_ERR_UNSUPPORTED, "more than %u clerk shares per batch", sda::kRevealMaxShares);
     if (n_vectors > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 vectors per launch");
-    if (n_vectors && (!out || !shares || !indices)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_vectors && ((need_out && !out) || !shares || !indices)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     HIP_TRY(hipSetDevice(h->device));
     if (n_vectors == 0) {
         o.zero(n_idx - kt);
         return ok();
     }
-    sda::PackedRepairArgs ra{nullptr, nullptr, dimension, n_vectors, verdict, out};
+    *run = true;
+    return SDA_OK;
+}
+
+// The four device entry points, T the share type; out == nullptr: the share check, else the checked reveal.
+template <typename T>
+sda_status device_form(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension, const uint64_t* indices,
+                       uint64_t n_idx, uint64_t n_vectors, const T* shares, void* verdict, bool reveal, int64_t* out,
+                       const CheckOutputs& o, void* stream) {
+    bool run;
+    const sda_status vs = validate(h, s, dimension, indices, n_idx, n_vectors, shares, static_cast<uint16_t*>(verdict),
+                                   !reveal, reveal, out, o, stream, &run);
+    if (!run) return vs;
+    sda::PackedRepairArgs ra{{nullptr, nullptr, dimension, n_vectors, static_cast<uint16_t*>(verdict)}, out};
     if constexpr (sizeof(T) == 4) ra.shares32 = shares; else ra.shares = shares;
-    if (sda_status e = run_reveal_checked(h, s, ra, indices, n_idx, o, pick(h, stream))) return e;
+    Counts c(n_idx);
+    if (sda_status e = reveal ? run_reveal_checked(h, s, ra, indices, n_idx, &c, pick(h, stream))
+                              : run_check(h, s, ra, indices, n_idx, &c, pick(h, stream)))
+        return e;
+    o.commit(c.redundancy, c.res, c.blame.data());
     return ok();
 }
 
@@ -216,6 +206,54 @@ sda_status check_host_rows(const sda_sharing_scheme* s, uint64_t B, const uint64
     return SDA_OK;
 }
 
+// Both host forms from where the scheme is no Additive one: sda_secret_reconstruct's checks in its order, the rows
+// staged (batched.rs:83-85: clerk i's batches) with B verdict words and `extra` more bytes behind them, then
+// run(rows, verdict words, extra bytes, &counts) on the engine's own stream.  The verdict words come back when the
+// caller keeps them or, with `verdict_always`, in any case; the extra bytes go to extra_out.  Everything reaches the
+// caller's memory only once the call has succeeded, and a failing read-back puts `rec`, the family's launch record,
+// back as it was before the run.
+template <typename Rec, typename Run>
+sda_status host_form(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension, const uint64_t* indices,
+                     const int64_t* const* rows, const uint64_t* lens, uint64_t n_rows, void* verdict,
+                     bool verdict_always, void* extra_out, size_t extra, Rec& rec, const CheckOutputs& o, Run run) {
+    if (s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown sharing scheme kind");
+    if (sda_status st = check_packed(s)) return st;
+    HIP_TRY(hipSetDevice(h->device));
+    const uint64_t k = s->secret_count, kt = s->privacy_threshold + k;
+    const uint64_t B = (dimension + k - 1) / k;             // batched.rs:77
+    if (B == 0) {                                           // no batch => no error checks run
+        o.zero(n_rows > kt ? n_rows - kt : 0);
+        return ok();
+    }
+    if (sda_status st = check_host_rows(s, B, indices, rows, lens, n_rows)) return st;
+    (void)pick(h, h->stream);                               // host entry points run on the engine's own stream
+    DevArena a;
+    if (sda_status e = stage(h, rup(n_rows * B * 8) + rup(B * 2) + rup(extra), &a)) return e;
+    int64_t* din = a.take<int64_t>(n_rows * B);
+    uint16_t* dver = a.take<uint16_t>(B);
+    char* dextra = a.take<char>(extra);
+    for (uint64_t i = 0; i < n_rows; ++i)
+        HIP_TRY(hipMemcpyAsync(din + i * B, rows[i], B * 8, hipMemcpyHostToDevice, h->stream));
+    Counts c(n_rows);
+    const Rec before = rec;
+    const bool keep_verdict = verdict || verdict_always;
+    if (sda_status e = run(din, keep_verdict ? dver : nullptr, dextra, &c)) return e;
+    if (keep_verdict || extra) {
+        std::vector<uint16_t> hv(B);
+        std::vector<char> hx(extra);
+        hipError_t ce = hipSuccess;
+        if (keep_verdict) ce = hipMemcpyAsync(hv.data(), dver, B * 2, hipMemcpyDeviceToHost, h->stream);
+        if (ce == hipSuccess && extra) ce = hipMemcpyAsync(hx.data(), dextra, extra, hipMemcpyDeviceToHost, h->stream);
+        if (ce == hipSuccess) ce = hipStreamSynchronize(h->stream);
+        if (ce != hipSuccess) rec = before;
+        HIP_TRY(ce);
+        if (verdict) memcpy(verdict, hv.data(), B * 2);
+        if (extra) memcpy(extra_out, hx.data(), extra);
+    }
+    o.commit(c.redundancy, c.res, c.blame.data());
+    return ok();
+}
+
 }  // namespace
 
 extern "C" {
@@ -225,8 +263,8 @@ sda_status sda_packed_check_dev(sda_engine* h, const sda_sharing_scheme* s, uint
                                 void* verdict, uint64_t* redundancy, uint64_t* bad_batches, uint64_t* first_bad,
                                 uint64_t* blame, void* stream) {
     SDA_ENTRY;
-    return packed_check(h, s, dimension, indices, n_idx, n_vectors, shares, static_cast<uint16_t*>(verdict),
-                        CheckOutputs{redundancy, bad_batches, first_bad, blame, n_idx}, stream);
+    return device_form(h, s, dimension, indices, n_idx, n_vectors, shares, verdict, false, nullptr,
+                       CheckOutputs{redundancy, bad_batches, first_bad, blame, n_idx}, stream);
 }
 
 sda_status sda_packed_check32_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
@@ -234,18 +272,17 @@ sda_status sda_packed_check32_dev(sda_engine* h, const sda_sharing_scheme* s, ui
                                   void* verdict, uint64_t* redundancy, uint64_t* bad_batches, uint64_t* first_bad,
                                   uint64_t* blame, void* stream) {
     SDA_ENTRY;
-    return packed_check(h, s, dimension, indices, n_idx, n_vectors, shares, static_cast<uint16_t*>(verdict),
-                        CheckOutputs{redundancy, bad_batches, first_bad, blame, n_idx}, stream);
+    return device_form(h, s, dimension, indices, n_idx, n_vectors, shares, verdict, false, nullptr,
+                       CheckOutputs{redundancy, bad_batches, first_bad, blame, n_idx}, stream);
 }
 
-// sda_secret_reconstruct's checks in its order (no output buffer here), then the device form on the staged rows
+// An Additive scheme's rows are checked as sda_secret_reconstruct checks them; the rest is host_form's
 sda_status sda_secret_check(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension, const uint64_t* indices,
                             const int64_t* const* rows, const uint64_t* lens, uint64_t n_rows, void* verdict,
                             uint64_t* redundancy, uint64_t* bad_batches, uint64_t* first_bad, uint64_t* blame) {
     SDA_ENTRY;
-    if (!h || !s || !redundancy || !bad_batches || !first_bad || (n_rows && !blame))
-        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     const CheckOutputs o{redundancy, bad_batches, first_bad, blame, n_rows};
+    if (!h || !s || !o.complete()) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     if (s->kind == SDA_SHARING_ADDITIVE) {
         // additive.rs:56-72 through combine_rows' checks: the dimension is row 0's length
         if (n_rows && (!rows || !lens)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -261,43 +298,11 @@ sda_status sda_secret_check(sda_engine* h, const sda_sharing_scheme* s, uint64_t
         o.zero(0);
         return ok();
     }
-    if (s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown sharing scheme kind");
-    if (sda_status st = check_packed(s)) return st;
-    HIP_TRY(hipSetDevice(h->device));
-    const uint64_t k = s->secret_count, kt = s->privacy_threshold + k;
-    const uint64_t B = (dimension + k - 1) / k;             // batched.rs:77
-    if (B == 0) {                                           // no batch => no error checks run
-        o.zero(n_rows > kt ? n_rows - kt : 0);
-        return ok();
-    }
-    if (sda_status st = check_host_rows(s, B, indices, rows, lens, n_rows)) return st;
-    (void)pick(h, h->stream);                               // host entry points run on the engine's own stream
-    DevArena a;
-    if (sda_status e = stage(h, rup(n_rows * B * 8) + rup(B * 2), &a)) return e;
-    int64_t* din = a.take<int64_t>(n_rows * B);
-    uint16_t* dver = a.take<uint16_t>(B);
-    for (uint64_t i = 0; i < n_rows; ++i)                   // batched.rs:83-85: clerk i's batches
-        HIP_TRY(hipMemcpyAsync(din + i * B, rows[i], B * 8, hipMemcpyHostToDevice, h->stream));
-    // the counts go to locals first: the verdict copy below may still fail
-    uint64_t r = 0, bad = 0, first = UINT64_MAX;
-    std::vector<uint64_t> bl(n_rows, 0);
-    const CheckOutputs tmp{&r, &bad, &first, bl.data(), n_rows};
-    const sda_engine::CheckLaunchInfo before = h->last.check;
-    sda::PackedCheckArgs ca{din, nullptr, dimension, 1, verdict ? dver : nullptr};
-    if (sda_status e = run_check(h, s, ca, indices, n_rows, tmp, h->stream)) return e;
-    if (verdict) {
-        std::vector<uint16_t> hv(B);
-        hipError_t ce = hipMemcpyAsync(hv.data(), dver, B * 2, hipMemcpyDeviceToHost, h->stream);
-        if (ce == hipSuccess) ce = hipStreamSynchronize(h->stream);
-        if (ce != hipSuccess) h->last.check = before;
-        HIP_TRY(ce);
-        memcpy(verdict, hv.data(), B * 2);
-    }
-    *redundancy = r;
-    *bad_batches = bad;
-    *first_bad = first;
-    for (uint64_t j = 0; j < n_rows; ++j) blame[j] = bl[j];
-    return ok();
+    return host_form(h, s, dimension, indices, rows, lens, n_rows, verdict, false, nullptr, 0, h->last.check, o,
+                     [&](const int64_t* din, uint16_t* dver, char*, Counts* c) {
+                         const sda::PackedCheckArgs ca{din, nullptr, dimension, 1, dver};
+                         return run_check(h, s, ca, indices, n_rows, c, h->stream);
+                     });
 }
 
 sda_status sda_packed_reveal_checked_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
@@ -305,8 +310,8 @@ sda_status sda_packed_reveal_checked_dev(sda_engine* h, const sda_sharing_scheme
                                          const int64_t* shares, int64_t* out, void* verdict, uint64_t* redundancy,
                                          uint64_t* bad_batches, uint64_t* first_bad, uint64_t* blame, void* stream) {
     SDA_ENTRY;
-    return packed_reveal_checked(h, s, dimension, indices, n_idx, n_vectors, shares, static_cast<uint16_t*>(verdict),
-                                 out, CheckOutputs{redundancy, bad_batches, first_bad, blame, n_idx}, stream);
+    return device_form(h, s, dimension, indices, n_idx, n_vectors, shares, verdict, true, out,
+                       CheckOutputs{redundancy, bad_batches, first_bad, blame, n_idx}, stream);
 }
 
 sda_status sda_packed_reveal_checked32_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
@@ -315,59 +320,25 @@ sda_status sda_packed_reveal_checked32_dev(sda_engine* h, const sda_sharing_sche
                                            uint64_t* bad_batches, uint64_t* first_bad, uint64_t* blame,
                                            void* stream) {
     SDA_ENTRY;
-    return packed_reveal_checked(h, s, dimension, indices, n_idx, n_vectors, shares, static_cast<uint16_t*>(verdict),
-                                 out, CheckOutputs{redundancy, bad_batches, first_bad, blame, n_idx}, stream);
+    return device_form(h, s, dimension, indices, n_idx, n_vectors, shares, verdict, true, out,
+                       CheckOutputs{redundancy, bad_batches, first_bad, blame, n_idx}, stream);
 }
 
-// sda_secret_check's checks in its order (out where sda_secret_reconstruct has its own), then the device form on the
-// staged rows; everything reaches the caller's memory only once the call has succeeded
+// `out` is checked where sda_secret_reconstruct has its own check; an Additive scheme has no packed reveal to correct
 sda_status sda_secret_reconstruct_checked(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
                                           const uint64_t* indices, const int64_t* const* rows, const uint64_t* lens,
                                           uint64_t n_rows, void* verdict, uint64_t* redundancy, uint64_t* bad_batches,
                                           uint64_t* first_bad, uint64_t* blame, int64_t* out) {
     SDA_ENTRY;
-    if (!h || !s || !redundancy || !bad_batches || !first_bad || (n_rows && !blame) || (dimension && !out))
-        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     const CheckOutputs o{redundancy, bad_batches, first_bad, blame, n_rows};
+    if (!h || !s || !o.complete() || (dimension && !out)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     if (s->kind == SDA_SHARING_ADDITIVE) return fail(SDA_ERR_UNSUPPORTED, "an Additive scheme has no checked reveal");
-    if (s->kind != SDA_SHARING_PACKED_SHAMIR) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown sharing scheme kind");
-    if (sda_status st = check_packed(s)) return st;
-    HIP_TRY(hipSetDevice(h->device));
-    const uint64_t k = s->secret_count, kt = s->privacy_threshold + k;
-    const uint64_t B = (dimension + k - 1) / k;             // batched.rs:77
-    if (B == 0) {                                           // no batch => no error checks run
-        o.zero(n_rows > kt ? n_rows - kt : 0);
-        return ok();
-    }
-    if (sda_status st = check_host_rows(s, B, indices, rows, lens, n_rows)) return st;
-    (void)pick(h, h->stream);                               // host entry points run on the engine's own stream
-    DevArena a;
-    if (sda_status e = stage(h, rup(n_rows * B * 8) + rup(B * 2) + rup(dimension * 8), &a)) return e;
-    int64_t* din = a.take<int64_t>(n_rows * B);
-    uint16_t* dver = a.take<uint16_t>(B);
-    int64_t* dout = a.take<int64_t>(dimension);
-    for (uint64_t i = 0; i < n_rows; ++i)                   // batched.rs:83-85: clerk i's batches
-        HIP_TRY(hipMemcpyAsync(din + i * B, rows[i], B * 8, hipMemcpyHostToDevice, h->stream));
-    uint64_t r = 0, bad = 0, first = UINT64_MAX;
-    std::vector<uint64_t> bl(n_rows, 0);
-    const CheckOutputs tmp{&r, &bad, &first, bl.data(), n_rows};
-    const sda_engine::RepairLaunchInfo before = h->last.repair;
-    const sda::PackedRepairArgs ra{din, nullptr, dimension, 1, dver, dout};
-    if (sda_status e = run_reveal_checked(h, s, ra, indices, n_rows, tmp, h->stream)) return e;
-    std::vector<uint16_t> hv(B);
-    std::vector<int64_t> ho(dimension);
-    hipError_t ce = hipMemcpyAsync(hv.data(), dver, B * 2, hipMemcpyDeviceToHost, h->stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(ho.data(), dout, dimension * 8, hipMemcpyDeviceToHost, h->stream);
-    if (ce == hipSuccess) ce = hipStreamSynchronize(h->stream);
-    if (ce != hipSuccess) h->last.repair = before;
-    HIP_TRY(ce);
-    if (verdict) memcpy(verdict, hv.data(), B * 2);
-    memcpy(out, ho.data(), dimension * 8);
-    *redundancy = r;
-    *bad_batches = bad;
-    *first_bad = first;
-    for (uint64_t j = 0; j < n_rows; ++j) blame[j] = bl[j];
-    return ok();
+    return host_form(h, s, dimension, indices, rows, lens, n_rows, verdict, true, out, dimension * 8, h->last.repair, o,
+                     [&](const int64_t* din, uint16_t* dver, char* dout, Counts* c) {
+                         const sda::PackedRepairArgs ra{{din, nullptr, dimension, 1, dver},
+                                                        reinterpret_cast<int64_t*>(dout)};
+                         return run_reveal_checked(h, s, ra, indices, n_rows, c, h->stream);
+                     });
 }
 
 sda_status sda_packed_reveal_checked_last_launch(sda_engine* h, uint32_t* path, uint32_t* bucket, uint64_t* fixed,

@@ -57,11 +57,11 @@ struct sda_engine {
     void* pipe = nullptr;         // recipient / participant pipeline scratch (mask, masked, compacted shares)
     size_t pipe_bytes = 0;
     sda::DeviceTable rev_tab;     // packed-Shamir Newton/Lagrange tables (per scheme + clerk set)
-    sda::DeviceTable chk_tab;     // share consistency check: parity weights (per scheme + clerk set)
-    void* chk_buf = nullptr;      // its counters, blame words and bad-batch log (sda::packed_check_buf_bytes())
+    sda::DeviceTable chk_tab;     // share check and checked reveal: parity rows, basis Lagrange rows, inverse weights
+                                  // (per scheme + clerk set; sda::ensure_check_table)
+    void* chk_buf = nullptr;      // their counters, blame words and bad-batch log (sda::packed_check_buf_bytes())
     size_t chk_buf_bytes = 0;
-    sda::DeviceTable rep_tab;     // checked reveal: parity rows, basis Lagrange rows, inverse weights (same key)
-    void* rep_ver = nullptr;      // its verdict words when the caller gives no buffer and something is bad
+    void* rep_ver = nullptr;      // checked reveal: verdict words when the caller gives no buffer and something is bad
     size_t rep_ver_bytes = 0;
     void* snap = nullptr;         // snapshot transposition copy plan
     size_t snap_bytes = 0;

@@ -181,69 +181,62 @@ hipError_t launch_packed_reveal_wide(const PackedRevealArgs& a, const uint64_t* 
                                      uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, int mode,
                                      DeviceTable& tab, hipStream_t s);
 
-// ---- packed_check.hip ----
-// Share consistency check of a reveal's input (sda_packed_check_dev): the shares as PackedRevealArgs lays them out,
-// the per-batch verdicts (device [n_vectors][B], or nullptr) and the counts.
+// ---- packed_check.hip / packed_repair.hip ----
+// Share consistency check of a reveal's input (sda_packed_check_dev): the shares as PackedRevealArgs lays them out and
+// the per-batch verdicts.  The checked reveal (sda_packed_reveal_checked_dev) takes the same plus `out`.
 struct PackedCheckArgs {
     const int64_t* shares; const int32_t* shares32;   // one of the two
     uint64_t dimension; uint64_t n_vectors;
-    uint16_t* verdict;
+    uint16_t* verdict;        // device [n_vectors][B], or nullptr
 };
+struct PackedRepairArgs : PackedCheckArgs {
+    int64_t* out;             // device [n_vectors][dimension]
+};
+// The counts of one call of either family.
 struct PackedCheckResult {
-    PackedCheckPlan plan;
-    bool launched;            // false: no redundancy or no batch -- nothing ran, the counts are zero
-    uint64_t bad, first_bad;  // bad batches; the smallest bad vec * B + b, UINT64_MAX for none
-    uint64_t located;         // batches the location pass walked: the bad ones, or on overflow every batch
-    bool overflowed;          // more bad batches than the log holds
+    uint64_t bad = 0, first_bad = UINT64_MAX;   // bad batches; the smallest bad vec * B + b, UINT64_MAX for none
+    uint64_t located = 0;     // batches the location pass walked: the bad ones, or on overflow every batch
+    uint64_t fixed = 0;       // batches packed_repair_fix_kernel rewrote
+    bool overflowed = false;  // more bad batches than the log holds
+    bool launched = false;    // false: no redundancy -- the check ran nothing and the counts are zero
 };
 constexpr uint32_t kCheckLogCap = 1u << 16;
 size_t packed_check_buf_bytes();
-// Runs the call as packed_check_plan (check_plan.h) decides it and waits for it: *res and blame_host[n_idx] (written
-// only when the location pass ran) are final on return.  `buf`: device memory of packed_check_buf_bytes() bytes;
-// log_cap <= kCheckLogCap entries of its log are used.  hipErrorInvalidValue for repeated clerk points: nothing is
-// launched and `tab` keeps its key.  The caller has checked n_idx >= k + t.
-hipError_t launch_packed_check(const PackedCheckArgs& a, const uint64_t* indices, uint32_t n_idx, uint32_t k,
-                               uint32_t t, uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, DeviceTable& tab,
-                               void* buf, uint32_t log_cap, hipStream_t s, uint64_t* blame_host,
+// The table of a (scheme, indices) pair, n_idx >= k + t, for both families: the check's parity rows, the basis
+// Lagrange rows and the inverse weights (packed_common.h, make_check_table, gives the layout).  hipErrorInvalidValue
+// for repeated clerk points: nothing is uploaded and `tab` keeps its key and contents.
+hipError_t ensure_check_table(DeviceTable& tab, const uint64_t* indices, uint32_t n_idx, uint32_t k, uint32_t t,
+                              uint32_t p, uint32_t omega_secrets, uint32_t omega_shares);
+// What every launch of one call shares.  tab: ensure_check_table's words at row stride ks; cnt: the counter block,
+// device memory of packed_check_buf_bytes() bytes, of whose log `cap` = min(log_cap, kCheckLogCap) entries are used.
+struct CheckGeom {
+    uint64_t B, D;            // batches per vector, the dimension
+    uint32_t n_idx, kt, k, ks;
+    MontP M;
+    const uint32_t* tab;
+    unsigned long long* cnt;
+    uint32_t cap;
+};
+CheckGeom check_geom(const PackedCheckArgs& a, uint32_t n_idx, uint32_t k, uint32_t t, uint32_t p,
+                     const DeviceTable& tab, void* buf, uint32_t log_cap);
+// Runs the check as packed_check_plan (check_plan.h) decides it and waits for it: *res and blame_host[n_idx] (written
+// only when the location pass ran) are final on return.  At least one batch and one vector, n_idx >= k + t.
+hipError_t launch_packed_check(const PackedCheckArgs& a, const CheckGeom& g, hipStream_t s, uint64_t* blame_host,
                                PackedCheckResult* res);
-// The location pass alone, over `total` logged batches of `buf` or with `all` over every batch: a.verdict (when given)
-// gets the located positions and buf's blame words their counts.  tab: parity rows at stride ks.  Only enqueues.
-hipError_t launch_packed_check_locate(const PackedCheckArgs& a, uint64_t B, uint32_t n_idx, uint32_t kt,
-                                      const uint32_t* tab, uint32_t ks, const MontP& M, void* buf, uint64_t total,
-                                      bool all, hipStream_t s);
-
-// ---- packed_repair.hip ----
-// Checked reveal (sda_packed_reveal_checked_dev): the check's arguments plus out [n_vectors][dimension].
-struct PackedRepairArgs {
-    const int64_t* shares; const int32_t* shares32;   // one of the two
-    uint64_t dimension; uint64_t n_vectors;
-    uint16_t* verdict;        // device [n_vectors][B], or nullptr
-    int64_t* out;
-};
-struct PackedRepairResult {
-    uint64_t bad, first_bad;  // bad batches; the smallest bad vec * B + b, UINT64_MAX for none
-    uint64_t fixed;           // batches packed_repair_fix_kernel rewrote
-    bool overflowed;          // more bad batches than the log holds
-};
-// The table of a (scheme, indices) pair: the check's parity rows, the basis Lagrange rows and the inverse weights
-// (packed_repair.hip gives the layout).  hipErrorInvalidValue for repeated clerk points: `tab` keeps its key.
-hipError_t ensure_repair_table(DeviceTable& tab, const uint64_t* indices, uint32_t n_idx, uint32_t k, uint32_t t,
-                               uint32_t p, uint32_t omega_secrets, uint32_t omega_shares);
+// The location pass alone, over `total` logged batches of g.cnt or with `all` over every batch: a.verdict (when given)
+// gets the located positions and the blame words their counts.  Only enqueues.
+hipError_t launch_packed_check_locate(const PackedCheckArgs& a, const CheckGeom& g, uint64_t total, bool all,
+                                      hipStream_t s);
 // The fused first pass (packed_repair_plan: kRepairFused) and its one wait: out holds the reveal of every batch from
-// its first k + t shares, a.verdict (when given) the provisional verdicts, *res the counts.  `tab`: ensure_repair_table's;
-// `buf` and log_cap as launch_packed_check takes them.
-hipError_t launch_packed_repair(const PackedRepairArgs& a, uint32_t n_idx, uint32_t k, uint32_t t, uint32_t p,
-                                const DeviceTable& tab, void* buf, uint32_t log_cap, hipStream_t s,
-                                PackedRepairResult* res);
-// What follows a pass that counted res->bad > 0 bad batches into `buf`, and its wait.  `verdict`: never nullptr (the
+// its first k + t shares, a.verdict (when given) the provisional verdicts, *res the counts.
+hipError_t launch_packed_repair(const PackedRepairArgs& a, const CheckGeom& g, hipStream_t s, PackedCheckResult* res);
+// What follows a pass that counted res->bad > 0 bad batches into g.cnt, and its wait.  `verdict`: never nullptr (the
 // caller's buffer, or zeroed scratch when it gave none).  locate: the location pass first (fused path; the composed
 // path's share check has run it).  recompute: every bad batch is first revealed again from its first k + t shares
 // (composed path: out holds the reveal from all shares); a batch located at a basis position is corrected either way.
 // Fills res->fixed, res->overflowed and, with locate, blame_host[n_idx].
-hipError_t launch_packed_repair_fix(const PackedRepairArgs& a, uint16_t* verdict, uint32_t n_idx, uint32_t k,
-                                    uint32_t t, uint32_t p, const DeviceTable& tab, void* buf, uint32_t log_cap,
-                                    bool locate, bool recompute, hipStream_t s, uint64_t* blame_host,
-                                    PackedRepairResult* res);
+hipError_t launch_packed_repair_fix(const PackedRepairArgs& a, uint16_t* verdict, const CheckGeom& g, bool locate,
+                                    bool recompute, hipStream_t s, uint64_t* blame_host, PackedCheckResult* res);
 
 // ---- codec_decode.hip (share payload codec: sodium.rs:36-41 / :82-88, integer-encoding 1.0 VarInt) ----
 // Host-side plan of the decode: blobs are split into 4 KiB regions aligned to the (16-byte

@@ -10,11 +10,12 @@
 // "syndrome is a multiple of column j" by cross-multiplication (no inverse).
 //
 // Device table (u32 words, Montgomery form): w[c][s] at c * KS + s, KS = kt rounded up to even, the pad word 0 (the
-// kernels take the products of a row in pairs that share one REDC, as reveal_canon_body does).
+// kernels take the products of a row in pairs that share one REDC, as reveal_canon_body does) -- the first r rows of
+// the table ensure_check_table keeps for both families (packed_common.h, make_check_table).
 //
-// The counter block, check_report and the register tuple of a batch are check_common.h's (shared with the checked
-// reveal, packed_repair.hip).
-#include "check_common.h"
+// The counter block, check_report and the register tuple of a batch are check_common.h's, the first pass and the
+// bucket dispatch check_launch.h's (shared with the checked reveal, packed_repair.hip).
+#include "check_launch.h"
 #include "check_plan.h"
 
 namespace sda {
@@ -195,115 +196,84 @@ __global__ __launch_bounds__(64) void packed_check32_locate_kernel(const int32_t
 
 // The location pass over `total` logged batches, or with `all` over every batch of the launch.
 template <class ST>
-hipError_t check_locate_launch_t(const ST* sh, uint16_t* verdict, uint64_t B, uint32_t n_idx, uint32_t kt,
-                                 const uint32_t* tab, uint32_t ks, const MontP& M, unsigned long long* cnt,
-                                 uint64_t total, bool all, hipStream_t s) {
+hipError_t check_locate_launch_t(const ST* sh, uint16_t* verdict, const CheckGeom& g, uint64_t total, bool all,
+                                 hipStream_t s) {
     const unsigned waves = (unsigned)(total < 8192 ? total : 8192);
-    if constexpr (sizeof(ST) == 4)
-        hipLaunchKernelGGL(packed_check32_locate_kernel, dim3(waves), dim3(64), 0, s, sh, B, n_idx, kt, tab, ks, M,
-                           verdict, cnt, total, all ? 1 : 0);
-    else
-        hipLaunchKernelGGL(packed_check_locate_kernel, dim3(waves), dim3(64), 0, s, sh, B, n_idx, kt, tab, ks, M,
-                           verdict, cnt, total, all ? 1 : 0);
+    auto kernel = [] {
+        if constexpr (sizeof(ST) == 4) return packed_check32_locate_kernel; else return packed_check_locate_kernel;
+    }();
+    hipLaunchKernelGGL(kernel, dim3(waves), dim3(64), 0, s, sh, g.B, g.n_idx, g.kt, g.tab, g.ks, g.M, verdict, g.cnt,
+                       total, all ? 1 : 0);
     return hipGetLastError();
 }
 
-// The launches of one call for share type ST: the kernel the plan names, the counters read back (one wait), then the
-// location pass over what the first pass logged (a second wait) when something is bad and r >= 2.
+// The launches of one call for share type ST: the first pass with the kernel the plan names (one wait), then the
+// location pass over what it logged (a second wait) when something is bad and r >= 2.
 template <class ST>
-hipError_t check_launch_t(const PackedCheckPlan& pl, const PackedCheckArgs& a, const ST* sh, uint64_t B, uint32_t n_idx,
-                          uint32_t kt, const uint32_t* tab, uint32_t ks, const MontP& M, unsigned long long* cnt,
-                          uint32_t cap, hipStream_t s, uint64_t* blame_host, PackedCheckResult* res) {
+hipError_t check_launch_t(const PackedCheckPlan& pl, const PackedCheckArgs& a, const ST* sh, const CheckGeom& g,
+                          hipStream_t s, uint64_t* blame_host, PackedCheckResult* res) {
     constexpr bool I32 = sizeof(ST) == 4;
-    const dim3 grid((unsigned)((B + 255) / 256), (unsigned)a.n_vectors);
+    const dim3 grid((unsigned)((g.B + 255) / 256), (unsigned)a.n_vectors);
     auto run = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, sh, B, n_idx, kt, tab, ks, M, a.verdict, cnt, cap);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, sh, g.B, g.n_idx, g.kt, g.tab, g.ks, g.M, a.verdict, g.cnt,
+                           g.cap);
     };
-    auto bucket = [&](auto nmax) {
-        if constexpr (I32) run(packed_check32_kernel<nmax>); else run(packed_check_kernel<nmax>);
-    };
-    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)(kCheckHdr + kCheckBlameCap) * sizeof(uint64_t), s);
-    if (e != hipSuccess) return e;
-    if (pl.path == kCheckLooped) {
-        if constexpr (I32) run(packed_check32_loop_kernel); else run(packed_check_loop_kernel);
-    } else if (pl.bucket == 8) {
-        bucket(std::integral_constant<int, 8>{});
-    } else if (pl.bucket == 16) {
-        bucket(std::integral_constant<int, 16>{});
-    } else if (pl.bucket == 32) {
-        bucket(std::integral_constant<int, 32>{});
-    } else {
-        return hipErrorInvalidValue;
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    uint64_t head[2] = {0, 0};
-    if ((e = hipMemcpyAsync(head, cnt, sizeof(head), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-    res->bad = head[0];
-    res->first_bad = ~head[1];                              // 0 (no max taken) -> UINT64_MAX
-    res->located = 0;
-    res->overflowed = false;
-    if (!pl.locate || res->bad == 0) return hipSuccess;
-    res->overflowed = res->bad > cap;
-    const uint64_t total = res->overflowed ? B * a.n_vectors : res->bad;
-    res->located = total;
-    if ((e = check_locate_launch_t(sh, a.verdict, B, n_idx, kt, tab, ks, M, cnt, total, res->overflowed, s)) != hipSuccess)
-        return e;
-    if ((e = hipMemcpyAsync(blame_host, cnt + kCheckHdr, (size_t)n_idx * sizeof(uint64_t), hipMemcpyDeviceToHost, s)) !=
-        hipSuccess)
+    hipError_t e = first_pass(g, s, [&] {
+        if (pl.path == kCheckLooped) {
+            if constexpr (I32) run(packed_check32_loop_kernel); else run(packed_check_loop_kernel);
+            return true;
+        }
+        return with_bucket(pl.bucket, [&](auto nmax) {
+            if constexpr (I32) run(packed_check32_kernel<nmax>); else run(packed_check_kernel<nmax>);
+        });
+    }, res);
+    if (e != hipSuccess || !pl.locate || res->bad == 0) return e;
+    res->located = bad_total(g, a.n_vectors, res);
+    if ((e = check_locate_launch_t(sh, a.verdict, g, res->located, res->overflowed, s)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(blame_host, g.cnt + kCheckHdr, (size_t)g.n_idx * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                            s)) != hipSuccess)
         return e;
     return hipStreamSynchronize(s);
 }
 
 }  // namespace
 
-hipError_t launch_packed_check_locate(const PackedCheckArgs& a, uint64_t B, uint32_t n_idx, uint32_t kt,
-                                      const uint32_t* tab, uint32_t ks, const MontP& M, void* buf, uint64_t total,
-                                      bool all, hipStream_t s) {
-    unsigned long long* cnt = static_cast<unsigned long long*>(buf);
-    return a.shares32 ? check_locate_launch_t(a.shares32, a.verdict, B, n_idx, kt, tab, ks, M, cnt, total, all, s)
-                      : check_locate_launch_t(a.shares, a.verdict, B, n_idx, kt, tab, ks, M, cnt, total, all, s);
-}
-
 size_t packed_check_buf_bytes() { return (size_t)(kCheckHdr + kCheckBlameCap + kCheckLogCap) * sizeof(uint64_t); }
 
-hipError_t launch_packed_check(const PackedCheckArgs& a, const uint64_t* indices, uint32_t n_idx, uint32_t k,
-                               uint32_t t, uint32_t p, uint32_t omega_secrets, uint32_t omega_shares, DeviceTable& tab,
-                               void* buf, uint32_t log_cap, hipStream_t s, uint64_t* blame_host,
-                               PackedCheckResult* res) {
-    const PackedCheckPlan pl = packed_check_plan(n_idx, k, t);
-    const uint32_t kt = k + t, r = pl.redundancy, ks = (kt + 1) & ~1u;
-    const uint64_t B = (a.dimension + k - 1) / k;
+hipError_t ensure_check_table(DeviceTable& tab, const uint64_t* indices, uint32_t n_idx, uint32_t k, uint32_t t,
+                              uint32_t p, uint32_t omega_secrets, uint32_t omega_shares) {
     std::vector<uint8_t> key(sizeof(uint32_t) * 6 + sizeof(uint64_t) * n_idx);
     const uint32_t kv[6] = {n_idx, k, t, p, omega_secrets, omega_shares};
     memcpy(key.data(), kv, sizeof(kv));
     memcpy(key.data() + sizeof(kv), indices, sizeof(uint64_t) * n_idx);
-    // repeated points have no systematic form: refused before anything is launched, and `tab` keeps its key
-    if (tab.key != key) {
-        const RevealTables T = make_reveal_tables(indices, n_idx, k, p, omega_secrets, omega_shares);
-        if (T.duplicate) return hipErrorInvalidValue;
-        std::vector<uint32_t> host((size_t)(r ? r : 1) * ks, 0);
-        if (r) {
-            const std::vector<int64_t> w = make_check_weights(T, n_idx, kt, p);
-            for (uint32_t c = 0; c < r; ++c)
-                for (uint32_t i = 0; i < kt; ++i) host[(size_t)c * ks + i] = to_mont(w[(size_t)c * kt + i], p);
-        }
-        const hipError_t e = ensure_table(tab, key, host.data(), host.size() * sizeof(uint32_t));
-        if (e != hipSuccess) return e;
-    }
-    res->plan = pl;
-    res->bad = res->located = 0;
-    res->first_bad = UINT64_MAX;
-    res->overflowed = false;
-    res->launched = false;
-    if (pl.path == kCheckNothing || B == 0 || a.n_vectors == 0) return hipSuccess;
+    if (tab.key == key) return hipSuccess;
+    const CheckTable T = make_check_table(indices, n_idx, k, t, p, omega_secrets, omega_shares);
+    if (T.duplicate) return hipErrorInvalidValue;         // repeated points have no systematic form
+    return ensure_table(tab, key, T.words.data(), T.words.size() * sizeof(uint32_t));
+}
+
+CheckGeom check_geom(const PackedCheckArgs& a, uint32_t n_idx, uint32_t k, uint32_t t, uint32_t p,
+                     const DeviceTable& tab, void* buf, uint32_t log_cap) {
+    const uint32_t kt = k + t;
+    return {(a.dimension + k - 1) / k, a.dimension, n_idx, kt, k, (kt + 1) & ~1u, make_mont(p),
+            static_cast<const uint32_t*>(tab.dev), static_cast<unsigned long long*>(buf),
+            log_cap < kCheckLogCap ? log_cap : kCheckLogCap};
+}
+
+hipError_t launch_packed_check_locate(const PackedCheckArgs& a, const CheckGeom& g, uint64_t total, bool all,
+                                      hipStream_t s) {
+    return a.shares32 ? check_locate_launch_t(a.shares32, a.verdict, g, total, all, s)
+                      : check_locate_launch_t(a.shares, a.verdict, g, total, all, s);
+}
+
+hipError_t launch_packed_check(const PackedCheckArgs& a, const CheckGeom& g, hipStream_t s, uint64_t* blame_host,
+                               PackedCheckResult* res) {
+    const PackedCheckPlan pl = packed_check_plan(g.n_idx, g.k, g.kt - g.k);
+    *res = PackedCheckResult{};
+    if (pl.path == kCheckNothing) return hipSuccess;
     res->launched = true;
-    const MontP M = make_mont(p);
-    const uint32_t cap = log_cap < kCheckLogCap ? log_cap : kCheckLogCap;
-    unsigned long long* cnt = static_cast<unsigned long long*>(buf);
-    const uint32_t* dtab = static_cast<const uint32_t*>(tab.dev);
-    return a.shares32 ? check_launch_t(pl, a, a.shares32, B, n_idx, kt, dtab, ks, M, cnt, cap, s, blame_host, res)
-                      : check_launch_t(pl, a, a.shares, B, n_idx, kt, dtab, ks, M, cnt, cap, s, blame_host, res);
+    return a.shares32 ? check_launch_t(pl, a, a.shares32, g, s, blame_host, res)
+                      : check_launch_t(pl, a, a.shares, g, s, blame_host, res);
 }
 
 }  // namespace sda

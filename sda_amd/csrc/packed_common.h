@@ -235,6 +235,33 @@ inline RepairTables make_repair_tables(const RevealTables& T, uint32_t n_idx, ui
     return R;
 }
 
+// The one device table of the share check and the checked reveal for a (scheme, clerk set), n_idx >= kt = k + t: u32
+// words in Montgomery form, rows of ks = kt rounded up to even words, the pad word 0 (the kernels take the products
+// of a row in pairs that share one REDC):
+//   rows [0, r)       make_check_weights' parity rows w[c][s], r = n_idx - kt
+//   rows [r, r + k)   make_repair_tables' lam[e][s]
+//   row  r + k        its winv[s] (zeros when r == 0)
+// duplicate: two points coincide, there is no systematic form and `words` is empty.
+struct CheckTable { std::vector<uint32_t> words; bool duplicate = false; };
+inline CheckTable make_check_table(const uint64_t* indices, uint32_t n_idx, uint32_t k, uint32_t t, int64_t p,
+                                   int64_t ws, int64_t wn) {
+    const uint32_t kt = k + t, r = n_idx - kt, ks = (kt + 1) & ~1u;
+    const RevealTables T = make_reveal_tables(indices, n_idx, k, p, ws, wn);
+    CheckTable C;
+    C.duplicate = T.duplicate;
+    if (T.duplicate) return C;
+    const std::vector<int64_t> w = r ? make_check_weights(T, n_idx, kt, p) : std::vector<int64_t>();
+    const RepairTables R = make_repair_tables(T, n_idx, k, kt, p, ws, w);
+    C.words.assign((size_t)(r + k + 1) * ks, 0);
+    auto row = [&](uint32_t at, const int64_t* src) {
+        for (uint32_t i = 0; i < kt; ++i) C.words[(size_t)at * ks + i] = to_mont(src[i], p);
+    };
+    for (uint32_t c = 0; c < r; ++c) row(c, w.data() + (size_t)c * kt);
+    for (uint32_t e = 0; e < k; ++e) row(r + e, R.lam.data() + (size_t)e * kt);
+    if (r) row(r + k, R.winv.data());
+    return C;
+}
+
 // Rust `v % p` from the canonical residue c and the sign word sw of the exact dividend v.
 //   exact (LAZY = false): trunc_rep, 5 VALU ops incl. the c == 0 case (v < 0, v = 0 mod p -> 0);
 //   LAZY: c - (p & sign), 3 ops, which gives -p instead of 0 exactly when v < 0 and v = 0 mod p

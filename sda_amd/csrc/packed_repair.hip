@@ -15,11 +15,12 @@
 // Schemes past the fused kernel (repair_plan.h) run the share check and the CANONICAL reveal as they are, and the
 // fix-up then recomputes every bad batch from its basis before it corrects.
 //
-// Device table (u32 words, Montgomery form, rows of KS = kt rounded up to even words, pad word 0):
+// Device table (u32 words, Montgomery form, rows of KS = kt rounded up to even words, pad word 0) -- the one
+// ensure_check_table (packed_check.hip) keeps for both families, built by make_check_table (packed_common.h):
 //   rows [0, r)       the check's parity rows w[c][s]
 //   rows [r, r + k)   lam[e][s]
 //   row  r + k        winv[s] (zeros when r == 0)
-#include "check_common.h"
+#include "check_launch.h"
 #include "repair_plan.h"
 
 namespace sda {
@@ -144,117 +145,60 @@ __global__ __launch_bounds__(256) void packed_repair32_fix_kernel(const int32_t*
     repair_fix_body(shares, B, D, out, n_idx, kt, k, tab, ks, M, verdict, cnt, total, all, recompute);
 }
 
-// The fused first pass for share type ST: counters zeroed, the bucket's kernel, the counts read back (one wait).
-template <class ST>
-hipError_t repair_launch_t(const PackedRepairPlan& pl, const PackedRepairArgs& a, const ST* sh, uint64_t B,
-                           uint32_t n_idx, uint32_t kt, uint32_t k, const uint32_t* tab, uint32_t ks, const MontP& M,
-                           unsigned long long* cnt, uint32_t cap, hipStream_t s, PackedRepairResult* res) {
-    const dim3 grid((unsigned)((B + 255) / 256), (unsigned)a.n_vectors);
-    const size_t lds = (size_t)256 * k * sizeof(int64_t);
-    auto bucket = [&](auto nmax) {
-        auto kernel = [&] {
-            if constexpr (sizeof(ST) == 4) return packed_repair32_kernel<nmax>; else return packed_repair_kernel<nmax>;
-        }();
-        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, sh, B, a.dimension, a.out, n_idx, kt, k, tab, ks, M,
-                           a.verdict, cnt, cap);
-    };
-    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)(kCheckHdr + kCheckBlameCap) * sizeof(uint64_t), s);
-    if (e != hipSuccess) return e;
-    if (pl.bucket == 8) bucket(std::integral_constant<int, 8>{});
-    else if (pl.bucket == 16) bucket(std::integral_constant<int, 16>{});
-    else if (pl.bucket == 32) bucket(std::integral_constant<int, 32>{});
-    else return hipErrorInvalidValue;
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    uint64_t head[2] = {0, 0};
-    if ((e = hipMemcpyAsync(head, cnt, sizeof(head), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-    res->bad = head[0];
-    res->first_bad = ~head[1];                              // 0 (no max taken) -> UINT64_MAX
-    return hipSuccess;
-}
 
-std::vector<uint8_t> repair_key(const uint64_t* indices, uint32_t n_idx, uint32_t k, uint32_t t, uint32_t p,
-                                uint32_t omega_secrets, uint32_t omega_shares) {
-    std::vector<uint8_t> key(sizeof(uint32_t) * 6 + sizeof(uint64_t) * n_idx);
-    const uint32_t kv[6] = {n_idx, k, t, p, omega_secrets, omega_shares};
-    memcpy(key.data(), kv, sizeof(kv));
-    memcpy(key.data() + sizeof(kv), indices, sizeof(uint64_t) * n_idx);
-    return key;
+// The fused first pass for share type ST: the bucket's kernel inside first_pass (one wait).
+template <class ST>
+hipError_t repair_launch_t(const PackedRepairPlan& pl, const PackedRepairArgs& a, const ST* sh, const CheckGeom& g,
+                           hipStream_t s, PackedCheckResult* res) {
+    const dim3 grid((unsigned)((g.B + 255) / 256), (unsigned)a.n_vectors);
+    const size_t lds = (size_t)256 * g.k * sizeof(int64_t);
+    return first_pass(g, s, [&] {
+        return with_bucket(pl.bucket, [&](auto nmax) {
+            auto kernel = [&] {
+                if constexpr (sizeof(ST) == 4) return packed_repair32_kernel<nmax>; else return packed_repair_kernel<nmax>;
+            }();
+            hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, sh, g.B, g.D, a.out, g.n_idx, g.kt, g.k, g.tab, g.ks,
+                               g.M, a.verdict, g.cnt, g.cap);
+        });
+    }, res);
 }
 
 }  // namespace
 
-hipError_t ensure_repair_table(DeviceTable& tab, const uint64_t* indices, uint32_t n_idx, uint32_t k, uint32_t t,
-                               uint32_t p, uint32_t omega_secrets, uint32_t omega_shares) {
-    const std::vector<uint8_t> key = repair_key(indices, n_idx, k, t, p, omega_secrets, omega_shares);
-    if (tab.key == key) return hipSuccess;
-    const uint32_t kt = k + t, r = n_idx - kt, ks = (kt + 1) & ~1u;
-    const RevealTables T = make_reveal_tables(indices, n_idx, k, p, omega_secrets, omega_shares);
-    if (T.duplicate) return hipErrorInvalidValue;         // repeated points have no systematic form
-    const std::vector<int64_t> w = r ? make_check_weights(T, n_idx, kt, p) : std::vector<int64_t>();
-    const RepairTables R = make_repair_tables(T, n_idx, k, kt, p, omega_secrets, w);
-    std::vector<uint32_t> host((size_t)(r + k + 1) * ks, 0);
-    for (uint32_t c = 0; c < r; ++c)
-        for (uint32_t i = 0; i < kt; ++i) host[(size_t)c * ks + i] = to_mont(w[(size_t)c * kt + i], p);
-    for (uint32_t e = 0; e < k; ++e)
-        for (uint32_t i = 0; i < kt; ++i) host[(size_t)(r + e) * ks + i] = to_mont(R.lam[(size_t)e * kt + i], p);
-    for (uint32_t i = 0; i < kt && r; ++i) host[(size_t)(r + k) * ks + i] = to_mont(R.winv[i], p);
-    return ensure_table(tab, key, host.data(), host.size() * sizeof(uint32_t));
-}
-
-hipError_t launch_packed_repair(const PackedRepairArgs& a, uint32_t n_idx, uint32_t k, uint32_t t, uint32_t p,
-                                const DeviceTable& tab, void* buf, uint32_t log_cap, hipStream_t s,
-                                PackedRepairResult* res) {
-    const PackedRepairPlan pl = packed_repair_plan(n_idx, k, t);
+hipError_t launch_packed_repair(const PackedRepairArgs& a, const CheckGeom& g, hipStream_t s, PackedCheckResult* res) {
+    const PackedRepairPlan pl = packed_repair_plan(g.n_idx, g.k, g.kt - g.k);
     if (pl.path != kRepairFused) return hipErrorInvalidValue;
-    const uint32_t kt = k + t, ks = (kt + 1) & ~1u;
-    const uint64_t B = (a.dimension + k - 1) / k;
-    const MontP M = make_mont(p);
-    const uint32_t cap = log_cap < kCheckLogCap ? log_cap : kCheckLogCap;
-    unsigned long long* cnt = static_cast<unsigned long long*>(buf);
-    const uint32_t* dtab = static_cast<const uint32_t*>(tab.dev);
-    res->bad = res->fixed = 0;
-    res->first_bad = UINT64_MAX;
-    res->overflowed = false;
-    return a.shares32 ? repair_launch_t(pl, a, a.shares32, B, n_idx, kt, k, dtab, ks, M, cnt, cap, s, res)
-                      : repair_launch_t(pl, a, a.shares, B, n_idx, kt, k, dtab, ks, M, cnt, cap, s, res);
+    *res = PackedCheckResult{};
+    res->launched = true;
+    return a.shares32 ? repair_launch_t(pl, a, a.shares32, g, s, res) : repair_launch_t(pl, a, a.shares, g, s, res);
 }
 
-hipError_t launch_packed_repair_fix(const PackedRepairArgs& a, uint16_t* verdict, uint32_t n_idx, uint32_t k,
-                                    uint32_t t, uint32_t p, const DeviceTable& tab, void* buf, uint32_t log_cap,
-                                    bool locate, bool recompute, hipStream_t s, uint64_t* blame_host,
-                                    PackedRepairResult* res) {
-    const uint32_t kt = k + t, ks = (kt + 1) & ~1u;
-    const uint64_t B = (a.dimension + k - 1) / k;
-    const MontP M = make_mont(p);
-    const uint32_t cap = log_cap < kCheckLogCap ? log_cap : kCheckLogCap;
-    unsigned long long* cnt = static_cast<unsigned long long*>(buf);
-    const uint32_t* dtab = static_cast<const uint32_t*>(tab.dev);
-    res->overflowed = res->bad > cap;
-    const uint64_t total = res->overflowed ? B * a.n_vectors : res->bad;
+hipError_t launch_packed_repair_fix(const PackedRepairArgs& a, uint16_t* verdict, const CheckGeom& g, bool locate,
+                                    bool recompute, hipStream_t s, uint64_t* blame_host, PackedCheckResult* res) {
+    const uint64_t total = bad_total(g, a.n_vectors, res);
     const int all = res->overflowed ? 1 : 0;
     hipError_t e;
     if (locate) {
-        const PackedCheckArgs ca{a.shares, a.shares32, a.dimension, a.n_vectors, verdict};
-        if ((e = launch_packed_check_locate(ca, B, n_idx, kt, dtab, ks, M, buf, total, res->overflowed, s)) != hipSuccess)
-            return e;
+        PackedCheckArgs ca = a;
+        ca.verdict = verdict;
+        if ((e = launch_packed_check_locate(ca, g, total, res->overflowed, s)) != hipSuccess) return e;
     }
     const uint64_t blocks = (total + 255) / 256;
     const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
     if (a.shares32)
-        hipLaunchKernelGGL(packed_repair32_fix_kernel, grid, dim3(256), 0, s, a.shares32, B, a.dimension, a.out, n_idx,
-                           kt, k, dtab, ks, M, verdict, cnt, total, all, recompute ? 1 : 0);
+        hipLaunchKernelGGL(packed_repair32_fix_kernel, grid, dim3(256), 0, s, a.shares32, g.B, g.D, a.out, g.n_idx, g.kt,
+                           g.k, g.tab, g.ks, g.M, verdict, g.cnt, total, all, recompute ? 1 : 0);
     else
-        hipLaunchKernelGGL(packed_repair_fix_kernel, grid, dim3(256), 0, s, a.shares, B, a.dimension, a.out, n_idx, kt,
-                           k, dtab, ks, M, verdict, cnt, total, all, recompute ? 1 : 0);
+        hipLaunchKernelGGL(packed_repair_fix_kernel, grid, dim3(256), 0, s, a.shares, g.B, g.D, a.out, g.n_idx, g.kt,
+                           g.k, g.tab, g.ks, g.M, verdict, g.cnt, total, all, recompute ? 1 : 0);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    std::vector<uint64_t> back(kCheckHdr + n_idx, 0);
-    if ((e = hipMemcpyAsync(back.data(), cnt, back.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
+    std::vector<uint64_t> back(kCheckHdr + g.n_idx, 0);
+    if ((e = hipMemcpyAsync(back.data(), g.cnt, back.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
         return e;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
     res->fixed = back[2];
     if (locate)
-        for (uint32_t j = 0; j < n_idx; ++j) blame_host[j] = back[kCheckHdr + j];
+        for (uint32_t j = 0; j < g.n_idx; ++j) blame_host[j] = back[kCheckHdr + j];
     return hipSuccess;
 }
 

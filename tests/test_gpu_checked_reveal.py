@@ -438,3 +438,114 @@ def test_record_is_all_zeros_before_the_first_checked_reveal():
         assert e.packed_reveal_checked_last_launch() == E.RepairLaunch(0, 0, 0, 0)
     finally:
         e.close()
+
+
+# ---- the one table of a (scheme, clerk set): shared by the share check and the checked reveal ----
+def _new_engine():
+    import torch
+    torch.cuda.init()                                        # torch opens the device first (tests/conftest.py)
+    return E.Engine(0)
+
+
+def _run_on(eng, kind, sch, D, idx, shares, width):
+    """One share check or checked reveal of `shares` [1][n_idx][B] on eng: everything the call hands back."""
+    dev = Dev(shares, width, 1, shares.shape[2], D)
+    if kind == "check":
+        fn = eng.packed_check32_dev if width == 32 else eng.packed_check_dev
+        got = fn(sch, D, idx, 1, dev.shares.data_ptr(), dev.verdict_ptr)
+        return got, dev.verdict().copy(), dev.out().copy(), eng.packed_check_last_launch()
+    got = _call(eng, sch, D, idx, 1, dev, width)
+    return got, dev.verdict().copy(), dev.out().copy(), eng.packed_reveal_checked_last_launch()
+
+
+def _same(a, b):
+    return a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]) and a[3] == b[3]
+
+
+def _fresh(kind, sch, D, idx, shares, width):
+    e = _new_engine()
+    try:
+        return _run_on(e, kind, sch, D, idx, shares, width)
+    finally:
+        e.close()
+
+
+def _two_faults(name, n_idx, seed):
+    """(indices, canonical shares [1][n_idx][65], D): a basis-position fault in batch 5 (position 2) and a
+    check-position fault in the last batch (position n_idx - 1)."""
+    sch = SCHEMES[name]
+    p = sch.prime_modulus
+    rows, _, D = _oracle_rows(name, 1, 65)
+    idx = _indices(sch, n_idx, seed)
+    canon = rows[0][:, idx, :] % p
+    canon[0, 1, 5] = (canon[0, 1, 5] + 1) % p
+    canon[0, n_idx - 2, 64] = (canon[0, n_idx - 2, 64] + p - 1) % p
+    return idx, canon, D
+
+
+@pytest.mark.parametrize("name,n_idx,width", (("b8", 7, 64), ("n80", 40, 32), ("n80", 40, 64)))
+def test_the_shared_table_serves_both_families_in_any_order(name, n_idx, width):
+    sch = SCHEMES[name]
+    assert n_idx - kt_of(sch) >= 2 and _composed(sch, n_idx) == (name == "n80")
+    idx1, sh1, D = _two_faults(name, n_idx, 101)
+    idx2, sh2, _ = _two_faults(name, n_idx, 202)
+    assert idx1 != idx2
+    eng = _new_engine()
+    try:
+        for kind, idx, sh in (("check", idx1, sh1), ("reveal", idx1, sh1), ("check", idx2, sh2), ("reveal", idx1, sh1)):
+            got = _run_on(eng, kind, sch, D, idx, sh, width)
+            assert _same(got, _fresh(kind, sch, D, idx, sh, width)), (kind, idx)
+            blame = [0] * n_idx
+            blame[1] = blame[n_idx - 2] = 1
+            assert got[0] == E.ShareCheck(n_idx - kt_of(sch), 2, 5, blame)
+            verdict = got[1][GUARD:-GUARD]
+            assert verdict[5] == 2 and verdict[64] == n_idx - 1 and np.count_nonzero(verdict) == 2
+    finally:
+        eng.close()
+
+
+def test_a_table_built_at_r0_carries_the_reveal_rows():
+    import torch
+    sch = SCHEMES["b8"]
+    assert kt_of(sch) == 3
+    rows, secrets, D = _oracle_rows("b8", 1, 65)
+    idx = _indices(sch, 3, 303)
+    shares = rows[0][:, idx, :]
+    eng = _new_engine()
+    try:
+        dev = Dev(shares, 64, 1, 65, D)
+        none = E.ShareCheck(0, 0, E.CHECK_NO_BAD, [0, 0, 0])
+        assert eng.packed_check_dev(sch, D, idx, 1, dev.shares.data_ptr(), None) == none      # launches nothing
+        assert eng.packed_check_last_launch() == E.CheckLaunch(0, 0, 0, 0)
+        assert _call(eng, sch, D, idx, 1, dev, 64) == none
+        plain = torch.full((D,), OUT_SENT, dtype=torch.int64, device="cuda")
+        eng.packed_reconstruct_dev(sch, D, idx, 1, dev.shares.data_ptr(), plain.data_ptr(), E.REVEAL_CANONICAL)
+        torch.cuda.synchronize()
+        assert np.array_equal(dev.out(), dev.expect_out(plain.cpu().numpy()))
+        assert np.array_equal(plain.cpu().numpy(), secrets[0, 0])
+        assert eng.packed_reveal_checked_last_launch() == E.RepairLaunch(E.REPAIR_PATH_FUSED, 8, 0, 0)
+    finally:
+        eng.close()
+
+
+def test_a_refused_call_leaves_the_cache_intact_across_families():
+    sch = SCHEMES["b8"]
+    idx, shares, D = _two_faults("b8", 7, 404)
+    repeated = idx[:-1] + [idx[0]]
+    eng = _new_engine()
+    try:
+        for valid, refused, message in (("check", "reveal", "the checked reveal needs distinct clerk indices"),
+                                        ("reveal", "check", "the share check needs distinct clerk indices")):
+            first = _run_on(eng, valid, sch, D, idx, shares, 64)
+            assert first[0].bad_batches == 2
+            dev = Dev(shares, 64, 1, 65, D)
+            with pytest.raises(E.SdaError) as e:
+                if refused == "reveal":
+                    _call(eng, sch, D, repeated, 1, dev, 64)
+                else:
+                    eng.packed_check_dev(sch, D, repeated, 1, dev.shares.data_ptr(), dev.verdict_ptr)
+            assert e.value.status == UNSUPPORTED and message in str(e.value)
+            assert (dev.out() == OUT_SENT).all() and (dev.verdict() == SENT).all()
+            assert _same(_run_on(eng, valid, sch, D, idx, shares, 64), first)
+    finally:
+        eng.close()
