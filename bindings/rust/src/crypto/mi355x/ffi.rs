@@ -195,6 +195,28 @@ extern "C" {
                                           blame: *mut u64, out: *mut i64) -> SdaStatus;
     pub fn sda_packed_reveal_checked_last_launch(h: *mut SdaEngine, path: *mut u32, bucket: *mut u32,
                                                  fixed: *mut u64, overflowed: *mut u32) -> SdaStatus;
+    // decoded reveal: the checked reveal's arguments plus wrong (u32 [n_vectors][B] on the device, host [B] for
+    // sda_secret_reconstruct_decoded, or NULL), the radius and the undecodable count
+    pub fn sda_packed_reveal_decoded_dev(h: *mut SdaEngine, s: *const SdaSharingScheme, dimension: u64,
+                                         indices: *const u64, n_idx: u64, n_vectors: u64, shares: *const i64,
+                                         out: *mut i64, verdict: *mut c_void, wrong: *mut c_void,
+                                         redundancy: *mut u64, radius: *mut u64, bad_batches: *mut u64,
+                                         first_bad: *mut u64, undecoded: *mut u64, blame: *mut u64,
+                                         stream: *mut c_void) -> SdaStatus;
+    pub fn sda_packed_reveal_decoded32_dev(h: *mut SdaEngine, s: *const SdaSharingScheme, dimension: u64,
+                                           indices: *const u64, n_idx: u64, n_vectors: u64, shares: *const i32,
+                                           out: *mut i64, verdict: *mut c_void, wrong: *mut c_void,
+                                           redundancy: *mut u64, radius: *mut u64, bad_batches: *mut u64,
+                                           first_bad: *mut u64, undecoded: *mut u64, blame: *mut u64,
+                                           stream: *mut c_void) -> SdaStatus;
+    pub fn sda_secret_reconstruct_decoded(h: *mut SdaEngine, s: *const SdaSharingScheme, dimension: u64,
+                                          indices: *const u64, share_rows: *const *const i64,
+                                          share_lens: *const u64, n_idx: u64, verdict: *mut c_void,
+                                          wrong: *mut c_void, redundancy: *mut u64, radius: *mut u64,
+                                          bad_batches: *mut u64, first_bad: *mut u64, undecoded: *mut u64,
+                                          blame: *mut u64, out: *mut i64) -> SdaStatus;
+    pub fn sda_packed_decode_last_launch(h: *mut SdaEngine, path: *mut u32, bucket: *mut u32, decoded: *mut u64,
+                                         fixed: *mut u64, max_errors: *mut u32, overflowed: *mut u32) -> SdaStatus;
     pub fn sda_additive_generate_dev(h: *mut SdaEngine, modulus: i64, share_count: u64, secrets: *const i64,
                                      dimension: u64, draws: *const i64, out: *mut i64, stream: *mut c_void)
                                      -> SdaStatus;

@@ -312,6 +312,63 @@ impl GpuReconstructor {
     }
 }
 
+/// What `reconstruct_decoded` found beside the secrets.
+pub struct ShareDecode {
+    /// r = shares given - (k + t), and the wrong shares per batch that are corrected, r / 2
+    pub redundancy: usize,
+    pub radius: usize,
+    pub bad_batches: usize,
+    pub first_bad: Option<usize>,
+    /// batches with more wrong shares than `radius`: their secrets are not to be trusted
+    pub undecoded: usize,
+    /// blame[i]: the batches in which indexed_shares[i] was found wrong and corrected
+    pub blame: Vec<usize>,
+    /// per batch: 0 consistent, the number of wrong shares corrected, 0xFFFF undecodable
+    pub verdict: Vec<u16>,
+    /// per batch: bit i set when indexed_shares[i] was wrong
+    pub wrong: Vec<u32>,
+}
+
+impl GpuReconstructor {
+    /// `reconstruct` with up to r / 2 wrong clerk results per batch corrected (sda_secret_reconstruct_decoded): the
+    /// canonical secrets of the shares that agree, and which clerks were wrong where.  A batch whose verdict is 0xFFFF
+    /// holds the reveal from the first k + t shares and is not to be trusted.  PackedShamir, at most 32 clerk
+    /// results and k <= 8.
+    pub fn reconstruct_decoded(&self, indexed_shares: &Vec<(usize, Vec<Share>)>)
+                               -> SdaClientResult<(Vec<Secret>, ShareDecode)> {
+        let idx: Vec<u64> = indexed_shares.iter().map(|&(i, _)| i as u64).collect();
+        let ptrs: Vec<*const i64> = indexed_shares.iter().map(|&(_, ref r)| r.as_ptr()).collect();
+        let lens: Vec<u64> = indexed_shares.iter().map(|&(_, ref r)| r.len() as u64).collect();
+        let mut out = vec![0_i64; std::cmp::max(self.dimension, 1)];
+        let mut verdict = vec![0_u16; std::cmp::max(self.dimension, 1)];
+        let mut wrong = vec![0_u32; std::cmp::max(self.dimension, 1)];
+        let mut blame = vec![0_u64; std::cmp::max(idx.len(), 1)];
+        let (mut r, mut rad, mut bad, mut first, mut und) = (0_u64, 0_u64, 0_u64, 0_u64, 0_u64);
+        let (c, dim) = (self.c, self.dimension as u64);
+        self.dev.call(|h| unsafe {
+            sda_secret_reconstruct_decoded(h, &c, dim, idx.as_ptr(), ptrs.as_ptr(), lens.as_ptr(), ptrs.len() as u64,
+                                           verdict.as_mut_ptr() as *mut c_void, wrong.as_mut_ptr() as *mut c_void,
+                                           &mut r, &mut rad, &mut bad, &mut first, &mut und, blame.as_mut_ptr(),
+                                           out.as_mut_ptr())
+        })?;
+        let k = std::cmp::max(c.secret_count as usize, 1);
+        out.truncate(self.dimension);
+        verdict.truncate((self.dimension + k - 1) / k);
+        wrong.truncate((self.dimension + k - 1) / k);
+        blame.truncate(idx.len());
+        Ok((out, ShareDecode {
+            redundancy: r as usize,
+            radius: rad as usize,
+            bad_batches: bad as usize,
+            first_bad: if first == u64::max_value() { None } else { Some(first as usize) },
+            undecoded: und as usize,
+            blame: blame.into_iter().map(|x| x as usize).collect(),
+            verdict: verdict,
+            wrong: wrong,
+        }))
+    }
+}
+
 impl SecretReconstructor for GpuReconstructor {
     fn reconstruct(&self, indexed_shares: &Vec<(usize, Vec<Share>)>) -> SdaClientResult<Vec<Secret>> {
         let idx: Vec<u64> = indexed_shares.iter().map(|&(i, _)| i as u64).collect();

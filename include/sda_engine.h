@@ -549,6 +549,65 @@ sda_status sda_secret_reconstruct_checked(sda_engine* h, const sda_sharing_schem
 sda_status sda_packed_reveal_checked_last_launch(sda_engine* h, uint32_t* path, uint32_t* bucket, uint64_t* fixed,
                                                  uint32_t* overflowed);
 
+/* ---- decoded reveal: the CANONICAL reveal with up to floor(r / 2) wrong clerk shares per batch corrected ----
+ * The n_idx + 1 points of a batch (the share check's: x_0 = 1, y_0 = 0, then x_j = omega_shares^(indices[j-1] + 1),
+ * y_j = share j mod p) are a word of a Reed-Solomon code of minimum distance r + 1, r = n_idx - (k + t), so up to
+ * e_max = floor(r / 2) wrong shares per batch are uniquely correctable.  Per batch:
+ *   consistent          one polynomial of degree < L = k + t + 1 passes through all n_idx + 1 points (the check's);
+ *   decoded with E      E a set of positions in 1 .. n_idx, 1 <= |E| <= e_max, the points without E are consistent
+ *                       and no smaller such set exists.  At most one such E exists (two would give two codewords at
+ *                       distance <= 2 e_max <= r).  Point 0 is never in E: a word whose nearest codeword disagrees
+ *                       with (1, 0) is undecodable;
+ *   undecodable         otherwise.
+ *                       verdict (uint16_t)   wrong (uint32_t, bit j-1 = position j)   secrets written
+ *   consistent          0                    0                  sda_packed_reconstruct_dev CANONICAL of all shares,
+ *                                                               bit for bit
+ *   decoded with E      |E|                  the bits of E      the CANONICAL reveal of the n_idx - |E| shares without E
+ *   undecodable         0xFFFF               0                  the CANONICAL reveal from the first k + t shares (the
+ *                                                               checked reveal's rule: flagged garbage)
+ * With |E| = 1 this is the share check's "located at j": every batch sda_packed_reveal_checked_dev answers with 0 or
+ * j gets the same secrets here, E = {j}.  r < 2 behaves as the checked reveal does (r == 0: the plain canonical
+ * reveal, zero counts; r == 1: detect and flag).  Output is always canonical, in [0, p); raw i64 shares outside
+ * (-p, p) are reduced exactly.
+ * Inputs and out as sda_packed_reveal_checked_dev takes them.  verdict: device uint16_t [n_vectors][B] or NULL; wrong:
+ * device uint32_t [n_vectors][B], 4-byte aligned, or NULL, independent of verdict.  Host outputs (all required; blame
+ * may be NULL when n_idx == 0): *redundancy = r, *radius = e_max, *bad_batches and *first_bad as the check gives
+ * them, *undecoded = the batches with verdict 0xFFFF, blame[j-1] = the batches whose E contains position j (the sum
+ * of blame is the sum of |E| over the call).
+ * Scope: PackedShamir, n_idx <= 32 and k <= 8 (the fused checked reveal's); beyond either SDA_ERR_UNSUPPORTED.  An
+ * Additive scheme and repeated indices return SDA_ERR_UNSUPPORTED.  All other checks, their order and their statuses
+ * are those of sda_packed_reveal_checked_dev; wrong not 4-byte aligned is SDA_ERR_INVALID_ARGUMENT.  dimension == 0
+ * and n_vectors == 0 return SDA_OK with zero counts and launch nothing.  A failing call writes nothing; the call
+ * drains its stream before it returns; stream ordering and the multi-device rule are those of every `_dev` call.
+ * Two passes: the checked reveal's fused first pass, then, when something is bad and e_max >= 1, one decode pass over
+ * the logged batches (one lane per batch: syndromes, Berlekamp-Massey, root search, Forney).
+ * SDA_CHECK_LOG_CAP applies as in the check: on overflow the decode pass walks every batch, with the same results. */
+sda_status sda_packed_reveal_decoded_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                         const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
+                                         const int64_t* shares, int64_t* out, void* verdict, void* wrong,
+                                         uint64_t* redundancy, uint64_t* radius, uint64_t* bad_batches,
+                                         uint64_t* first_bad, uint64_t* undecoded, uint64_t* blame, void* stream);
+sda_status sda_packed_reveal_decoded32_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                           const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
+                                           const int32_t* shares, int64_t* out, void* verdict, void* wrong,
+                                           uint64_t* redundancy, uint64_t* radius, uint64_t* bad_batches,
+                                           uint64_t* first_bad, uint64_t* undecoded, uint64_t* blame, void* stream);
+/* The same from host share rows, as sda_secret_reconstruct_checked takes them (one vector; verdict: HOST uint16_t [B]
+ * or NULL; wrong: HOST uint32_t [B] or NULL; out: HOST [dimension], required when dimension > 0).  Checks and statuses
+ * are those of sda_secret_reconstruct_checked, ragged rows included, then the scope above. */
+sda_status sda_secret_reconstruct_decoded(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                          const uint64_t* indices, const int64_t* const* share_rows,
+                                          const uint64_t* share_lens, uint64_t n_idx, void* verdict, void* wrong,
+                                          uint64_t* redundancy, uint64_t* radius, uint64_t* bad_batches,
+                                          uint64_t* first_bad, uint64_t* undecoded, uint64_t* blame, int64_t* out);
+/* How the last decoded reveal on this handle that launched something ran (written when it returns SDA_OK; host-side
+ * only; all zeros before): path 1 the first pass alone (nothing bad, or e_max == 0) / 2 the decode pass too; bucket
+ * 8 / 16 / 32 shares; decoded = the batches the decode pass walked (the bad ones, or every batch when the log
+ * overflowed); fixed = the batches whose out it rewrote (E meets the first k + t positions); max_errors = the largest
+ * |E| of the call; overflowed = more bad batches than the log held. */
+sda_status sda_packed_decode_last_launch(sda_engine* h, uint32_t* path, uint32_t* bucket, uint64_t* decoded,
+                                         uint64_t* fixed, uint32_t* max_errors, uint32_t* overflowed);
+
 /* Additive share generation: secrets [dimension], draws [dimension][n-1], out [n][dimension]. */
 sda_status sda_additive_generate_dev(sda_engine* h, int64_t modulus, uint64_t share_count,
                                      const int64_t* secrets, uint64_t dimension,

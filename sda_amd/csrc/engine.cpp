@@ -340,6 +340,7 @@ void sda_engine_destroy(sda_engine* h) {
     sda::free_table(h->gen_tab);
     sda::free_table(h->rev_tab);
     sda::free_table(h->chk_tab);
+    sda::free_table(h->dec_tab);
     if (h->rej_host) (void)hipHostFree(h->rej_host);
     if (h->hs_pin) (void)hipHostFree(h->hs_pin);
     dev_free(h->hs_dev);

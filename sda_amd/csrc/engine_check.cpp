@@ -128,6 +128,50 @@ sda_status run_reveal_checked(sda_engine* h, const sda_sharing_scheme* s, const 
     return SDA_OK;
 }
 
+// What a decoded reveal hands back beside the check's outputs.
+struct DecodeExtra {
+    uint64_t *radius, *undecoded;
+    bool complete() const { return radius && undecoded; }
+};
+
+sda_status decode_scope(uint64_t n_idx, uint64_t k) {
+    if (n_idx > sda::kDecodeMaxShares)
+        return fail(SDA_ERR_UNSUPPORTED, "the decoded reveal takes at most %u clerk shares per batch", sda::kDecodeMaxShares);
+    if (k > sda::kDecodeMaxK)
+        return fail(SDA_ERR_UNSUPPORTED, "the decoded reveal takes at most %u secrets per batch", sda::kDecodeMaxK);
+    return SDA_OK;
+}
+
+// The decoded reveal of a call validated as run_check's and inside decode_scope, on stream st, as packed_decode_plan
+// decides it: the checked reveal's fused first pass, then the decode pass over what it logged.  wrong: device uint32
+// [n_vectors][B] or nullptr.
+sda_status run_reveal_decoded(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedRepairArgs& ra, uint32_t* wrong,
+                              const uint64_t* indices, uint64_t n_idx, Counts* c, uint64_t* undecoded, hipStream_t st) {
+    sda::CheckGeom g;
+    if (sda_status e = prepare(h, s, ra, indices, n_idx, "the decoded reveal needs distinct clerk indices", &g)) return e;
+    const sda::PackedDecodePlan pl = sda::packed_decode_plan(g.n_idx, g.k, g.kt - g.k);
+    if (pl.decode)
+        HIP_TRY(sda::ensure_decode_table(h->dec_tab, indices, g.n_idx, g.k, g.kt - g.k, g.M.p, (uint32_t)s->omega_secrets,
+                                         (uint32_t)s->omega_shares));
+    sda::PackedCheckResult& res = c->res;
+    sda::PackedDecodeResult dres;
+    c->redundancy = pl.redundancy;
+    if (wrong) HIP_TRY(hipMemsetAsync(wrong, 0, ra.n_vectors * g.B * sizeof(uint32_t), st));
+    HIP_TRY(sda::launch_packed_repair(ra, g, st, &res));
+    const bool second = res.bad && pl.decode;
+    if (second)
+        HIP_TRY(sda::launch_packed_decode(ra, wrong, g, static_cast<const uint32_t*>(h->dec_tab.dev), st,
+                                          c->blame.data(), &res, &dres));
+    *undecoded = second ? dres.undecoded : res.bad;
+    h->last.decode.path = second ? sda::kDecodeDecoded : sda::kDecodeFirstPass;
+    h->last.decode.bucket = pl.bucket;
+    h->last.decode.decoded = dres.decoded;
+    h->last.decode.fixed = second ? res.fixed : 0;
+    h->last.decode.max_errors = dres.max_errors;
+    h->last.decode.overflowed = second && res.overflowed ? 1 : 0;
+    return SDA_OK;
+}
+
 // The argument ladder of the four device entry points: sda_packed_reconstruct_dev's checks in its order.
 // additive_clean: an Additive scheme needs every share, so it has no redundancy to check and the call is done with
 // zero counts (the share check); otherwise it is refused (no packed reveal to correct).  need_out: `out` is checked
@@ -183,6 +227,40 @@ sda_status device_form(sda_engine* h, const sda_sharing_scheme* s, uint64_t dime
                               : run_check(h, s, ra, indices, n_idx, &c, pick(h, stream)))
         return e;
     o.commit(c.redundancy, c.res, c.blame.data());
+    return ok();
+}
+
+// Both device forms of the decoded reveal, T the share type: the checked reveal's ladder, then the decoder's scope.
+template <typename T>
+sda_status decoded_device_form(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension, const uint64_t* indices,
+                               uint64_t n_idx, uint64_t n_vectors, const T* shares, int64_t* out, void* verdict,
+                               void* wrong, const CheckOutputs& o, const DecodeExtra& x, void* stream) {
+    if (h && s && !x.complete()) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (h && s && o.complete() && s->kind == SDA_SHARING_ADDITIVE)
+        return fail(SDA_ERR_UNSUPPORTED, "an Additive scheme has no decoded reveal");
+    bool run;
+    const sda_status vs = validate(h, s, dimension, indices, n_idx, n_vectors, shares, static_cast<uint16_t*>(verdict),
+                                   false, true, out, o, stream, &run);
+    if (!run) {
+        if (vs == SDA_OK) {                                 // no batch or no vector: zero counts
+            *x.radius = *o.redundancy / 2;
+            *x.undecoded = 0;
+        }
+        return vs;
+    }
+    if (sda_status e = decode_scope(n_idx, s->secret_count)) return e;
+    if (wrong && (reinterpret_cast<uintptr_t>(wrong) & 3))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "wrong must be 4-byte aligned");
+    sda::PackedRepairArgs ra{{nullptr, nullptr, dimension, n_vectors, static_cast<uint16_t*>(verdict)}, out};
+    if constexpr (sizeof(T) == 4) ra.shares32 = shares; else ra.shares = shares;
+    Counts c(n_idx);
+    uint64_t undecoded = 0;
+    if (sda_status e = run_reveal_decoded(h, s, ra, static_cast<uint32_t*>(wrong), indices, n_idx, &c, &undecoded,
+                                          pick(h, stream)))
+        return e;
+    o.commit(c.redundancy, c.res, c.blame.data());
+    *x.radius = c.redundancy / 2;
+    *x.undecoded = undecoded;
     return ok();
 }
 
@@ -349,6 +427,76 @@ sda_status sda_packed_reveal_checked_last_launch(sda_engine* h, uint32_t* path, 
     *bucket = h->last.repair.bucket;
     *fixed = h->last.repair.fixed;
     *overflowed = h->last.repair.overflowed;
+    return ok();
+}
+
+sda_status sda_packed_reveal_decoded_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                         const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
+                                         const int64_t* shares, int64_t* out, void* verdict, void* wrong,
+                                         uint64_t* redundancy, uint64_t* radius, uint64_t* bad_batches,
+                                         uint64_t* first_bad, uint64_t* undecoded, uint64_t* blame, void* stream) {
+    SDA_ENTRY;
+    return decoded_device_form(h, s, dimension, indices, n_idx, n_vectors, shares, out, verdict, wrong,
+                               CheckOutputs{redundancy, bad_batches, first_bad, blame, n_idx},
+                               DecodeExtra{radius, undecoded}, stream);
+}
+
+sda_status sda_packed_reveal_decoded32_dev(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                           const uint64_t* indices, uint64_t n_idx, uint64_t n_vectors,
+                                           const int32_t* shares, int64_t* out, void* verdict, void* wrong,
+                                           uint64_t* redundancy, uint64_t* radius, uint64_t* bad_batches,
+                                           uint64_t* first_bad, uint64_t* undecoded, uint64_t* blame, void* stream) {
+    SDA_ENTRY;
+    return decoded_device_form(h, s, dimension, indices, n_idx, n_vectors, shares, out, verdict, wrong,
+                               CheckOutputs{redundancy, bad_batches, first_bad, blame, n_idx},
+                               DecodeExtra{radius, undecoded}, stream);
+}
+
+// sda_secret_reconstruct_checked's front; the B `wrong` words travel behind `out` in host_form's extra bytes
+sda_status sda_secret_reconstruct_decoded(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimension,
+                                          const uint64_t* indices, const int64_t* const* rows, const uint64_t* lens,
+                                          uint64_t n_rows, void* verdict, void* wrong, uint64_t* redundancy,
+                                          uint64_t* radius, uint64_t* bad_batches, uint64_t* first_bad,
+                                          uint64_t* undecoded, uint64_t* blame, int64_t* out) {
+    SDA_ENTRY;
+    const CheckOutputs o{redundancy, bad_batches, first_bad, blame, n_rows};
+    if (!h || !s || !o.complete() || !radius || !undecoded || (dimension && !out))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (s->kind == SDA_SHARING_ADDITIVE) return fail(SDA_ERR_UNSUPPORTED, "an Additive scheme has no decoded reveal");
+    const uint64_t k = s->secret_count ? s->secret_count : 1, B = (dimension + k - 1) / k;
+    const size_t out_bytes = rup(dimension * 8), extra = out_bytes + (wrong ? B * 4 : 0);
+    std::vector<char> back(extra);
+    uint64_t und = 0;
+    const sda_status st =
+        host_form(h, s, dimension, indices, rows, lens, n_rows, verdict, false, back.data(), extra, h->last.decode, o,
+                  [&](const int64_t* din, uint16_t* dver, char* dextra, Counts* c) {
+                      if (sda_status e = decode_scope(n_rows, s->secret_count)) return e;
+                      const sda::PackedRepairArgs ra{{din, nullptr, dimension, 1, dver},
+                                                     reinterpret_cast<int64_t*>(dextra)};
+                      return run_reveal_decoded(h, s, ra, wrong ? reinterpret_cast<uint32_t*>(dextra + out_bytes) : nullptr,
+                                                indices, n_rows, c, &und, h->stream);
+                  });
+    if (st != SDA_OK) return st;
+    if (extra) {
+        memcpy(out, back.data(), dimension * 8);
+        if (wrong) memcpy(wrong, back.data() + out_bytes, B * 4);
+    }
+    *radius = *redundancy / 2;
+    *undecoded = und;
+    return st;
+}
+
+sda_status sda_packed_decode_last_launch(sda_engine* h, uint32_t* path, uint32_t* bucket, uint64_t* decoded,
+                                         uint64_t* fixed, uint32_t* max_errors, uint32_t* overflowed) {
+    SDA_ENTRY;
+    if (!h || !path || !bucket || !decoded || !fixed || !max_errors || !overflowed)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    *path = h->last.decode.path;
+    *bucket = h->last.decode.bucket;
+    *decoded = h->last.decode.decoded;
+    *fixed = h->last.decode.fixed;
+    *max_errors = h->last.decode.max_errors;
+    *overflowed = h->last.decode.overflowed;
     return ok();
 }
 

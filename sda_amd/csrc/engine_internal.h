@@ -3,7 +3,8 @@
 //
 //   engine.cpp              handle life cycle, call scope, scratch, scheme helpers, the trait calls on host buffers
 //   engine_dev.cpp          the device-resident (`_dev`) entry points
-//   engine_check.cpp        the packed-Shamir share consistency check and the checked reveal (device and host forms)
+//   engine_check.cpp        the packed-Shamir share consistency check, the checked reveal and the decoded reveal
+//                           (device and host forms)
 //   hbm.cpp                 sda_hbm_*: HBM buffers built from fixed-size physical chunks
 //   engine_codec.cpp        the share payload codec's host side and the snapshot transposition
 //   engine_recipient.cpp    the fused recipient pipeline, sda_recipient_reveal and the recipient job
@@ -59,6 +60,8 @@ struct sda_engine {
     sda::DeviceTable rev_tab;     // packed-Shamir Newton/Lagrange tables (per scheme + clerk set)
     sda::DeviceTable chk_tab;     // share check and checked reveal: parity rows, basis Lagrange rows, inverse weights
                                   // (per scheme + clerk set; sda::ensure_check_table)
+    sda::DeviceTable dec_tab;     // decoded reveal: syndrome rows, points and inverse multipliers (per scheme + clerk
+                                  // set; sda::ensure_decode_table)
     void* chk_buf = nullptr;      // their counters, blame words and bad-batch log (sda::packed_check_buf_bytes())
     size_t chk_buf_bytes = 0;
     void* rep_ver = nullptr;      // checked reveal: verdict words when the caller gives no buffer and something is bad
@@ -98,6 +101,10 @@ struct sda_engine {
         uint32_t path = 0, bucket = 0, overflowed = 0;
         uint64_t fixed = 0;
     };
+    struct DecodeLaunchInfo {
+        uint32_t path = 0, bucket = 0, max_errors = 0, overflowed = 0;
+        uint64_t decoded = 0, fixed = 0;
+    };
     struct Records {
         // sda_chacha_last_launch: how the last mask combine or participant mask on this handle ran; chacha_split:
         // that call split its seeds over the handle's devices (chacha_combine_multi), each recording its own part
@@ -128,6 +135,8 @@ struct sda_engine {
         CheckLaunchInfo check;
         // sda_packed_reveal_checked_last_launch: written when a checked reveal that launched something returns SDA_OK
         RepairLaunchInfo repair;
+        // sda_packed_decode_last_launch: written when a decoded reveal that launched something returns SDA_OK
+        DecodeLaunchInfo decode;
     } last;
     // participant job (sda_participant_job, sda_participant_job_dev): the share rows [n][B] of a call (a tile of the
     // host form) and the Full mask row behind them -- int32 where they fit by construction, else i64

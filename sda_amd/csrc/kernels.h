@@ -10,6 +10,7 @@
 #include "reveal_plan.h"
 #include "check_plan.h"
 #include "repair_plan.h"
+#include "decode_plan.h"
 
 namespace sda {
 
@@ -237,6 +238,23 @@ hipError_t launch_packed_repair(const PackedRepairArgs& a, const CheckGeom& g, h
 // Fills res->fixed, res->overflowed and, with locate, blame_host[n_idx].
 hipError_t launch_packed_repair_fix(const PackedRepairArgs& a, uint16_t* verdict, const CheckGeom& g, bool locate,
                                     bool recompute, hipStream_t s, uint64_t* blame_host, PackedCheckResult* res);
+
+// ---- packed_decode.hip ----
+// The decoded reveal's table of a (scheme, indices) pair with r = n_idx - (k + t) >= 2 inside packed_decode_plan's
+// scope (decode_tables.h gives the layout).  hipErrorInvalidValue for repeated clerk points, as ensure_check_table.
+hipError_t ensure_decode_table(DeviceTable& tab, const uint64_t* indices, uint32_t n_idx, uint32_t k, uint32_t t,
+                               uint32_t p, uint32_t omega_secrets, uint32_t omega_shares);
+struct PackedDecodeResult {
+    uint64_t decoded = 0;     // batches the decode pass walked: the bad ones, or on overflow every batch
+    uint64_t undecoded = 0;   // bad batches left at verdict 0xFFFF
+    uint32_t max_errors = 0;  // the largest error set of the call
+};
+// The decode pass behind launch_packed_repair when it counted res->bad > 0 bad batches into g.cnt, and its wait: every
+// decodable bad batch gets its corrected secrets in a.out, its |E| in a.verdict and its error set in `wrong` (device
+// uint32 [n_vectors][B]; either may be nullptr).  dtab: ensure_decode_table's words.  Fills res->fixed,
+// res->overflowed, *dres and blame_host[n_idx].
+hipError_t launch_packed_decode(const PackedRepairArgs& a, uint32_t* wrong, const CheckGeom& g, const uint32_t* dtab,
+                                hipStream_t s, uint64_t* blame_host, PackedCheckResult* res, PackedDecodeResult* dres);
 
 // ---- codec_decode.hip (share payload codec: sodium.rs:36-41 / :82-88, integer-encoding 1.0 VarInt) ----
 // Host-side plan of the decode: blobs are split into 4 KiB regions aligned to the (16-byte

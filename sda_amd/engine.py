@@ -130,6 +130,13 @@ REPAIR_PATH_FUSED = 1
 REPAIR_PATH_COMPOSED = 2
 RepairLaunch = collections.namedtuple("RepairLaunch", "path bucket fixed overflowed")
 
+# Decoded reveal (sda_packed_reveal_decoded_dev): its counts, sda_packed_decode_last_launch's path codes and record
+DECODE_PATH_FIRST_PASS = 1
+DECODE_PATH_DECODED = 2
+DECODE_UNDECODABLE = 0xFFFF
+ShareDecode = collections.namedtuple("ShareDecode", "redundancy radius bad_batches first_bad undecoded blame")
+DecodeLaunch = collections.namedtuple("DecodeLaunch", "path bucket decoded fixed max_errors overflowed")
+
 # Elements one workgroup of the draws kernel produces (csrc/kernels.h kDrawsTile): the sizes at which
 # sda_draws_dev's grid gains a workgroup
 DRAWS_TILE = 2048
@@ -217,6 +224,16 @@ SIGNATURES = [
     ("sda_secret_reconstruct_checked", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.POINTER(_i64p),
                                              _u64p, C.c_uint64, _vp, _u64p, _u64p, _u64p, _u64p, _i64p]),
     ("sda_packed_reveal_checked_last_launch", _st, [_vp, _u32p, _u32p, _u64p, _u32p]),
+    ("sda_packed_reveal_decoded_dev", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.c_uint64,
+                                            C.c_uint64, _vp, _vp, _vp, _vp, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p,
+                                            _vp]),
+    ("sda_packed_reveal_decoded32_dev", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.c_uint64,
+                                              C.c_uint64, _vp, _vp, _vp, _vp, _u64p, _u64p, _u64p, _u64p, _u64p,
+                                              _u64p, _vp]),
+    ("sda_secret_reconstruct_decoded", _st, [_vp, C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.POINTER(_i64p),
+                                             _u64p, C.c_uint64, _vp, _vp, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p,
+                                             _i64p]),
+    ("sda_packed_decode_last_launch", _st, [_vp, _u32p, _u32p, _u64p, _u64p, _u32p, _u32p]),
     ("sda_additive_generate_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp]),
     ("sda_chacha_mask_combine_dev", _st, [_vp, C.c_int64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
     ("sda_draws_dev", _st, [_vp, _u32p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp]),
@@ -972,6 +989,68 @@ class Engine:
         _check(self.lib.sda_packed_reveal_checked_last_launch(self.h, C.byref(path), C.byref(bucket), C.byref(fixed),
                                                               C.byref(over)))
         return RepairLaunch(int(path.value), int(bucket.value), int(fixed.value), int(over.value))
+
+    # decoded reveal (include/sda_engine.h "decoded reveal"): the checked reveal's arguments plus wrong
+    def _packed_reveal_decoded(self, fn, scheme, dimension, indices, n_vectors, shares_ptr, out_ptr, verdict_ptr,
+                               wrong_ptr, stream):
+        s = scheme.c()
+        idx = _arr(indices, np.uint64)
+        r, rad, bad, first, und = (C.c_uint64() for _ in range(5))
+        blame = np.zeros(max(idx.size, 1), np.uint64)
+        _check(fn(self.h, C.byref(s), dimension, _ptr(idx, _u64p), idx.size, n_vectors, shares_ptr, out_ptr,
+                  verdict_ptr, wrong_ptr, C.byref(r), C.byref(rad), C.byref(bad), C.byref(first), C.byref(und),
+                  _ptr(blame, _u64p), stream))
+        return ShareDecode(int(r.value), int(rad.value), int(bad.value), int(first.value), int(und.value),
+                           [int(x) for x in blame[: idx.size]])
+
+    def packed_reveal_decoded_dev(self, scheme, dimension, indices, n_vectors, shares_ptr, out_ptr,
+                                  verdict_ptr=None, wrong_ptr=None, stream=None):
+        """The canonical reveal of i64 shares [n_vectors][n_idx][B] into out_ptr (device i64 [n_vectors][dimension])
+        with up to radius = redundancy // 2 wrong shares per batch corrected; verdict_ptr: device uint16
+        [n_vectors][B] (|E|, 0xFFFF undecodable) or None; wrong_ptr: device uint32 [n_vectors][B] (the bits of E) or
+        None.  Returns ShareDecode(redundancy, radius, bad_batches, first_bad, undecoded, blame)
+        (sda_packed_reveal_decoded_dev).  Waits for its stream."""
+        return self._packed_reveal_decoded(self.lib.sda_packed_reveal_decoded_dev, scheme, dimension, indices,
+                                           n_vectors, shares_ptr, out_ptr, verdict_ptr, wrong_ptr, stream)
+
+    def packed_reveal_decoded32_dev(self, scheme, dimension, indices, n_vectors, shares_ptr, out_ptr,
+                                    verdict_ptr=None, wrong_ptr=None, stream=None):
+        """packed_reveal_decoded_dev over int32 shares (sda_packed_reveal_decoded32_dev)."""
+        return self._packed_reveal_decoded(self.lib.sda_packed_reveal_decoded32_dev, scheme, dimension, indices,
+                                           n_vectors, shares_ptr, out_ptr, verdict_ptr, wrong_ptr, stream)
+
+    def secret_reconstruct_decoded(self, scheme, dimension: int, indexed_shares, want_verdict=True, want_wrong=True):
+        """The decoded reveal of host share rows, as secret_reconstruct_checked takes them
+        (sda_secret_reconstruct_decoded): (secrets, ShareDecode, verdict, wrong) with verdict a uint16 and wrong a
+        uint32 array of one entry per batch, or None."""
+        s = scheme.c()
+        idx = _arr([i for i, _ in indexed_shares], np.uint64)
+        arrs, ptrs, lens, n = _rows([r for _, r in indexed_shares])
+        k = max(int(getattr(scheme, "secret_count", 1) or 1), 1)
+        nb = (dimension + k - 1) // k
+        verdict = np.full(max(nb, 1), 0xAAAA, np.uint16) if want_verdict else None
+        wrong = np.full(max(nb, 1), 0xAAAAAAAA, np.uint32) if want_wrong else None
+        out = np.zeros(max(dimension, 1), np.int64)
+        r, rad, bad, first, und = (C.c_uint64() for _ in range(5))
+        blame = np.zeros(max(n, 1), np.uint64)
+        _check(self.lib.sda_secret_reconstruct_decoded(self.h, C.byref(s), dimension, _ptr(idx, _u64p), ptrs, lens, n,
+                                                       verdict.ctypes.data if want_verdict else None,
+                                                       wrong.ctypes.data if want_wrong else None, C.byref(r),
+                                                       C.byref(rad), C.byref(bad), C.byref(first), C.byref(und),
+                                                       _ptr(blame, _u64p), _ptr(out)))
+        res = ShareDecode(int(r.value), int(rad.value), int(bad.value), int(first.value), int(und.value),
+                          [int(x) for x in blame[:n]])
+        return (out[:dimension], res, verdict[:nb] if want_verdict else None, wrong[:nb] if want_wrong else None)
+
+    def packed_decode_last_launch(self):
+        """DecodeLaunch(path, bucket, decoded, fixed, max_errors, overflowed) of the handle's last decoded reveal that
+        launched something (sda_packed_decode_last_launch): all zeros before the first."""
+        path, bucket, over, mx = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        decoded, fixed = C.c_uint64(), C.c_uint64()
+        _check(self.lib.sda_packed_decode_last_launch(self.h, C.byref(path), C.byref(bucket), C.byref(decoded),
+                                                      C.byref(fixed), C.byref(mx), C.byref(over)))
+        return DecodeLaunch(int(path.value), int(bucket.value), int(decoded.value), int(fixed.value), int(mx.value),
+                            int(over.value))
 
     def packed_generate_keyed_dev(self, scheme, secrets_ptr, dimension, n_vectors, key, stream_id, out_ptr, mode,
                                   first_batch=0, stream=None):
