@@ -13,12 +13,12 @@ LIB     ?= sda_amd/libsda_engine.so
 # share-gen objects, one per (n+1, k+t+1): the n+1 = 81 instantiations dominate the build, so they compile in parallel
 GEN_PARTS    := 3_2 9_2 9_4 9_8 27_2 27_4 27_8 27_16 81_2 81_4 81_8 81_16 81_32 81_64
 REVEAL_PARTS := 8 16 32 64 96
-PLAIN   := combine elementwise chacha codec_decode codec_encode snapshot packed_wide packed_check packed_repair packed_decode draws additive_keyed mask_keyed recipient_job
+PLAIN   := combine elementwise chacha codec_decode codec_encode snapshot packed_wide packed_check packed_repair packed_decode draws additive_keyed mask_keyed recipient_job recipient_repair
 HOST    := engine engine_dev engine_check hbm engine_codec engine_recipient engine_participant engine_host
 OBJS    := $(patsubst %,$(OBJDIR)/%.o,$(PLAIN)) $(patsubst %,$(OBJDIR)/%.o,$(HOST)) \
            $(OBJDIR)/packed_gen.o $(patsubst %,$(OBJDIR)/packed_gen_%.o,$(GEN_PARTS)) \
            $(OBJDIR)/packed_reveal.o $(patsubst %,$(OBJDIR)/packed_reveal_%.o,$(REVEAL_PARTS))
-HDRS    := $(CSRC)/packed_common.h $(CSRC)/kernels.h $(CSRC)/reveal_plan.h $(CSRC)/check_plan.h $(CSRC)/repair_plan.h $(CSRC)/decode_plan.h $(CSRC)/decode_tables.h $(CSRC)/decode_core.h $(CSRC)/check_common.h $(CSRC)/check_launch.h $(CSRC)/modarith.h $(CSRC)/xcd.h $(CSRC)/draws_common.h $(CSRC)/codec_common.h include/sda_engine.h
+HDRS    := $(CSRC)/packed_common.h $(CSRC)/kernels.h $(CSRC)/reveal_plan.h $(CSRC)/check_plan.h $(CSRC)/repair_plan.h $(CSRC)/decode_plan.h $(CSRC)/decode_tables.h $(CSRC)/decode_core.h $(CSRC)/check_common.h $(CSRC)/check_launch.h $(CSRC)/repair_body.h $(CSRC)/modarith.h $(CSRC)/xcd.h $(CSRC)/draws_common.h $(CSRC)/codec_common.h include/sda_engine.h
 
 all: $(LIB) oracle
 

@@ -332,6 +332,33 @@ extern "C" {
     pub fn sda_recipient_job_last_launch(h: *mut SdaEngine, mask_route: *mut u32, share_route: *mut u32,
                                          seeds_decoded: *mut u32) -> SdaStatus;
 
+    // ---- robust recipient job: the same calls over the decoded reveal (wrong clerk results corrected) ----
+    pub fn sda_recipient_job_decoded(h: *mut SdaEngine, ms: *const SdaMaskingScheme, mask_blobs: *const *const u8,
+                                     mask_lens: *const u64, n_masks: u64, ss: *const SdaSharingScheme,
+                                     dimension: u64, indices: *const u64, clerk_blobs: *const *const u8,
+                                     clerk_lens: *const u64, n_idx: u64, output_modulus: i64, out: *mut i64,
+                                     out_cap: u64, out_len: *mut u64, verdict: *mut c_void, wrong: *mut c_void,
+                                     redundancy: *mut u64, radius: *mut u64, bad_batches: *mut u64,
+                                     first_bad: *mut u64, undecoded: *mut u64, blame: *mut u64) -> SdaStatus;
+    pub fn sda_recipient_job_decoded_dev(h: *mut SdaEngine, ms: *const SdaMaskingScheme, mask: *const i64,
+                                         mask_len: u64, seed_bytes: *const u8, seed_off: *const u64, n_seeds: u64,
+                                         ss: *const SdaSharingScheme, dimension: u64, indices: *const u64,
+                                         clerk_bytes: *const u8, clerk_off: *const u64, n_idx: u64,
+                                         output_modulus: i64, out: *mut i64, out_cap: u64, out_len: *mut u64,
+                                         verdict: *mut c_void, wrong: *mut c_void, redundancy: *mut u64,
+                                         radius: *mut u64, bad_batches: *mut u64, first_bad: *mut u64,
+                                         undecoded: *mut u64, blame: *mut u64, stream: *mut c_void) -> SdaStatus;
+    pub fn sda_recipient_reveal_decoded_dev(h: *mut SdaEngine, ms: *const SdaMaskingScheme, mask_in: *const c_void,
+                                            n_masks: u64, mask_width: u64, ss: *const SdaSharingScheme,
+                                            dimension: u64, indices: *const u64, shares: *const i64, n_idx: u64,
+                                            share_len: u64, output_modulus: i64, out: *mut i64, out_cap: u64,
+                                            out_len: *mut u64, verdict: *mut c_void, wrong: *mut c_void,
+                                            redundancy: *mut u64, radius: *mut u64, bad_batches: *mut u64,
+                                            first_bad: *mut u64, undecoded: *mut u64, blame: *mut u64,
+                                            stream: *mut c_void) -> SdaStatus;
+    pub fn sda_recipient_decoded_last_launch(h: *mut SdaEngine, unmask_route: *mut u32, reveal_runs: *mut u32,
+                                             compact: *mut u32) -> SdaStatus;
+
     // ---- participant job: mask, mask payload, shares and every clerk payload in one call ----
     pub fn sda_full_mask_keyed_dev(h: *mut SdaEngine, modulus: i64, secrets: *const i64, dimension: u64,
                                    key: *const u32, stream_id: u32, first: u64, masked_out: *mut i64,

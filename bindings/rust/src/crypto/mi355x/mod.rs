@@ -369,6 +369,50 @@ impl GpuReconstructor {
     }
 }
 
+/// The recipient's reveal (receive.rs:98-157 + positive()) from the opened payloads with wrong clerk results
+/// corrected (sda_recipient_job_decoded): `mask_blobs` are the participations' opened mask payloads, `clerk_blobs`
+/// the (clerk index, opened result) pairs.  Returns the aggregate in [0, p) and what the decoder found; a batch
+/// whose verdict is 0xFFFF is not to be trusted.  PackedShamir with at most 32 results and k <= 8, and both the
+/// masking modulus and `output_modulus` equal to the sharing prime.
+pub fn receive_decoded(dev: &Device, masking: &LinearMaskingScheme, sharing: &LinearSecretSharingScheme,
+                       dimension: usize, mask_blobs: &[Vec<u8>], clerk_blobs: &[(usize, Vec<u8>)],
+                       output_modulus: i64) -> SdaClientResult<(Vec<i64>, ShareDecode)> {
+    let (ms, ss) = (masking_c(masking), sharing_c(sharing));
+    let mptrs: Vec<*const u8> = mask_blobs.iter().map(|b| b.as_ptr()).collect();
+    let mlens: Vec<u64> = mask_blobs.iter().map(|b| b.len() as u64).collect();
+    let idx: Vec<u64> = clerk_blobs.iter().map(|&(i, _)| i as u64).collect();
+    let cptrs: Vec<*const u8> = clerk_blobs.iter().map(|&(_, ref b)| b.as_ptr()).collect();
+    let clens: Vec<u64> = clerk_blobs.iter().map(|&(_, ref b)| b.len() as u64).collect();
+    let k = std::cmp::max(ss.secret_count as usize, 1);
+    let batches = (dimension + k - 1) / k;
+    let mut out = vec![0_i64; std::cmp::max(dimension, 1)];
+    let mut verdict = vec![0_u16; std::cmp::max(batches, 1)];
+    let mut wrong = vec![0_u32; std::cmp::max(batches, 1)];
+    let mut blame = vec![0_u64; std::cmp::max(idx.len(), 1)];
+    let (mut out_len, mut r, mut rad, mut bad, mut first, mut und) = (0_u64, 0_u64, 0_u64, 0_u64, 0_u64, 0_u64);
+    dev.call(|h| unsafe {
+        sda_recipient_job_decoded(h, &ms, mptrs.as_ptr(), mlens.as_ptr(), mptrs.len() as u64, &ss, dimension as u64,
+                                  idx.as_ptr(), cptrs.as_ptr(), clens.as_ptr(), cptrs.len() as u64, output_modulus,
+                                  out.as_mut_ptr(), dimension as u64, &mut out_len,
+                                  verdict.as_mut_ptr() as *mut c_void, wrong.as_mut_ptr() as *mut c_void, &mut r,
+                                  &mut rad, &mut bad, &mut first, &mut und, blame.as_mut_ptr())
+    })?;
+    out.truncate(out_len as usize);
+    verdict.truncate(batches);
+    wrong.truncate(batches);
+    blame.truncate(idx.len());
+    Ok((out, ShareDecode {
+        redundancy: r as usize,
+        radius: rad as usize,
+        bad_batches: bad as usize,
+        first_bad: if first == u64::max_value() { None } else { Some(first as usize) },
+        undecoded: und as usize,
+        blame: blame.into_iter().map(|x| x as usize).collect(),
+        verdict: verdict,
+        wrong: wrong,
+    }))
+}
+
 impl SecretReconstructor for GpuReconstructor {
     fn reconstruct(&self, indexed_shares: &Vec<(usize, Vec<Share>)>) -> SdaClientResult<Vec<Secret>> {
         let idx: Vec<u64> = indexed_shares.iter().map(|&(i, _)| i as u64).collect();

@@ -1072,6 +1072,97 @@ sda_status sda_recipient_job_dev(sda_engine* h, const sda_masking_scheme* ms,
 sda_status sda_recipient_job_last_launch(sda_engine* h, uint32_t* mask_route, uint32_t* share_route,
                                          uint32_t* seeds_decoded);
 
+/* ---------------- robust recipient job: the recipient pipeline over the decoded reveal ----------------
+ * The recipient job with sda_packed_reveal_decoded_dev as its reveal: up to e_max = floor(r / 2) wrong clerk results
+ * per batch (r = n_idx - (k + t); truncated to a wrong value, stale, reduced by another modulus, ...) are located,
+ * blamed on their clerks and corrected inside the one call, and a batch with more is flagged, never returned as
+ * if it were right.  sda_recipient_job itself reveals from whatever it is given and returns SDA_OK.
+ *
+ * CONTRACT.  With p = ss->modulus, B = ceil(dimension / k) and clerk row i = sda_varint_decode(clerk_blobs[i]) read
+ * over [0, B) (sda_recipient_reveal_decoded_dev: row i of `shares`), the call reveals what
+ * sda_secret_reconstruct_decoded reveals from those rows -- the secrets s, verdict, wrong, *redundancy, *radius,
+ * *bad_batches, *first_bad, *undecoded and blame[n_idx], bit for bit -- and returns
+ *     out[i] = (s_i - mask_i) mod p  in [0, p),   i < dimension,
+ * where mask is the combined mask exactly as sda_recipient_job / sda_recipient_job_dev / sda_recipient_reveal_dev
+ * builds or takes it (no masking: mask_i = 0) and every i64 mask value is reduced exactly.  The output is DEFINED as
+ * that residue, not through the reference's wrapping `-` (full.rs:58-66, chacha.rs:83-91) followed by positive(): a
+ * corrected batch has no counterpart in the reference.  For every mask an engine call produces (values in (-p, p))
+ * the two agree.  Consequences:
+ *   - with no more than e_max wrong results in any batch, out equals sda_recipient_job's output on the uncorrupted
+ *     payloads, *undecoded == 0, and blame counts the batches in which each clerk was wrong;
+ *   - on consistent results, out equals sda_recipient_job's output on the same payloads, in either mode, and every
+ *     count is zero.
+ * SCOPE.  Defined only where the decoded reveal's canonical output is the whole answer; everything else is refused
+ * with SDA_ERR_UNSUPPORTED on the schemes alone, right after the NULL checks and before any data is looked at:
+ *   an Additive sharing scheme ("Additive"); k > 8 ("secrets per batch"); output_modulus != p ("output_modulus");
+ *   Full or ChaCha masking with |ms->modulus| != p ("masking modulus").
+ * After them come sda_recipient_job's own checks in its order, with its statuses and messages (the mask combine's,
+ * the scheme's, the count pass's, index out of bounds, Not enough shares), except that more than 32 clerk results
+ * are refused (SDA_ERR_UNSUPPORTED) where the job refuses more than 1023.  Repeated clerk indices are refused
+ * (SDA_ERR_UNSUPPORTED) when the check table is built: after the length and out_cap checks, before anything is
+ * written.  dimension == 0 returns SDA_OK, *out_len = 0 and sda_secret_reconstruct_decoded's counts for it
+ * (*redundancy = max(n_idx, k + t) - (k + t), *first_bad = UINT64_MAX, the rest 0) and launches nothing; r == 0 and
+ * r == 1 behave as the decoded reveal does (nothing is correctable, a bad batch is flagged 0xFFFF and undecoded).
+ * A failing call writes nothing to out, verdict, wrong or any host output and leaves every *_last_launch record of
+ * the handle as it was.  A multi-device handle behaves as in sda_recipient_job.
+ *
+ * verdict: uint16 [B] or NULL, wrong: uint32 [B] or NULL, independently; both as sda_packed_reveal_decoded_dev
+ * writes them for one vector.  redundancy, radius, bad_batches, first_bad and undecoded may not be NULL, nor blame
+ * when n_idx > 0.  The reused code fills sda_packed_decode_last_launch, sda_codec_last_launch,
+ * sda_chacha_last_launch, sda_combine_last_launch, sda_recipient_last_launch (reveal_mode 2; unmask_launches counts
+ * the separate unmask passes, 0 on routes 0 and 1 below) and sda_recipient_job_last_launch as it does today.
+ *
+ * ChaCha masking: the mask combine is queued ahead of the reveal, whose write-back reads the finished mask.  Should
+ * the combine report rejected draws (probability about 2^-33 a draw at these moduli), the mask is fixed and the
+ * reveal passes run again over the same inputs.
+ * Knobs, read per call: SDA_RECIPIENT_FUSE_UNMASK=0 runs the plain first pass into scratch and unmasks in a pass of
+ * its own (route 2); SDA_RECIPIENT_REDO=1 takes the rerun branch of a ChaCha call as if its mask had changed. */
+
+/* Host form: sda_recipient_job's arguments without `mode`; verdict and wrong are HOST buffers. */
+sda_status
+sda_recipient_job_decoded(sda_engine* h, const sda_masking_scheme* ms,
+                          const uint8_t* const* mask_blobs, const uint64_t* mask_lens, uint64_t n_masks,
+                          const sda_sharing_scheme* ss, uint64_t dimension, const uint64_t* indices,
+                          const uint8_t* const* clerk_blobs, const uint64_t* clerk_lens, uint64_t n_idx,
+                          int64_t output_modulus, int64_t* out, uint64_t out_cap, uint64_t* out_len,
+                          void* verdict, void* wrong, uint64_t* redundancy, uint64_t* radius,
+                          uint64_t* bad_batches, uint64_t* first_bad, uint64_t* undecoded, uint64_t* blame);
+
+/* Device form: sda_recipient_job_dev's arguments without `mode`; verdict and wrong are DEVICE buffers (wrong 4-byte
+ * aligned, else SDA_ERR_INVALID_ARGUMENT).  The call drains its stream before returning: it returns counts. */
+sda_status
+sda_recipient_job_decoded_dev(sda_engine* h, const sda_masking_scheme* ms,
+                              const int64_t* mask, uint64_t mask_len,
+                              const uint8_t* seed_bytes, const uint64_t* seed_off, uint64_t n_seeds,
+                              const sda_sharing_scheme* ss, uint64_t dimension, const uint64_t* indices,
+                              const uint8_t* clerk_bytes, const uint64_t* clerk_off, uint64_t n_idx,
+                              int64_t output_modulus, int64_t* out, uint64_t out_cap, uint64_t* out_len,
+                              void* verdict, void* wrong, uint64_t* redundancy, uint64_t* radius,
+                              uint64_t* bad_batches, uint64_t* first_bad, uint64_t* undecoded, uint64_t* blame,
+                              void* stream);
+
+/* The clerk results as device i64 rows [n_idx][share_len]: sda_recipient_reveal_dev's arguments without `mode`, the
+ * outputs of the device form above.  Drains its stream before returning. */
+sda_status sda_recipient_reveal_decoded_dev(sda_engine* h, const sda_masking_scheme* ms, const void* mask_in,
+                                            uint64_t n_masks, uint64_t mask_width, const sda_sharing_scheme* ss,
+                                            uint64_t dimension, const uint64_t* indices, const int64_t* shares,
+                                            uint64_t n_idx, uint64_t share_len, int64_t output_modulus,
+                                            int64_t* out, uint64_t out_cap, uint64_t* out_len,
+                                            void* verdict, void* wrong, uint64_t* redundancy, uint64_t* radius,
+                                            uint64_t* bad_batches, uint64_t* first_bad, uint64_t* undecoded,
+                                            uint64_t* blame, void* stream);
+
+/* Diagnostic (read-only): how the handle's most recent robust recipient call ran.  Written when such a call returns
+ * SDA_OK with a non-empty output, as sda_recipient_last_launch is; before any such call every field is 0.
+ *   unmask_route  0  no masking: the reveal wrote out itself
+ *                 1  the mask subtracted in the first pass's write-back (recipient_repair_kernel)
+ *                 2  a separate unmask pass behind the plain first pass (SDA_RECIPIENT_FUSE_UNMASK=0)
+ *   reveal_runs   1, or 2 when the reveal passes ran again behind a ChaCha mask that changed
+ *   compact       as in sda_recipient_last_launch: the clerk rows were longer than B and compacted first
+ * A host-side record: nothing is waited for or copied.  No pointer may be NULL. */
+sda_status sda_recipient_decoded_last_launch(sda_engine* h, uint32_t* unmask_route, uint32_t* reveal_runs,
+                                             uint32_t* compact);
+
 /* Synthetic benchmark input: dst[r*cols + c] = lo + splitmix64(seed, r, c) % (hi - lo). */
 sda_status sda_synth_fill_dev(sda_engine* h, int64_t* dst, uint64_t rows, uint64_t cols,
                               uint64_t seed, int64_t lo, int64_t hi, void* stream);

@@ -145,8 +145,13 @@ sda_status decode_scope(uint64_t n_idx, uint64_t k) {
 // The decoded reveal of a call validated as run_check's and inside decode_scope, on stream st, as packed_decode_plan
 // decides it: the checked reveal's fused first pass, then the decode pass over what it logged.  wrong: device uint32
 // [n_vectors][B] or nullptr.
+// mask (device, `dimension` i64 values; the recipient pipeline's call, one vector of i64 rows): out holds
+// (secret - mask) mod p instead of the secrets -- subtracted in the first pass's write-back, or, with `unfused`
+// (scratch of `dimension` values), by launch_recipient_unmask behind the plain first pass.  The decode pass corrects a
+// residue by a difference mod p, so it runs behind either as it is.
 sda_status run_reveal_decoded(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedRepairArgs& ra, uint32_t* wrong,
-                              const uint64_t* indices, uint64_t n_idx, Counts* c, uint64_t* undecoded, hipStream_t st) {
+                              const uint64_t* indices, uint64_t n_idx, Counts* c, uint64_t* undecoded, hipStream_t st,
+                              const int64_t* mask = nullptr, int64_t* unfused = nullptr) {
     sda::CheckGeom g;
     if (sda_status e = prepare(h, s, ra, indices, n_idx, "the decoded reveal needs distinct clerk indices", &g)) return e;
     const sda::PackedDecodePlan pl = sda::packed_decode_plan(g.n_idx, g.k, g.kt - g.k);
@@ -157,7 +162,16 @@ sda_status run_reveal_decoded(sda_engine* h, const sda_sharing_scheme* s, const 
     sda::PackedDecodeResult dres;
     c->redundancy = pl.redundancy;
     if (wrong) HIP_TRY(hipMemsetAsync(wrong, 0, ra.n_vectors * g.B * sizeof(uint32_t), st));
-    HIP_TRY(sda::launch_packed_repair(ra, g, st, &res));
+    if (!mask) {
+        HIP_TRY(sda::launch_packed_repair(ra, g, st, &res));
+    } else if (!unfused) {
+        HIP_TRY(sda::launch_recipient_repair(ra, mask, g, st, &res));
+    } else {
+        sda::PackedRepairArgs plain = ra;
+        plain.out = unfused;
+        HIP_TRY(sda::launch_packed_repair(plain, g, st, &res));
+        HIP_TRY(sda::launch_recipient_unmask(unfused, mask, ra.dimension, g.M, ra.out, st));
+    }
     const bool second = res.bad && pl.decode;
     if (second)
         HIP_TRY(sda::launch_packed_decode(ra, wrong, g, static_cast<const uint32_t*>(h->dec_tab.dev), st,
@@ -333,6 +347,20 @@ sda_status host_form(sda_engine* h, const sda_sharing_scheme* s, uint64_t dimens
 }
 
 }  // namespace
+
+sda_status sda_host::reveal_decoded_masked(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedRepairArgs& ra,
+                                           const int64_t* mask, int64_t* unfused, const uint64_t* indices,
+                                           uint64_t n_idx, DecodedReveal* d, hipStream_t st) {
+    Counts c(n_idx);
+    uint64_t undecoded = 0;
+    if (sda_status e = run_reveal_decoded(h, s, ra, d->wrong, indices, n_idx, &c, &undecoded, st, mask, unfused)) return e;
+    d->redundancy = c.redundancy;
+    d->bad_batches = c.res.bad;
+    d->first_bad = c.res.first_bad;
+    d->undecoded = undecoded;
+    d->blame = c.blame;
+    return SDA_OK;
+}
 
 extern "C" {
 

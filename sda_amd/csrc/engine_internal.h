@@ -7,7 +7,8 @@
 //                           (device and host forms)
 //   hbm.cpp                 sda_hbm_*: HBM buffers built from fixed-size physical chunks
 //   engine_codec.cpp        the share payload codec's host side and the snapshot transposition
-//   engine_recipient.cpp    the fused recipient pipeline, sda_recipient_reveal and the recipient job
+//   engine_recipient.cpp    the fused recipient pipeline, sda_recipient_reveal, the recipient job and their robust
+//                           forms over the decoded reveal
 //   engine_participant.cpp  the participant pipeline's steps, sda_participant_share*_dev and the participant job
 //   engine_host.cpp         the streaming, multi-device host path (RCCL loaded at run time)
 //
@@ -83,6 +84,9 @@ struct sda_engine {
     struct RecipientLaunchInfo {
         uint32_t mask_kind = 0, reveal_mode = 0, fell_back = 0, compact = 0, unmask_launches = 0;
     };
+    struct RecipientDecodedLaunchInfo {
+        uint32_t unmask_route = 0, reveal_runs = 0, compact = 0;
+    };
     struct ParticipantLaunchInfo {
         uint32_t mask_route = 0, share_route = 0, passes = 0;
     };
@@ -127,6 +131,9 @@ struct sda_engine {
         // `recipient` is; sda_participant_job_last_launch: written when a participant job of dimension > 0 returns SDA_OK
         RecipientJobLaunchInfo recipient_job;
         ParticipantJobLaunchInfo participant_job;
+        // sda_recipient_decoded_last_launch: how the last robust recipient call (sda_recipient_job_decoded and its
+        // device forms) unmasked and how often its reveal passes ran, written as `recipient` is
+        RecipientDecodedLaunchInfo recipient_decoded;
         // sda_packed_keyed_last_launch: how the last keyed packed launch on this handle got its draws -- 0 none yet,
         // 1 made in the share kernels, 2 staged through keyed_draws -- and the draw bytes that crossed HBM
         uint32_t keyed_path = 0;
@@ -294,6 +301,24 @@ sda_status packed_generate(sda_engine* h, const sda_sharing_scheme* s, sda::Pack
 sda_status packed_reveal(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedRevealArgs& ra,
                          const uint64_t* indices, uint64_t n_idx, int32_t mode, hipStream_t st,
                          bool* refused = nullptr);
+
+// ---------------- decoded reveal inside the recipient pipeline (engine_check.cpp) ----------------
+// What a robust recipient call asks of the decoded reveal and gets back from it: the device buffers of its per-batch
+// words (either may be nullptr), then sda_packed_reveal_decoded_dev's counts of the run.
+struct DecodedReveal {
+    uint16_t* verdict = nullptr;  // device [B]
+    uint32_t* wrong = nullptr;    // device [B], 4-byte aligned
+    uint64_t redundancy = 0, bad_batches = 0, first_bad = UINT64_MAX, undecoded = 0;
+    std::vector<uint64_t> blame;  // [n_idx]
+};
+// The decoded reveal of one vector of i64 clerk rows (PackedShamir, k + t <= n_idx <= 32, k <= 8, at least one
+// batch) with the same table caches, counter block and records as sda_packed_reveal_decoded_dev, and its wait.
+// mask == nullptr: ra.out holds the secrets.  Else ra.out[i] = (secret_i - mask[i]) mod p: subtracted in the first
+// pass's write-back, or with `unfused` (device scratch of `dimension` values) by a pass of its own behind the plain
+// first pass.  Repeated clerk indices are refused before anything is queued.
+sda_status reveal_decoded_masked(sda_engine* h, const sda_sharing_scheme* s, const sda::PackedRepairArgs& ra,
+                                 const int64_t* mask, int64_t* unfused, const uint64_t* indices, uint64_t n_idx,
+                                 DecodedReveal* d, hipStream_t st);
 
 // ---------------- payload encoder (engine_codec.cpp) ----------------
 // rows x len values of [rows][stride] device rows (T: int64_t or int32_t) encoded back to back into dst;

@@ -1,5 +1,6 @@
 // engine_recipient.cpp -- the fused recipient pipeline of the C ABI (include/sda_engine.h):
-// sda_recipient_reveal and the recipient job, on device-resident inputs and on host ones.
+// sda_recipient_reveal and the recipient job, on device-resident inputs and on host ones, and the robust forms of
+// both, which reveal with the decoded reveal (engine_check.cpp) and unmask in its write-back.
 #include "engine_internal.h"
 
 using namespace sda_host;
@@ -81,12 +82,16 @@ struct RecipientCall {
     hipStream_t st;
     MaskSource mask;
     ShareSource shares;
+    // a robust call (sda_recipient_*_decoded*): the packed branch reveals with the decoded reveal into `out` itself and
+    // leaves its counts here; `mode` is not read
+    DecodedReveal* dec = nullptr;
 };
 
 // A pipeline call that returned SDA_OK: its output length, and the record the caller commits when its call succeeds.
 struct RecipientDone {
     uint64_t len = 0;
     sda_engine::RecipientLaunchInfo rec;
+    sda_engine::RecipientDecodedLaunchInfo dec;             // a robust call's own record
 };
 
 // Scratch in h->pipe: [mask | masked | compacted shares], carved once per call -- before the clerk payloads of an
@@ -168,7 +173,8 @@ sda_status recipient_pipeline(sda_engine* h, const RecipientCall& c, RecipientDo
         if (sda_status e = fold_checks(D, ss->modulus)) return e;
     } else if (ss->kind == SDA_SHARING_PACKED_SHAMIR) {
         if (sda_status e = check_packed(ss)) return e;
-        if (c.mode != SDA_REVEAL_EXACT && c.mode != SDA_REVEAL_CANONICAL) return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
+        if (!c.dec && c.mode != SDA_REVEAL_EXACT && c.mode != SDA_REVEAL_CANONICAL)
+            return fail(SDA_ERR_INVALID_ARGUMENT, "bad mode");
         const uint64_t B = (dimension + ss->secret_count - 1) / ss->secret_count;
         if (blobs) {
             // the count pass's one wait supplies the lengths of the reference's checks: ragged rows are read over
@@ -189,6 +195,9 @@ sda_status recipient_pipeline(sda_engine* h, const RecipientCall& c, RecipientDo
             if (!enough) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");  // packed_shamir.rs:75
             if (n_idx > sda::kRevealMaxShares)
                 return fail(SDA_ERR_UNSUPPORTED, "more than %u clerk shares per batch", sda::kRevealMaxShares);
+            if (c.dec && n_idx > sda::kDecodeMaxShares)
+                return fail(SDA_ERR_UNSUPPORTED, "the decoded reveal takes at most %u clerk shares per batch",
+                            sda::kDecodeMaxShares);
         }
         D = dimension;
     } else {
@@ -206,8 +215,13 @@ sda_status recipient_pipeline(sda_engine* h, const RecipientCall& c, RecipientDo
     const bool packed = ss->kind == SDA_SHARING_PACKED_SHAMIR;
     const uint64_t B = packed ? (dimension + ss->secret_count - 1) / ss->secret_count : 0;
     const bool compact = packed && stride != B;
+    // A robust call writes c.out from the reveal itself; only its unfused route (SDA_RECIPIENT_FUSE_UNMASK=0, read
+    // per call) parks the secrets in `masked` first.
+    const char* fuse = getenv("SDA_RECIPIENT_FUSE_UNMASK");
+    const bool masked_call = ms->kind != SDA_MASKING_NONE;
+    const bool unfused = c.dec && masked_call && fuse && strcmp(fuse, "0") == 0;
     if (!sc.masked)                                         // (a payload job's Additive reconstruction has run)
-        if (sda_status e = sc.carve(h, D, D, compact ? n_idx * B * 8 : 0)) return e;
+        if (sda_status e = sc.carve(h, c.dec && !unfused ? 0 : D, D, compact ? n_idx * B * 8 : 0)) return e;
     sda_engine::RecipientLaunchInfo& rec = done->rec;
     rec.mask_kind = c.mask.multi_combined ? 4 : ms->kind == SDA_MASKING_NONE ? 1 : ms->kind == SDA_MASKING_FULL ? 2 : 3;
     rec.compact = compact;
@@ -242,6 +256,32 @@ sda_status recipient_pipeline(sda_engine* h, const RecipientCall& c, RecipientDo
         if (compact) {                                      // batched.rs:83-85 reads [clerk][0..B)
             HIP_TRY(hipMemcpy2DAsync(sc.compact, B * 8, rows, stride * 8, B * 8, n_idx, hipMemcpyDeviceToDevice, st));
             rows = sc.compact;
+        }
+        if (c.dec) {
+            // The decoded reveal (engine_check.cpp) in place of the packed reveal, the mask subtracted in its first
+            // pass's write-back: the scope checks have made both moduli the sharing prime, so the output is the one
+            // residue (secret - mask) mod p, and the decode pass's correction mod p commutes with that subtraction.
+            // The mask combine is queued ahead on the same stream.  A ChaCha mask that turns out to have had rejected
+            // draws is fixed (chacha_combine_end) and the reveal passes run again over the same inputs.
+            const sda::PackedRepairArgs da{{rows, nullptr, dimension, 1, c.dec->verdict}, c.out};
+            const int64_t* m = masked_call ? mask : nullptr;
+            int64_t* park = unfused ? sc.masked : nullptr;
+            if (sda_status e = reveal_decoded_masked(h, ss, da, m, park, c.indices, n_idx, c.dec, st)) return e;
+            done->dec = {masked_call ? (unfused ? 2u : 1u) : 0u, 1u, compact ? 1u : 0u};
+            if (pc.pending) {
+                bool changed = false;                       // (the reveal's own wait has drained the stream)
+                if (sda_status e = chacha_combine_end(h, pc, st, &changed)) return e;
+                const char* redo = getenv("SDA_RECIPIENT_REDO");
+                if (changed || (redo && atoi(redo) == 1)) {
+                    if (sda_status e = reveal_decoded_masked(h, ss, da, m, park, c.indices, n_idx, c.dec, st)) return e;
+                    done->dec.reveal_runs = 2;
+                }
+            }
+            if (unfused) HIP_TRY(hipStreamSynchronize(st)); // the unmask pass may still run: the call returns counts
+            rec.reveal_mode = 2;
+            rec.unmask_launches = unfused ? done->dec.reveal_runs : 0;
+            done->len = D;
+            return SDA_OK;
         }
         sda::PackedRevealArgs ra{rows, dimension, 1, sc.masked};
         // The output is positive(unmask(reveal)).  When the masking modulus (or no mask) and output_modulus are
@@ -286,6 +326,7 @@ sda_status recipient_dev_call(sda_engine* h, const RecipientCall& c, uint64_t* o
     RecipientDone done;
     if (sda_status e = recipient_pipeline(h, c, &done)) return e;
     if (done.len) h->last.recipient = done.rec;
+    if (done.len && c.dec) h->last.recipient_decoded = done.dec;
     *out_len = done.len;
     return ok();
 }
@@ -298,11 +339,202 @@ sda_status recipient_host_call(sda_engine* h, const RecipientCall& c, int64_t* o
     if (out_cap < done.len) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
     if (done.len) {
         h->last.recipient = done.rec;
+        if (c.dec) h->last.recipient_decoded = done.dec;
         HIP_TRY(hipMemcpyAsync(out, c.out, done.len * 8, hipMemcpyDeviceToHost, h->stream));
     }
     *out_len = done.len;
     return finish(h);
 }
+
+// What a robust call hands back beside `out`: the per-batch words (host or device, either may be NULL) and the
+// decoded reveal's counts.  Nothing is written before the call has succeeded.
+struct DecodedOutputs {
+    void *verdict, *wrong;
+    uint64_t *redundancy, *radius, *bad_batches, *first_bad, *undecoded, *blame;
+    uint64_t n_idx;
+    bool complete() const {
+        return redundancy && radius && bad_batches && first_bad && undecoded && (!n_idx || blame);
+    }
+    // len == 0: no batch, no check (batched.rs:77-81) -- sda_secret_reconstruct_decoded's counts for it
+    void commit(const DecodedReveal& d, const sda_sharing_scheme* ss, uint64_t len) const {
+        const uint64_t kt = ss->privacy_threshold + ss->secret_count;
+        *redundancy = len ? d.redundancy : (n_idx > kt ? n_idx - kt : 0);
+        *radius = *redundancy / 2;
+        *bad_batches = len ? d.bad_batches : 0;
+        *first_bad = len ? d.first_bad : UINT64_MAX;
+        *undecoded = len ? d.undecoded : 0;
+        for (uint64_t j = 0; j < n_idx; ++j) blame[j] = len && j < d.blame.size() ? d.blame[j] : 0;
+    }
+};
+
+// Where a robust call is defined, checked on the schemes alone: the decoded reveal's output is canonical, so unmask +
+// positive() must be one subtraction mod the sharing prime.  wrong_dev: the device form's `wrong` buffer.
+sda_status decoded_scope(const sda_masking_scheme* ms, const sda_sharing_scheme* ss, int64_t output_modulus,
+                         const void* wrong_dev) {
+    if (ss->kind == SDA_SHARING_ADDITIVE) return fail(SDA_ERR_UNSUPPORTED, "an Additive scheme has no decoded reveal");
+    if (ss->kind == SDA_SHARING_PACKED_SHAMIR) {
+        if (ss->secret_count > sda::kDecodeMaxK)
+            return fail(SDA_ERR_UNSUPPORTED, "the decoded reveal takes at most %u secrets per batch", sda::kDecodeMaxK);
+        if (output_modulus != ss->modulus)
+            return fail(SDA_ERR_UNSUPPORTED, "the robust recipient job needs output_modulus == the sharing prime");
+        if ((ms->kind == SDA_MASKING_FULL || ms->kind == SDA_MASKING_CHACHA) &&
+            (ms->modulus < 0 ? (uint64_t)0 - (uint64_t)ms->modulus : (uint64_t)ms->modulus) != (uint64_t)ss->modulus)
+            return fail(SDA_ERR_UNSUPPORTED, "the robust recipient job needs a masking modulus equal to the sharing prime");
+    }
+    if (wrong_dev && (reinterpret_cast<uintptr_t>(wrong_dev) & 3))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "wrong must be 4-byte aligned");
+    return SDA_OK;
+}
+
+// sda_recipient_job_dev, and with `dec` (and the outputs `dout` its counts go to) sda_recipient_job_decoded_dev: the
+// same call with the decoded reveal in the pipeline, behind the scope checks that make its output defined.
+sda_status job_dev(sda_engine* h, const sda_masking_scheme* ms, const int64_t* mask, uint64_t mask_len,
+                   const uint8_t* seed_bytes, const uint64_t* seed_off, uint64_t n_seeds, const sda_sharing_scheme* ss,
+                   uint64_t dimension, const uint64_t* indices, const uint8_t* clerk_bytes, const uint64_t* clerk_off,
+                   uint64_t n_idx, int64_t output_modulus, int32_t mode, int64_t* out, uint64_t out_cap,
+                   uint64_t* out_len, void* stream, DecodedReveal* dec, const DecodedOutputs* dout) {
+    if (!h || !ms || !ss || !out_len || (dec && (!dout->complete() || (dimension && !out))))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    const bool full = ms->kind == SDA_MASKING_FULL;
+    if (full) n_seeds = 0;                                  // the seed arguments belong to ChaCha and None
+    if ((n_idx && (!clerk_bytes || !clerk_off || !indices)) || (n_seeds && (!seed_bytes || !seed_off)) ||
+        (full && mask_len && !mask))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (dec)
+        if (sda_status e = decoded_scope(ms, ss, output_modulus, dec->wrong)) return e;
+    HIP_TRY(hipSetDevice(h->device));
+    RecipientCall c{*ms, ss, dimension, indices, n_idx, output_modulus, mode, out, out_cap, pick(h, stream)};
+    if (n_seeds)
+        if (sda_status e = check_blob_buffer(seed_bytes, seed_off, n_seeds)) return e;
+    if (n_idx)
+        if (sda_status e = check_blob_buffer(clerk_bytes, clerk_off, n_idx)) return e;
+    c.shares = {ShareSource::kBlobs, nullptr, 0, clerk_bytes, clerk_off};
+    c.mask.n = n_seeds;
+    if (full) {                                             // one row, already folded: full.rs:38-51 has run
+        c.mask = {MaskSource::kReady, mask_len ? 1u : 0u, mask_len, mask};
+    } else if (ms->kind == SDA_MASKING_CHACHA) {
+        c.mask = {MaskSource::kSeedBlobs, n_seeds, sda::kSeedWords, nullptr, seed_bytes, seed_off};
+    } else {                                                // none.rs:23: a blob with a byte decodes to a value
+        for (uint64_t i = 0; i < n_seeds; ++i) c.mask.width |= seed_off[i + 1] - seed_off[i];
+    }
+    RecordsGuard records(h);
+    c.dec = dec;
+    if (sda_status e = recipient_dev_call(h, c, out_len)) return e;
+    if (dec) dout->commit(*dec, ss, *out_len);
+    if (*out_len)
+        h->last.recipient_job = {ms->kind == SDA_MASKING_NONE ? 0u : full ? 1u : 3u,
+                                 ss->kind == SDA_SHARING_ADDITIVE ? 1u : 2u,
+                                 ms->kind == SDA_MASKING_CHACHA ? (uint32_t)n_seeds : 0u};
+    records.keep();
+    return ok();
+}
+
+
+// sda_recipient_job, and with `dec` sda_recipient_job_decoded (dout: HOST verdict / wrong and the counts).
+sda_status job_host(sda_engine* h, const sda_masking_scheme* ms, const uint8_t* const* mask_blobs,
+                    const uint64_t* mask_lens, uint64_t n_masks, const sda_sharing_scheme* ss, uint64_t dimension,
+                    const uint64_t* indices, const uint8_t* const* clerk_blobs, const uint64_t* clerk_lens,
+                    uint64_t n_idx, int64_t output_modulus, int32_t mode, int64_t* out, uint64_t out_cap,
+                    uint64_t* out_len, DecodedReveal* dec, const DecodedOutputs* dout) {
+    if (!h || !ms || !ss || !out_len || (n_masks && (!mask_blobs || !mask_lens)) ||
+        (n_idx && (!clerk_blobs || !clerk_lens || !indices)) || (dec && (!dout->complete() || (dimension && !out))))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (uint64_t i = 0; i < n_masks; ++i)
+        if (mask_lens[i] && !mask_blobs[i])
+            return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument (mask blob %llu)", (unsigned long long)i);
+    for (uint64_t i = 0; i < n_idx; ++i)
+        if (clerk_lens[i] && !clerk_blobs[i])
+            return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument (clerk blob %llu)", (unsigned long long)i);
+    if (dec)
+        if (sda_status e = decoded_scope(ms, ss, output_modulus, nullptr)) return e;
+    *out_len = 0;
+    HIP_TRY(hipSetDevice(h->device));
+    (void)pick(h, h->stream);
+    RecordsGuard records(h);                                // a failing return below: every record stays the previous call's
+    // 1. the mask combine's inputs and panics (receive.rs:101-117), before anything of the clerk results is looked at
+    // (a robust call's capacity is checked where the pipeline checks it, ahead of the check table)
+    RecipientCall c{*ms, ss, dimension, indices, n_idx, output_modulus, mode, nullptr, dec ? out_cap : (uint64_t)-1,
+                    h->stream};
+    c.mask.n = n_masks;
+    const bool chacha = ms->kind == SDA_MASKING_CHACHA;
+    uint32_t mask_route = 0;
+    if (ms->kind == SDA_MASKING_FULL) {
+        // full.rs:38-51 is combiner.rs:16-28: the blobs stream through the clerk's decode -> combine, a group of
+        // them in HBM at a time, and the folded mask stays on the device
+        int64_t* acc = nullptr;
+        uint64_t len = 0;
+        if (sda_status e = host_decode_combine(h, ms->modulus, mask_blobs, mask_lens, n_masks, nullptr, 0, &len, &acc))
+            return e == SDA_ERR_WRONG_DIMENSION ? fail(SDA_ERR_PRECONDITION, "assertion failed: mask.len() == dimension")
+                                                : e;
+        c.mask = {MaskSource::kReady, len ? 1u : 0u, len, acc};
+        mask_route = 2;
+    } else if (chacha) {
+        c.mask = {MaskSource::kSeedBlobs, n_masks, sda::kSeedWords};
+        uint64_t mask_len;
+        if (sda_status e = mask_combine_checks(ms, n_masks, c.mask.width, &mask_len)) return e;
+        mask_route = 3;
+    } else {
+        if (sda_status e = no_mask_checks(mask_lens, n_masks)) return e;
+    }
+    uint64_t seed_total = 0, clerk_total = 0;
+    if (chacha)
+        for (uint64_t i = 0; i < n_masks; ++i) seed_total += mask_lens[i];
+    for (uint64_t i = 0; i < n_idx; ++i) clerk_total += clerk_lens[i];
+    std::vector<uint64_t> seed_off, clerk_off;
+    uint8_t* dseed_bytes = nullptr;
+    // A multi-device handle combines its ChaCha mask as sda_recipient_reveal does: the key words are decoded on the
+    // device and read back (32 bytes a seed) for combine_mask_multi.
+    const bool multi = multi_mask(h, ms, n_masks);
+    if (multi) {
+        DevArena a;
+        if (sda_status e = stage(h, rup(seed_total + 32) + rup(n_masks * sda::kSeedWords * 4) + rup((n_masks + 1) * 8), &a))
+            return e;
+        if (sda_status e = upload_blobs(h, mask_blobs, mask_lens, n_masks, &a, &dseed_bytes, &seed_off)) return e;
+        uint32_t* dwords = a.take<uint32_t>(n_masks * sda::kSeedWords);
+        uint64_t* doff = a.take<uint64_t>(n_masks + 1);
+        std::vector<uint32_t> seeds(n_masks * sda::kSeedWords);
+        HIP_TRY(sda::launch_recipient_seeds(dseed_bytes, seed_off.data(), n_masks, doff, dwords, h->stream));
+        HIP_TRY(hipMemcpyAsync(seeds.data(), dwords, seeds.size() * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (sda_status e = combine_mask_multi(h, seeds, sda::kSeedWords, n_masks, &c)) return e;
+        mask_route = 4;
+    }
+    // 2. one upload of the seed and clerk payloads
+    const uint64_t outn = ss->kind == SDA_SHARING_ADDITIVE ? (n_idx ? clerk_lens[0] : 0) : dimension;
+    const bool up_seeds = chacha && !multi && n_masks;
+    DevArena a;
+    // a robust call's B verdict and wrong words travel behind `out`
+    const uint64_t kk = ss->secret_count ? ss->secret_count : 1, Bw = dec ? (dimension + kk - 1) / kk : 0;
+    if (sda_status e = stage(h, (up_seeds ? rup(seed_total + 32) : 0) + rup(clerk_total + 32) + rup(outn * 8 + 8) +
+                                    rup(Bw * 2) + rup(Bw * 4), &a))
+        return e;
+    if (up_seeds) {
+        if (sda_status e = upload_blobs(h, mask_blobs, mask_lens, n_masks, &a, &dseed_bytes, &seed_off)) return e;
+        c.mask.seed_bytes = dseed_bytes;
+        c.mask.seed_off = seed_off.data();
+    }
+    uint8_t* dclerk = nullptr;
+    if (sda_status e = upload_blobs(h, clerk_blobs, clerk_lens, n_idx, &a, &dclerk, &clerk_off)) return e;
+    c.shares = {ShareSource::kBlobs, nullptr, 0, dclerk, clerk_off.data()};
+    c.out = a.take<int64_t>(outn + 1);
+    if (dec) {
+        c.dec = dec;
+        if (dout->verdict) dec->verdict = a.take<uint16_t>(Bw);
+        if (dout->wrong) dec->wrong = a.take<uint32_t>(Bw);
+    }
+    // 3. the pipeline, the clerk results decoded where it reconstructs
+    if (sda_status e = recipient_host_call(h, c, out, out_cap, out_len)) return e;
+    if (dec) {
+        if (*out_len && dec->verdict) HIP_TRY(hipMemcpy(dout->verdict, dec->verdict, Bw * 2, hipMemcpyDeviceToHost));
+        if (*out_len && dec->wrong) HIP_TRY(hipMemcpy(dout->wrong, dec->wrong, Bw * 4, hipMemcpyDeviceToHost));
+        dout->commit(*dec, ss, *out_len);
+    }
+    if (*out_len)
+        h->last.recipient_job = {mask_route, ss->kind == SDA_SHARING_ADDITIVE ? 1u : 2u, chacha ? (uint32_t)n_masks : 0u};
+    records.keep();
+    return SDA_OK;
+}
+
 
 }  // namespace
 
@@ -401,35 +633,8 @@ sda_status sda_recipient_job_dev(sda_engine* h, const sda_masking_scheme* ms, co
                                  int64_t output_modulus, int32_t mode, int64_t* out, uint64_t out_cap,
                                  uint64_t* out_len, void* stream) {
     SDA_ENTRY;
-    if (!h || !ms || !ss || !out_len) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    const bool full = ms->kind == SDA_MASKING_FULL;
-    if (full) n_seeds = 0;                                  // the seed arguments belong to ChaCha and None
-    if ((n_idx && (!clerk_bytes || !clerk_off || !indices)) || (n_seeds && (!seed_bytes || !seed_off)) ||
-        (full && mask_len && !mask))
-        return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    HIP_TRY(hipSetDevice(h->device));
-    RecipientCall c{*ms, ss, dimension, indices, n_idx, output_modulus, mode, out, out_cap, pick(h, stream)};
-    if (n_seeds)
-        if (sda_status e = check_blob_buffer(seed_bytes, seed_off, n_seeds)) return e;
-    if (n_idx)
-        if (sda_status e = check_blob_buffer(clerk_bytes, clerk_off, n_idx)) return e;
-    c.shares = {ShareSource::kBlobs, nullptr, 0, clerk_bytes, clerk_off};
-    c.mask.n = n_seeds;
-    if (full) {                                             // one row, already folded: full.rs:38-51 has run
-        c.mask = {MaskSource::kReady, mask_len ? 1u : 0u, mask_len, mask};
-    } else if (ms->kind == SDA_MASKING_CHACHA) {
-        c.mask = {MaskSource::kSeedBlobs, n_seeds, sda::kSeedWords, nullptr, seed_bytes, seed_off};
-    } else {                                                // none.rs:23: a blob with a byte decodes to a value
-        for (uint64_t i = 0; i < n_seeds; ++i) c.mask.width |= seed_off[i + 1] - seed_off[i];
-    }
-    RecordsGuard records(h);
-    if (sda_status e = recipient_dev_call(h, c, out_len)) return e;
-    if (*out_len)
-        h->last.recipient_job = {ms->kind == SDA_MASKING_NONE ? 0u : full ? 1u : 3u,
-                                 ss->kind == SDA_SHARING_ADDITIVE ? 1u : 2u,
-                                 ms->kind == SDA_MASKING_CHACHA ? (uint32_t)n_seeds : 0u};
-    records.keep();
-    return ok();
+    return job_dev(h, ms, mask, mask_len, seed_bytes, seed_off, n_seeds, ss, dimension, indices, clerk_bytes, clerk_off,
+                   n_idx, output_modulus, mode, out, out_cap, out_len, stream, nullptr, nullptr);
 }
 
 sda_status sda_recipient_job(sda_engine* h, const sda_masking_scheme* ms, const uint8_t* const* mask_blobs,
@@ -438,86 +643,80 @@ sda_status sda_recipient_job(sda_engine* h, const sda_masking_scheme* ms, const 
                              const uint64_t* clerk_lens, uint64_t n_idx, int64_t output_modulus, int32_t mode,
                              int64_t* out, uint64_t out_cap, uint64_t* out_len) {
     SDA_ENTRY;
-    if (!h || !ms || !ss || !out_len || (n_masks && (!mask_blobs || !mask_lens)) ||
-        (n_idx && (!clerk_blobs || !clerk_lens || !indices)))
+    return job_host(h, ms, mask_blobs, mask_lens, n_masks, ss, dimension, indices, clerk_blobs, clerk_lens, n_idx,
+                    output_modulus, mode, out, out_cap, out_len, nullptr, nullptr);
+}
+// ---------------- robust recipient job: the same calls over the decoded reveal ----------------
+sda_status
+sda_recipient_job_decoded(sda_engine* h, const sda_masking_scheme* ms, const uint8_t* const* mask_blobs,
+                                     const uint64_t* mask_lens, uint64_t n_masks, const sda_sharing_scheme* ss,
+                                     uint64_t dimension, const uint64_t* indices, const uint8_t* const* clerk_blobs,
+                                     const uint64_t* clerk_lens, uint64_t n_idx, int64_t output_modulus, int64_t* out,
+                                     uint64_t out_cap, uint64_t* out_len, void* verdict, void* wrong,
+                                     uint64_t* redundancy, uint64_t* radius, uint64_t* bad_batches,
+                                     uint64_t* first_bad, uint64_t* undecoded, uint64_t* blame) {
+    SDA_ENTRY;
+    DecodedReveal dec;
+    const DecodedOutputs dout{verdict, wrong, redundancy, radius, bad_batches, first_bad, undecoded, blame, n_idx};
+    return job_host(h, ms, mask_blobs, mask_lens, n_masks, ss, dimension, indices, clerk_blobs, clerk_lens, n_idx,
+                    output_modulus, SDA_REVEAL_CANONICAL, out, out_cap, out_len, &dec, &dout);
+}
+
+sda_status
+sda_recipient_job_decoded_dev(sda_engine* h, const sda_masking_scheme* ms, const int64_t* mask,
+                                         uint64_t mask_len, const uint8_t* seed_bytes, const uint64_t* seed_off,
+                                         uint64_t n_seeds, const sda_sharing_scheme* ss, uint64_t dimension,
+                                         const uint64_t* indices, const uint8_t* clerk_bytes, const uint64_t* clerk_off,
+                                         uint64_t n_idx, int64_t output_modulus, int64_t* out, uint64_t out_cap,
+                                         uint64_t* out_len, void* verdict, void* wrong, uint64_t* redundancy,
+                                         uint64_t* radius, uint64_t* bad_batches, uint64_t* first_bad,
+                                         uint64_t* undecoded, uint64_t* blame, void* stream) {
+    SDA_ENTRY;
+    DecodedReveal dec;
+    dec.verdict = static_cast<uint16_t*>(verdict);
+    dec.wrong = static_cast<uint32_t*>(wrong);
+    const DecodedOutputs dout{verdict, wrong, redundancy, radius, bad_batches, first_bad, undecoded, blame, n_idx};
+    return job_dev(h, ms, mask, mask_len, seed_bytes, seed_off, n_seeds, ss, dimension, indices, clerk_bytes, clerk_off,
+                   n_idx, output_modulus, SDA_REVEAL_CANONICAL, out, out_cap, out_len, stream, &dec, &dout);
+}
+
+sda_status sda_recipient_reveal_decoded_dev(sda_engine* h, const sda_masking_scheme* ms, const void* mask_in,
+                                            uint64_t n_masks, uint64_t mask_width, const sda_sharing_scheme* ss,
+                                            uint64_t dimension, const uint64_t* indices, const int64_t* shares,
+                                            uint64_t n_idx, uint64_t share_len, int64_t output_modulus, int64_t* out,
+                                            uint64_t out_cap, uint64_t* out_len, void* verdict, void* wrong,
+                                            uint64_t* redundancy, uint64_t* radius, uint64_t* bad_batches,
+                                            uint64_t* first_bad, uint64_t* undecoded, uint64_t* blame, void* stream) {
+    SDA_ENTRY;
+    const DecodedOutputs dout{verdict, wrong, redundancy, radius, bad_batches, first_bad, undecoded, blame, n_idx};
+    if (!h || !ms || !ss || !out_len || !dout.complete() || (dimension && !out) || (n_idx && (!shares || !indices)) ||
+        (n_masks && mask_width && !mask_in))
         return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    for (uint64_t i = 0; i < n_masks; ++i)
-        if (mask_lens[i] && !mask_blobs[i])
-            return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument (mask blob %llu)", (unsigned long long)i);
-    for (uint64_t i = 0; i < n_idx; ++i)
-        if (clerk_lens[i] && !clerk_blobs[i])
-            return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument (clerk blob %llu)", (unsigned long long)i);
-    *out_len = 0;
+    if (sda_status e = decoded_scope(ms, ss, output_modulus, wrong)) return e;
     HIP_TRY(hipSetDevice(h->device));
-    (void)pick(h, h->stream);
-    RecordsGuard records(h);                                // a failing return below: every record stays the previous call's
-    // 1. the mask combine's inputs and panics (receive.rs:101-117), before anything of the clerk results is looked at
-    RecipientCall c{*ms, ss, dimension, indices, n_idx, output_modulus, mode, nullptr, (uint64_t)-1, h->stream};
-    c.mask.n = n_masks;
-    const bool chacha = ms->kind == SDA_MASKING_CHACHA;
-    uint32_t mask_route = 0;
-    if (ms->kind == SDA_MASKING_FULL) {
-        // full.rs:38-51 is combiner.rs:16-28: the blobs stream through the clerk's decode -> combine, a group of
-        // them in HBM at a time, and the folded mask stays on the device
-        int64_t* acc = nullptr;
-        uint64_t len = 0;
-        if (sda_status e = host_decode_combine(h, ms->modulus, mask_blobs, mask_lens, n_masks, nullptr, 0, &len, &acc))
-            return e == SDA_ERR_WRONG_DIMENSION ? fail(SDA_ERR_PRECONDITION, "assertion failed: mask.len() == dimension")
-                                                : e;
-        c.mask = {MaskSource::kReady, len ? 1u : 0u, len, acc};
-        mask_route = 2;
-    } else if (chacha) {
-        c.mask = {MaskSource::kSeedBlobs, n_masks, sda::kSeedWords};
-        uint64_t mask_len;
-        if (sda_status e = mask_combine_checks(ms, n_masks, c.mask.width, &mask_len)) return e;
-        mask_route = 3;
-    } else {
-        if (sda_status e = no_mask_checks(mask_lens, n_masks)) return e;
-    }
-    uint64_t seed_total = 0, clerk_total = 0;
-    if (chacha)
-        for (uint64_t i = 0; i < n_masks; ++i) seed_total += mask_lens[i];
-    for (uint64_t i = 0; i < n_idx; ++i) clerk_total += clerk_lens[i];
-    std::vector<uint64_t> seed_off, clerk_off;
-    uint8_t* dseed_bytes = nullptr;
-    // A multi-device handle combines its ChaCha mask as sda_recipient_reveal does: the key words are decoded on the
-    // device and read back (32 bytes a seed) for combine_mask_multi.
-    const bool multi = multi_mask(h, ms, n_masks);
-    if (multi) {
-        DevArena a;
-        if (sda_status e = stage(h, rup(seed_total + 32) + rup(n_masks * sda::kSeedWords * 4) + rup((n_masks + 1) * 8), &a))
-            return e;
-        if (sda_status e = upload_blobs(h, mask_blobs, mask_lens, n_masks, &a, &dseed_bytes, &seed_off)) return e;
-        uint32_t* dwords = a.take<uint32_t>(n_masks * sda::kSeedWords);
-        uint64_t* doff = a.take<uint64_t>(n_masks + 1);
-        std::vector<uint32_t> seeds(n_masks * sda::kSeedWords);
-        HIP_TRY(sda::launch_recipient_seeds(dseed_bytes, seed_off.data(), n_masks, doff, dwords, h->stream));
-        HIP_TRY(hipMemcpyAsync(seeds.data(), dwords, seeds.size() * 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (sda_status e = combine_mask_multi(h, seeds, sda::kSeedWords, n_masks, &c)) return e;
-        mask_route = 4;
-    }
-    // 2. one upload of the seed and clerk payloads
-    const uint64_t outn = ss->kind == SDA_SHARING_ADDITIVE ? (n_idx ? clerk_lens[0] : 0) : dimension;
-    const bool up_seeds = chacha && !multi && n_masks;
-    DevArena a;
-    if (sda_status e = stage(h, (up_seeds ? rup(seed_total + 32) : 0) + rup(clerk_total + 32) + rup(outn * 8 + 8), &a))
-        return e;
-    if (up_seeds) {
-        if (sda_status e = upload_blobs(h, mask_blobs, mask_lens, n_masks, &a, &dseed_bytes, &seed_off)) return e;
-        c.mask.seed_bytes = dseed_bytes;
-        c.mask.seed_off = seed_off.data();
-    }
-    uint8_t* dclerk = nullptr;
-    if (sda_status e = upload_blobs(h, clerk_blobs, clerk_lens, n_idx, &a, &dclerk, &clerk_off)) return e;
-    c.shares = {ShareSource::kBlobs, nullptr, 0, dclerk, clerk_off.data()};
-    c.out = a.take<int64_t>(outn + 1);
-    // 3. the pipeline, the clerk results decoded where it reconstructs
-    if (sda_status e = recipient_host_call(h, c, out, out_cap, out_len)) return e;
-    if (*out_len)
-        h->last.recipient_job = {mask_route, ss->kind == SDA_SHARING_ADDITIVE ? 1u : 2u, chacha ? (uint32_t)n_masks : 0u};
+    DecodedReveal dec;
+    dec.verdict = static_cast<uint16_t*>(verdict);
+    dec.wrong = static_cast<uint32_t*>(wrong);
+    RecipientCall c{*ms, ss, dimension, indices, n_idx, output_modulus, SDA_REVEAL_CANONICAL, out, out_cap, pick(h, stream)};
+    c.mask = {MaskSource::kRows, n_masks, mask_width, mask_in};
+    c.shares = {ShareSource::kRows, shares, share_len};
+    c.dec = &dec;
+    RecordsGuard records(h);
+    if (sda_status e = recipient_dev_call(h, c, out_len)) return e;
+    dout.commit(dec, ss, *out_len);
     records.keep();
-    return SDA_OK;
+    return ok();
+}
+
+sda_status sda_recipient_decoded_last_launch(sda_engine* h, uint32_t* unmask_route, uint32_t* reveal_runs,
+                                             uint32_t* compact) {
+    SDA_ENTRY;
+    if (!h || !unmask_route || !reveal_runs || !compact) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    const sda_engine::RecipientDecodedLaunchInfo& r = h->last.recipient_decoded;
+    *unmask_route = r.unmask_route;
+    *reveal_runs = r.reveal_runs;
+    *compact = r.compact;
+    return ok();
 }
 
 sda_status sda_recipient_job_last_launch(sda_engine* h, uint32_t* mask_route, uint32_t* share_route,

@@ -231,6 +231,14 @@ hipError_t launch_packed_check_locate(const PackedCheckArgs& a, const CheckGeom&
 // The fused first pass (packed_repair_plan: kRepairFused) and its one wait: out holds the reveal of every batch from
 // its first k + t shares, a.verdict (when given) the provisional verdicts, *res the counts.
 hipError_t launch_packed_repair(const PackedRepairArgs& a, const CheckGeom& g, hipStream_t s, PackedCheckResult* res);
+// The same first pass over i64 rows with the recipient's mask (device [n_vectors][dimension], 8-byte aligned)
+// subtracted in its write-back (recipient_repair.hip): out[i] = (secret_i - mask_i) mod p in [0, p), every i64 mask
+// value reduced exactly.  launch_recipient_unmask is that subtraction as a pass of its own over secrets in [0, p)
+// (only enqueues).
+hipError_t launch_recipient_repair(const PackedRepairArgs& a, const int64_t* mask, const CheckGeom& g, hipStream_t s,
+                                   PackedCheckResult* res);
+hipError_t launch_recipient_unmask(const int64_t* secrets, const int64_t* mask, uint64_t D, const MontP& M,
+                                   int64_t* out, hipStream_t s);
 // What follows a pass that counted res->bad > 0 bad batches into g.cnt, and its wait.  `verdict`: never nullptr (the
 // caller's buffer, or zeroed scratch when it gave none).  locate: the location pass first (fused path; the composed
 // path's share check has run it).  recompute: every bad batch is first revealed again from its first k + t shares

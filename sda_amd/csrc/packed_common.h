@@ -402,25 +402,37 @@ __device__ __forceinline__ bool share_in_range(int32_t v, uint32_t p, int64_t) {
 // The results leave as nontemporal stores (written once, streamed out), 16 bytes per lane when the block's
 // output is 16-byte aligned (lds_o is the dynamic LDS base, so 16-byte aligned too): canonical reveal -1.4 to
 // -2.8 %, exact -0.7 to -1.1 % against 8-byte cached stores (in-process A/B on two boxes, profiles/r06ab, r06ac).
+// What is stored is epi.at(first) applied to what was parked: at(first) binds the epilogue to the block's first
+// element of the vector, and its one(v, j) / pair(v, j) give the value of element j (elements j, j + 1) of the
+// block from the parked v.  FlushAsIs stores the results as they are.
+using FlushPair = int64_t __attribute__((ext_vector_type(2)));
+struct FlushAsIs {
+    __device__ __forceinline__ FlushAsIs at(uint64_t) const { return *this; }
+    __device__ __forceinline__ int64_t one(int64_t v, uint32_t) const { return v; }
+    __device__ __forceinline__ FlushPair pair(FlushPair v, uint32_t) const { return v; }
+};
+template <class Epi>
+__device__ __forceinline__ void reveal_flush_with(int64_t* lds_o, int64_t* o, uint64_t b0, uint64_t B, uint64_t D,
+                                                  uint32_t k, const Epi& epilogue) {
+    __syncthreads();
+    const uint64_t first = b0 * k;
+    const uint64_t last = (b0 + 256 < B ? b0 + 256 : B) * k;
+    const uint32_t cnt = (uint32_t)((last < D ? last : D) - first);
+    int64_t* dst = o + first;
+    const auto epi = epilogue.at(first);
+    if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+        const FlushPair* src2 = reinterpret_cast<const FlushPair*>(lds_o);
+        FlushPair* dst2 = reinterpret_cast<FlushPair*>(dst);
+        for (uint32_t j = threadIdx.x; j < cnt / 2; j += 256) __builtin_nontemporal_store(epi.pair(src2[j], 2 * j), dst2 + j);
+        if ((cnt & 1) && threadIdx.x == 0) __builtin_nontemporal_store(epi.one(lds_o[cnt - 1], cnt - 1), dst + cnt - 1);
+    } else {
+        for (uint32_t j = threadIdx.x; j < cnt; j += 256) __builtin_nontemporal_store(epi.one(lds_o[j], j), dst + j);
+    }
+}
 template <bool STAGED>
 __device__ __forceinline__ void reveal_flush(int64_t* lds_o, int64_t* o, uint64_t b0, uint64_t B, uint64_t D,
                                              uint32_t k) {
-    if constexpr (STAGED) {
-        __syncthreads();
-        const uint64_t first = b0 * k;
-        const uint64_t last = (b0 + 256 < B ? b0 + 256 : B) * k;
-        const uint32_t cnt = (uint32_t)((last < D ? last : D) - first);
-        int64_t* dst = o + first;
-        if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-            using V2 = int64_t __attribute__((ext_vector_type(2)));
-            const V2* src2 = reinterpret_cast<const V2*>(lds_o);
-            V2* dst2 = reinterpret_cast<V2*>(dst);
-            for (uint32_t j = threadIdx.x; j < cnt / 2; j += 256) __builtin_nontemporal_store(src2[j], dst2 + j);
-            if ((cnt & 1) && threadIdx.x == 0) __builtin_nontemporal_store(lds_o[cnt - 1], dst + cnt - 1);
-        } else {
-            for (uint32_t j = threadIdx.x; j < cnt; j += 256) __builtin_nontemporal_store(lds_o[j], dst + j);
-        }
-    }
+    if constexpr (STAGED) reveal_flush_with(lds_o, o, b0, B, D, k, FlushAsIs{});
 }
 
 constexpr int ilog(int x, int b) { return x <= 1 ? 0 : 1 + ilog(x / b, b); }

@@ -21,6 +21,7 @@
 //   rows [r, r + k)   lam[e][s]
 //   row  r + k        winv[s] (zeros when r == 0)
 #include "check_launch.h"
+#include "repair_body.h"
 #include "repair_plan.h"
 
 namespace sda {
@@ -28,32 +29,7 @@ using namespace packed;
 
 namespace {
 
-// One lane = one batch, in check_body's shape: the loads, the residues as one register tuple, the r syndrome rows,
-// then k rows against lam into the workgroup's LDS block ([lane][k]), the report, and reveal_flush's coalesced
-// write-back (16-byte nontemporal stores when the block's output is 16-byte aligned, 8-byte ones otherwise; the tail
-// batch is cut at `dimension` there).  Lanes past the last batch hold the last batch again; neither pass keeps them.
-template <class ST, int NMAX>
-__device__ __forceinline__ void repair_body(const ST* __restrict__ shares, uint64_t B, uint64_t D,
-                                            int64_t* __restrict__ out, uint32_t n_idx, uint32_t kt, uint32_t k,
-                                            const uint32_t* __restrict__ tab, uint32_t ks, const MontP& M,
-                                            uint16_t* __restrict__ verdict, unsigned long long* __restrict__ cnt,
-                                            uint32_t cap, int64_t* lds_o) {
-    const uint32_t wave0 = wave_first_thread();
-    const uint64_t b0 = (uint64_t)blockIdx.x * 256, rest = B - b0;
-    const ST* sh = shares + ((uint64_t)blockIdx.y * n_idx * B + b0) + (threadIdx.x < rest ? threadIdx.x : (uint32_t)rest - 1);
-    const uint32_t p = M.p;
-    const ShareTuple<NMAX> S = load_residues<ST, NMAX>(sh, B, n_idx, p);
-    const uint32_t r = n_idx - kt;
-    uint32_t nz = 0;
-    for (uint32_t c = 0; c < r; ++c)
-        nz |= addm(row_mac<NMAX>(tab + (size_t)c * ks, S, kt, M), S[(kt + c) & (NMAX - 1)], p);     // kt + c < n_idx <= NMAX
-    const uint32_t* lam = tab + (size_t)r * ks;
-    int64_t* dst = lds_o + threadIdx.x * k;
-    for (uint32_t e = 0; e < k; ++e) dst[e] = (int64_t)row_mac<NMAX>(lam + (size_t)e * ks, S, kt, M);
-    check_report(nz != 0, wave0, B, verdict, cnt, cap);
-    reveal_flush<true>(lds_o, out + (uint64_t)blockIdx.y * D, b0, B, D, k);
-}
-
+// The first pass is repair_body (repair_body.h) with the secrets stored as they are.
 template <int NMAX>
 __global__ __launch_bounds__(256) void packed_repair_kernel(const int64_t* __restrict__ shares, uint64_t B, uint64_t D,
                                                             int64_t* __restrict__ out, uint32_t n_idx, uint32_t kt,
@@ -61,7 +37,7 @@ __global__ __launch_bounds__(256) void packed_repair_kernel(const int64_t* __res
                                                             MontP M, uint16_t* __restrict__ verdict,
                                                             unsigned long long* __restrict__ cnt, uint32_t cap) {
     extern __shared__ int64_t lds_o[];
-    repair_body<int64_t, NMAX>(shares, B, D, out, n_idx, kt, k, tab, ks, M, verdict, cnt, cap, lds_o);
+    repair_body<int64_t, NMAX>(shares, B, D, out, n_idx, kt, k, tab, ks, M, verdict, cnt, cap, lds_o, FlushAsIs{});
 }
 
 template <int NMAX>
@@ -72,7 +48,7 @@ __global__ __launch_bounds__(256) void packed_repair32_kernel(const int32_t* __r
                                                               uint16_t* __restrict__ verdict,
                                                               unsigned long long* __restrict__ cnt, uint32_t cap) {
     extern __shared__ int64_t lds_o[];
-    repair_body<int32_t, NMAX>(shares, B, D, out, n_idx, kt, k, tab, ks, M, verdict, cnt, cap, lds_o);
+    repair_body<int32_t, NMAX>(shares, B, D, out, n_idx, kt, k, tab, ks, M, verdict, cnt, cap, lds_o, FlushAsIs{});
 }
 
 // One lane per bad batch -- the `total` logged ones, or with `all` every batch of the call (the log overflowed).  A

@@ -136,6 +136,11 @@ DECODE_PATH_DECODED = 2
 DECODE_UNDECODABLE = 0xFFFF
 ShareDecode = collections.namedtuple("ShareDecode", "redundancy radius bad_batches first_bad undecoded blame")
 DecodeLaunch = collections.namedtuple("DecodeLaunch", "path bucket decoded fixed max_errors overflowed")
+# Robust recipient job (sda_recipient_job_decoded): sda_recipient_decoded_last_launch's unmask_route codes and record
+RECIPIENT_UNMASK_NONE = 0
+RECIPIENT_UNMASK_FUSED = 1
+RECIPIENT_UNMASK_SEPARATE = 2
+RecipientDecodedLaunch = collections.namedtuple("RecipientDecodedLaunch", "unmask_route reveal_runs compact")
 
 # Elements one workgroup of the draws kernel produces (csrc/kernels.h kDrawsTile): the sizes at which
 # sda_draws_dev's grid gains a workgroup
@@ -275,6 +280,19 @@ SIGNATURES = [
                                     C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, _vp, _u64p, C.c_uint64,
                                     C.c_int64, C.c_int32, _vp, C.c_uint64, _u64p, _vp]),
     ("sda_recipient_job_last_launch", _st, [_vp, _u32p, _u32p, _u32p]),
+    ("sda_recipient_job_decoded", _st, [_vp, C.POINTER(S.MaskingSchemeC), C.POINTER(_u8p), _u64p, C.c_uint64,
+                                        C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, C.POINTER(_u8p), _u64p,
+                                        C.c_uint64, C.c_int64, _i64p, C.c_uint64, _u64p, _vp, _vp, _u64p, _u64p,
+                                        _u64p, _u64p, _u64p, _u64p]),
+    ("sda_recipient_job_decoded_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _vp, C.c_uint64, _vp, _u64p, C.c_uint64,
+                                            C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, _vp, _u64p, C.c_uint64,
+                                            C.c_int64, _vp, C.c_uint64, _u64p, _vp, _vp, _u64p, _u64p, _u64p, _u64p,
+                                            _u64p, _u64p, _vp]),
+    ("sda_recipient_reveal_decoded_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _vp, C.c_uint64, C.c_uint64,
+                                               C.POINTER(S.SharingSchemeC), C.c_uint64, _u64p, _vp, C.c_uint64,
+                                               C.c_uint64, C.c_int64, _vp, C.c_uint64, _u64p, _vp, _vp, _u64p, _u64p,
+                                               _u64p, _u64p, _u64p, _u64p, _vp]),
+    ("sda_recipient_decoded_last_launch", _st, [_vp, _u32p, _u32p, _u32p]),
     ("sda_participant_share_dev", _st, [_vp, C.POINTER(S.MaskingSchemeC), _u32p, C.c_uint64, _vp,
                                         C.POINTER(S.SharingSchemeC), _vp, C.c_uint64, _vp, C.c_int32, _vp, _vp,
                                         C.c_uint64, _u64p, _vp]),
@@ -657,6 +675,40 @@ class Engine:
                                           _ptr(idx, _u64p), sptrs, slens, ns, output_modulus, mode, _ptr(out),
                                           out.size, C.byref(olen)))
         return out[: olen.value]
+
+    def recipient_job_decoded(self, masking, mask_blobs: Sequence[bytes], sharing, dimension: int, indexed_blobs,
+                              output_modulus: int, want_verdict=True, want_wrong=True):
+        """recipient_job with the decoded reveal inside (sda_recipient_job_decoded): up to radius wrong clerk results
+        per batch are corrected.  Returns (out, ShareDecode, verdict, wrong) as secret_reconstruct_decoded does, out
+        being (secret - mask) mod p in [0, p)."""
+        ms, ss = masking.c(), sharing.c()
+        mbufs, mptrs, mlens, nm = self._blobs(mask_blobs)
+        idx = _arr([i for i, _ in indexed_blobs], np.uint64)
+        sbufs, sptrs, slens, ns = self._blobs([b for _, b in indexed_blobs])
+        k = max(int(getattr(sharing, "secret_count", 1) or 1), 1)
+        nb = (dimension + k - 1) // k
+        verdict = np.full(max(nb, 1), 0xAAAA, np.uint16) if want_verdict else None
+        wrong = np.full(max(nb, 1), 0xAAAAAAAA, np.uint32) if want_wrong else None
+        out = np.zeros(max(dimension, 1), np.int64)
+        olen = C.c_uint64(0)
+        r, rad, bad, first, und = (C.c_uint64() for _ in range(5))
+        blame = np.zeros(max(ns, 1), np.uint64)
+        _check(self.lib.sda_recipient_job_decoded(self.h, C.byref(ms), mptrs, mlens, nm, C.byref(ss), dimension,
+                                                  _ptr(idx, _u64p), sptrs, slens, ns, output_modulus, _ptr(out),
+                                                  dimension, C.byref(olen),
+                                                  verdict.ctypes.data if want_verdict else None,
+                                                  wrong.ctypes.data if want_wrong else None, C.byref(r), C.byref(rad),
+                                                  C.byref(bad), C.byref(first), C.byref(und), _ptr(blame, _u64p)))
+        res = ShareDecode(int(r.value), int(rad.value), int(bad.value), int(first.value), int(und.value),
+                          [int(x) for x in blame[:ns]])
+        return (out[: olen.value], res, verdict[:nb] if want_verdict else None, wrong[:nb] if want_wrong else None)
+
+    def recipient_decoded_last_launch(self):
+        """RecipientDecodedLaunch(unmask_route, reveal_runs, compact) of the handle's last robust recipient call with
+        a non-empty output (sda_recipient_decoded_last_launch): all zeros before the first."""
+        route, runs, compact = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(self.lib.sda_recipient_decoded_last_launch(self.h, C.byref(route), C.byref(runs), C.byref(compact)))
+        return RecipientDecodedLaunch(int(route.value), int(runs.value), int(compact.value))
 
     def synchronize(self):
         _check(self.lib.sda_engine_synchronize(self.h))
@@ -1222,6 +1274,47 @@ class Engine:
                                               _ptr(coff, _u64p), coff.size - 1, output_modulus, mode, out_ptr,
                                               out_cap, C.byref(olen), stream))
         return olen.value
+
+    def _decoded_counts(self, n_idx):
+        cs = [C.c_uint64() for _ in range(5)]
+        blame = np.zeros(max(n_idx, 1), np.uint64)
+        done = lambda: ShareDecode(*[int(c.value) for c in cs], [int(x) for x in blame[:n_idx]])
+        return [C.byref(c) for c in cs] + [_ptr(blame, _u64p)], done
+
+    def recipient_reveal_decoded_dev(self, masking, mask_ptr, n_masks, mask_width, sharing, dimension, indices,
+                                     shares_ptr, share_len, output_modulus, out_ptr, out_cap, verdict_ptr=None,
+                                     wrong_ptr=None, stream=None):
+        """recipient_reveal_dev with the decoded reveal inside (sda_recipient_reveal_decoded_dev): verdict_ptr device
+        uint16 [B] or None, wrong_ptr device uint32 [B] or None.  Returns (out_len, ShareDecode).  Waits for its
+        stream."""
+        ms, ss = masking.c(), sharing.c()
+        idx = _arr(indices, np.uint64)
+        olen = C.c_uint64(0)
+        counts, done = self._decoded_counts(idx.size)
+        _check(self.lib.sda_recipient_reveal_decoded_dev(self.h, C.byref(ms), mask_ptr, n_masks, mask_width,
+                                                         C.byref(ss), dimension, _ptr(idx, _u64p), shares_ptr,
+                                                         idx.size, share_len, output_modulus, out_ptr, out_cap,
+                                                         C.byref(olen), verdict_ptr, wrong_ptr, *counts, stream))
+        return olen.value, done()
+
+    def recipient_job_decoded_dev(self, masking, sharing, dimension, indices, clerk_ptr, clerk_off, output_modulus,
+                                  out_ptr, out_cap, mask_ptr=None, mask_len=0, seed_ptr=None, seed_off=(),
+                                  verdict_ptr=None, wrong_ptr=None, stream=None):
+        """recipient_job_dev with the decoded reveal inside (sda_recipient_job_decoded_dev); the inputs as
+        recipient_job_dev takes them, verdict_ptr / wrong_ptr as recipient_reveal_decoded_dev.  Returns
+        (out_len, ShareDecode).  Waits for its stream."""
+        ms, ss = masking.c(), sharing.c()
+        idx = _arr(indices, np.uint64)
+        coff = _arr(clerk_off if len(clerk_off) else [0], np.uint64)
+        soff = _arr(seed_off if len(seed_off) else [0], np.uint64)
+        olen = C.c_uint64(0)
+        counts, done = self._decoded_counts(idx.size)
+        _check(self.lib.sda_recipient_job_decoded_dev(self.h, C.byref(ms), mask_ptr, mask_len, seed_ptr,
+                                                      _ptr(soff, _u64p), soff.size - 1, C.byref(ss), dimension,
+                                                      _ptr(idx, _u64p), clerk_ptr, _ptr(coff, _u64p), coff.size - 1,
+                                                      output_modulus, out_ptr, out_cap, C.byref(olen), verdict_ptr,
+                                                      wrong_ptr, *counts, stream))
+        return olen.value, done()
 
     def participant_share_dev(self, masking, sharing, secrets_ptr, dimension, draws_ptr, shares_ptr, seed=None,
                               full_masks_ptr=None, payload_ptr=None, payload_cap=0, mode=REVEAL_EXACT, stream=None):
