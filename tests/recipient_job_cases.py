@@ -133,20 +133,25 @@ def expected_output(case):
 def expected_records(case, form, multi=False):
     """(sda_recipient_job_last_launch, sda_recipient_last_launch) of a successful call with a non-empty output."""
     masks, indexed = rows(case)
-    lens = [len(r) for _, r in indexed]
-    if isinstance(case.ms, S.NoMasking):
+    return records(case.ms, len(masks), case.ss, case.dimension, [i for i, _ in indexed],
+                   [len(r) for _, r in indexed], case.m_out, case.mode, form, multi=multi, late="late" in case.tags)
+
+
+def records(ms, n_masks, ss, dimension, indices, lens, m_out, mode, form, multi=False, late=False):
+    """expected_records from the call's shape alone: n_masks mask blobs, clerk results of `lens` values at clerk
+    `indices`."""
+    packed = PD.is_packed(ss)
+    if isinstance(ms, S.NoMasking):
         route = MASK_NONE
-    elif isinstance(case.ms, S.FullMasking):
+    elif isinstance(ms, S.FullMasking):
         route = MASK_FULL_STREAMED if form == "host" else MASK_FULL_COMBINED
     else:
-        route = MASK_CHACHA_SPLIT if multi and PD.multi_mask(case.ms, len(masks)) else MASK_CHACHA
-    job = (route, SHARE_PACKED if case.packed else SHARE_ADDITIVE,
-           len(masks) if isinstance(case.ms, S.ChaChaMasking) else 0)
+        route = MASK_CHACHA_SPLIT if multi and PD.multi_mask(ms, n_masks) else MASK_CHACHA
+    job = (route, SHARE_PACKED if packed else SHARE_ADDITIVE, n_masks if isinstance(ms, S.ChaChaMasking) else 0)
     # the i64 rows of packed clerk results have the longest result's length: compacted unless that is B
-    share_len = max(lens) if case.packed else (lens[0] if lens else 0)
-    rec = PD.recipient_record(case.ms, case.ss, case.dimension, [i for i, _ in indexed], share_len, case.m_out,
-                              case.mode, late_resolve="late" in case.tags and route != MASK_CHACHA_SPLIT,
-                              multi_mask=route == MASK_CHACHA_SPLIT)
+    share_len = max(lens) if packed else (lens[0] if lens else 0)
+    rec = PD.recipient_record(ms, ss, dimension, list(indices), share_len, m_out, mode,
+                              late_resolve=late and route != MASK_CHACHA_SPLIT, multi_mask=route == MASK_CHACHA_SPLIT)
     return job, rec
 
 

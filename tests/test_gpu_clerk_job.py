@@ -44,6 +44,23 @@ def _chunks(n):
     return -(-n // CD.ENC_CHUNK)
 
 
+def job_record(record, continued, pay, dim, bound):
+    """sda_clerk_job_last_launch of a call over blobs whose sda_codec_last_launch record is `record`: the slot path
+    encodes by route 1, its grid sized by the host's bound on the dimension (`bound`: blob 0's bytes, or prior_dim),
+    every other path by route 2 over the dimension; `pay`: the call asked for the payload"""
+    slots = record[0] in (CD.SLOTS, CD.SLOTS_GROUPED)
+    route, chunks = ((1, _chunks(bound)) if slots else (2, _chunks(dim))) if pay else (0, 0)
+    return (1 if continued else 0, route, chunks)
+
+
+FINISH_CODEC_RECORD = (CD.NONE, 0, 0, 0)
+
+
+def finish_record(dim):
+    """sda_clerk_job_last_launch of the n_blobs == 0 finish call with a payload"""
+    return (1, 2, _chunks(dim))
+
+
 class Job:
     """blobs on the device, back to back behind 16 bytes of junk, with the host offsets"""
 
@@ -134,15 +151,14 @@ def _run_split(engine, case, split, finish, knobs):
         assert slots or record[0] == (CD.MATRIX32 if CJ.is_field(m) else CD.MATRIX64), record
         # route 1 sizes its grid by the host's bound on the dimension: blob 0's bytes, or prior_dim
         bound = dim if b0 else len(job.blobs[0])
-        route, chunks = ((1, _chunks(bound)) if slots else (2, _chunks(dim))) if pay else (0, 0)
-        assert engine.clerk_job_last_launch() == (1 if b0 else 0, route, chunks), (split, i)
+        assert engine.clerk_job_last_launch() == job_record(record, b0, pay, dim, bound), (split, i)
         b0 += k
     if finish:
         got = engine.clerk_job_dev(m, job.ptr(), [], g.state_ptr(), dim, first_participation=n, prior_dim=dim,
                                    payload_ptr=g.payload_ptr(), payload_cap=len(want_payload))
         assert got == (dim, len(want_payload))
-        assert engine.clerk_job_last_launch() == (1, 2, _chunks(dim))
-        assert engine.codec_last_launch() == (CD.NONE, 0, 0, 0)
+        assert engine.clerk_job_last_launch() == finish_record(dim)
+        assert engine.codec_last_launch() == FINISH_CODEC_RECORD
     state, payload = g.host()
     exp_state, exp_payload = g.expect(want, want_payload)
     assert np.array_equal(state[PAD:PAD + dim], _one_call_reference(engine, case)), (split, finish)
